@@ -27,6 +27,7 @@ RAW = (768, 2560)          # raw camera size -> img 3x384x1280, range image 4x38
 NPTS = 64 * 2048
 PEAK_HBM_GBS = 8000.0          # MI355X_MICROARCH.md: HBM3E 8 TB/s peak (6.3 TB/s measured streaming)
 PEAK_F32_MFMA_TFLOPS = 157.3   # MI355X_MICROARCH.md: v_mfma_f32_32x32x2_f32, dense
+DUMP_BYTES = 64 * 10 ** 6      # --dump-outputs: all .npy files of one run together (headers included)
 
 
 def parse():
@@ -51,7 +52,15 @@ def parse():
     ap.add_argument('--set', action='append', default=[], metavar='MODULE.ATTR=VALUE',
                     help='builder A/B runs: set a switch of efgh_amd (e.g. ops.PLANE_DMA=0) before anything is built; the line '
                          'records it under "switches" (a default run has none)')
-    return ap.parse_args()
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help='write what the LAST timed step of each timed workload returned (forward: the prediction dict; training: '
+                         'losses, prediction dict, and the weights and gradients after the step) as DIR/<name>.npy, float32 / '
+                         'float64, at most %d MB in all (larger arrays: a fixed, seeded sample, see capture_outputs); same '
+                         'arguments -> same inputs and weights, so two builds can be compared output for output' % (DUMP_BYTES // 10 ** 6))
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
+    return a
 
 
 def cpu_model():
@@ -152,6 +161,60 @@ def dump_shapes(prof, path):
         fh.write('mode M N T C | calls ms TFLOP/s\n')
         for key, (n, ms, f) in rows[:40]:
             fh.write('%s | %d %.2f %.1f\n' % (' '.join(map(str, key)), n, ms, f / (ms * 1e-3) / 1e12 if ms > 0 else 0))
+
+
+def capture_outputs(prefix, obj, budget):
+    """--dump-outputs: the tensors in `obj` (nested dicts / lists / tuples; other values are skipped) -> {name: host array}, at most
+    `budget` bytes as .npy files.  Floating tensors become float32 (float64 stays float64), integer and bool tensors float64 (exact
+    below 2**53).  When not everything fits, every array is cut to one common element cap, the largest that fits: an array above it
+    becomes a 1-D sample of `cap` elements, one per equal stratum of its flat index range at an offset drawn from
+    RandomState(crc32(name)), gathered on the device.  The same shapes give the same indices in every run and every build."""
+    import zlib
+    import numpy as np
+    import torch
+    items = []
+
+    def walk(name, v):
+        if torch.is_tensor(v):
+            items.append((name, v.detach()))
+        elif isinstance(v, dict):
+            for k, x in v.items():
+                walk('%s.%s' % (name, k), x)
+        elif isinstance(v, (list, tuple)):
+            for i, x in enumerate(v):
+                walk('%s.%d' % (name, i), x)
+    walk(prefix, obj)
+    wide = lambda t: torch.float64 if t.dtype == torch.float64 or not t.is_floating_point() else torch.float32
+    isz = [torch.empty((), dtype=wide(t)).element_size() for _, t in items]
+    room = budget - 256 * len(items)                  # (an .npy header: 128 bytes for these shapes)
+    fits = lambda cap: sum(min(t.numel(), cap) * b for (_, t), b in zip(items, isz)) <= room
+    lo, hi = 0, max([t.numel() for _, t in items] + [0])
+    while lo < hi:                                    # the largest cap that fits
+        mid = (lo + hi + 1) // 2
+        lo, hi = (mid, hi) if fits(mid) else (lo, mid - 1)
+    assert lo > 0 or not items, 'bench.py --dump-outputs: %d arrays do not fit in %d bytes' % (len(items), budget)
+    out = {}
+    for name, t in items:
+        n = t.numel()
+        if n <= lo:
+            out[name] = t.to(wide(t)).cpu().numpy()
+        else:
+            edges = np.arange(lo + 1, dtype=np.int64) * n // lo
+            off = np.random.RandomState(zlib.crc32(name.encode())).random_sample(lo) * np.diff(edges)
+            idx = torch.from_numpy(edges[:-1] + off.astype(np.int64)).to(t.device)
+            out[name] = t.reshape(-1)[idx].to(wide(t)).cpu().numpy()
+    return out
+
+
+def write_outputs(dumps, path):
+    """--dump-outputs: {name: array} -> path/<name>.npy"""
+    import re
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, arr in dumps.items():
+        np.save(os.path.join(path, re.sub(r'[^A-Za-z0-9_.-]', '_', name) + '.npy'), arr)
+    sys.stderr.write('bench.py: %d arrays (%.1f MB) of the last timed step written to %s\n'
+                     % (len(dumps), sum(v.nbytes for v in dumps.values()) / 2 ** 20, path))
 
 
 def committed_traffic(family, workload='train', launches_per_step=None, kernel=None):
@@ -628,6 +691,7 @@ def main():
     model = EFGHBackbone(args).to(dev)
 
     def timed(fn, steps, warmup):
+        """-> (seconds of `steps` calls of fn, launch profile, what the last call returned)"""
         for _ in range(warmup):
             fn()
         barrier()
@@ -635,8 +699,9 @@ def main():
         ops.PROFILE_WINO2D, ops.PROFILE_WINO2D_GEMM, ops.PROFILE_THIN, ops.PROFILE_DED = [], [], [], []
         lattice.PROFILE = ops.PROFILE_BCL
         t0 = time.perf_counter()
-        for _ in range(steps):
+        for _ in range(steps - 1):
             fn()
+        last = fn()
         barrier()
         dt = max_over_ranks(time.perf_counter() - t0)
         prof = {'gemm': ops.PROFILE, 'wgrad': ops.PROFILE_WGRAD, 'wino': ops.PROFILE_WINO,
@@ -645,7 +710,7 @@ def main():
         ops.PROFILE_THIN = ops.PROFILE_DED = None
         ops.PROFILE = ops.PROFILE_WGRAD = ops.PROFILE_WINO = ops.PROFILE_WINO_WGRAD = ops.PROFILE_BCL = lattice.PROFILE = None
         ops.PROFILE_WINO2D = ops.PROFILE_WINO2D_GEMM = None
-        return dt, prof
+        return dt, prof, last
 
     def attach_serialized(dst, step_fn, workload):
         """Independent branches of the network run on up to four streams (nets/efghbackbone.py, nets/fnet.py; weight gradients on
@@ -662,7 +727,7 @@ def main():
         nser = max(1, min(a.steps, 3))
         bb.SIDE_STREAM, wg, ops.WGRAD_SIDE = False, ops.WGRAD_SIDE, False
         try:
-            _, prof2 = timed(step_fn, nser, 1)
+            _, prof2, _ = timed(step_fn, nser, 1)
         finally:
             bb.SIDE_STREAM, ops.WGRAD_SIDE = True, wg
         if dst is None:
@@ -753,7 +818,10 @@ def main():
 
     out = None
     fwd = None
-    if a.mode == 'fwd' or not a.no_forward_section:
+    run_fwd = a.mode == 'fwd' or not a.no_forward_section
+    dumps = {}                                            # --dump-outputs: each timed workload gets an equal share of DUMP_BYTES
+    dump_budget = DUMP_BYTES // (int(run_fwd) + int(a.mode == 'train'))
+    if run_fwd:
         Bf = a.batch if (a.mode == 'fwd' and a.batch) else 4
         fsets, fcount = load(Bf), [0]
         model.eval()
@@ -763,7 +831,10 @@ def main():
             fcount[0] += 1
             with torch.no_grad():
                 return model(*inp)
-        dt, prof = timed(fstep, a.steps, a.warmup)
+        dt, prof, last = timed(fstep, a.steps, a.warmup)
+        if a.dump_outputs and rank == 0:
+            dumps.update(capture_outputs('fwd', last, dump_budget))
+        del last
         fwd = {'metric': 'frame-pairs/sec EFGHNet forward (384x1280 RGB + 64x2048 range), whole job',
                'value': world * Bf * a.steps / dt, 'unit': 'frame-pairs/s', 'ms_per_step': dt / a.steps * 1e3,
                'workload': 'BASELINE.json configs[1]: EFGHNet forward only (eval), batch=%d per GPU' % Bf,
@@ -784,8 +855,13 @@ def main():
             tcount[0] += 1
             return trainer.step(*inp, gt)
         lat0 = dict(lattice.STATS)
-        dt, prof = timed(tstep, a.steps, a.warmup)
+        dt, prof, last = timed(tstep, a.steps, a.warmup)
         lat1 = dict(lattice.STATS)
+        if a.dump_outputs and rank == 0:
+            # what the caller holds after the step: trainer.step's (losses, prediction) and the model's weights and gradients
+            dumps.update(capture_outputs('train', {'loss': last[0], 'pred': last[1], 'params': trainer.flat.w,
+                                                   'grads': trainer.flat.g}, dump_budget))
+        del last
         if rank == 0:
             out = {
                 'metric': 'frame-pairs/sec EFGHNet fwd+bwd (384x1280 RGB + 64x2048 range), whole job',
@@ -832,6 +908,8 @@ def main():
                }
         out.update({k: v for k, v in fwd.items() if k.startswith('roofline') or k == 'mfma_step_utilisation'})
     if rank == 0:
+        if a.dump_outputs:
+            write_outputs(dumps, a.dump_outputs)
         if world == 1 and not a.no_cpu_baseline:
             out['cpu_baseline'] = cpu_baseline(raw, npts, a.mode)
         if world == 1 and not a.small and not a.no_config_r:

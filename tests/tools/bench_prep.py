@@ -1,6 +1,6 @@
 """sample preparation: GPU (efgh_amd.data) vs the Pillow/numpy path the reference uses, one RELLIS-sized sample"""
-import sys, time
-sys.path.insert(0, '/root/repo')
+import os, sys, time
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import numpy as np
 import torch
 from PIL import Image

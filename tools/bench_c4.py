@@ -1,7 +1,7 @@
 """micro-benchmark: the 4-channel input layers of config S at batch 8 on efgh_c4_conv3x3 / efgh_c4_wgrad vs the generic
 implicit-GEMM kernels (GPU box)"""
-import sys
-sys.path.insert(0, '/root/repo')
+import os, sys
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 import torch.nn as nn
 from efgh_amd import ops

@@ -1,8 +1,8 @@
 """BASELINE configs[0] (the reference's shipped RELLIS configuration: raw 900x1600, 65 536 points, batch 1) on the GPU box:
 eval forward and one training step, for the comparison with the oracle timings in SURVEY 8(d)"""
-import sys
+import os, sys
 import time
-sys.path.insert(0, '/root/repo')
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from efgh_amd import synthetic as syn
 from efgh_amd.losses import EFGHCriterion

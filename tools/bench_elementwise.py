@@ -1,6 +1,6 @@
 """HBM rate of the BatchNorm/activation streaming passes (GPU box)"""
-import sys
-sys.path.insert(0, '/root/repo')
+import os, sys
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from efgh_amd import ops
 

@@ -1,6 +1,6 @@
 """micro-benchmark of the gather-GEMM on representative conv shapes (run on the GPU box)"""
-import sys, time
-sys.path.insert(0, '/root/repo')
+import os, sys, time
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 import torch.nn as nn
 from efgh_amd import ops

@@ -1,6 +1,6 @@
 """time of the batched in-place repack (all packed layouts + their Winograd images) of the full model, tiled vs flat kernel (GPU box)"""
-import sys
-sys.path.insert(0, '/root/repo')
+import os, sys
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from efgh_amd import ops, synthetic as syn
 from efgh_amd.losses import EFGHCriterion

@@ -1,8 +1,8 @@
 """timing of the overlay images at the shipped RELLIS size (900x1600 raw, 65 536 points) on the GPU box"""
 import math
-import sys
+import os, sys
 import time
-sys.path.insert(0, '/root/repo')
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import torch
 from efgh_amd import synthetic as syn

@@ -1,6 +1,6 @@
 """thin (<= 4 channel) layers: VALU kernels vs the MFMA gather-GEMM / wgrad on the same shapes (GPU box)"""
-import sys
-sys.path.insert(0, '/root/repo')
+import os, sys
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 import torch.nn as nn
 from efgh_amd import ops

@@ -1,6 +1,6 @@
 """micro-benchmark: Winograd F(4,3) kernel vs the direct gather-GEMM on the 3x3 layers of config S (GPU box)"""
-import sys
-sys.path.insert(0, '/root/repo')
+import os, sys
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 import torch.nn as nn
 from efgh_amd import ops

@@ -1,7 +1,7 @@
 """one 3x3 layer through the Winograd forward kernel, N launches (for rocprofv3 --pmc passes):
 python tools/bench_wino_one.py B H W Cin Cout [iters]"""
-import sys
-sys.path.insert(0, '/root/repo')
+import os, sys
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch

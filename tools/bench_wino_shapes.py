@@ -1,6 +1,6 @@
 """k_wino43 on one layer shape (64->64, 128->128) at equal pixel counts but different row lengths (L2 locality probe)"""
-import sys
-sys.path.insert(0, '/root/repo')
+import os, sys
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch, torch.nn as nn
 from efgh_amd import ops
 from efgh_amd.nets import layers as L

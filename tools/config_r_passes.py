@@ -1,7 +1,7 @@
 """Per-launch time of the BatchNorm-backward passes inside ONE training iteration of the reference's own configuration
 (900x1600 / 65 536 points / batch 1): which shapes the reduce / apply kernels see there and at what rate (GPU box)."""
-import sys
-sys.path.insert(0, '/root/repo')
+import os, sys
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from efgh_amd import ops, synthetic as syn
 from efgh_amd.losses import EFGHCriterion

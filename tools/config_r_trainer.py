@@ -1,8 +1,8 @@
 """config_r (900x1600 / 65 536 points / batch 1) through Trainer.step (flat parameters, direct gradient writes, fused Adam)
 instead of the reference's loop with stock Adam: the upper bound of what re-homing the optimizer buys that loop (GPU box)."""
-import sys
+import os, sys
 import time
-sys.path.insert(0, '/root/repo')
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import torch
 from efgh_amd import synthetic as syn

@@ -1,11 +1,11 @@
-import sys; sys.path.insert(0, '/root/repo')
+import os, sys; sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import json, torch
 from efgh_amd import synthetic as syn
 from efgh_amd.losses import EFGHCriterion
 from efgh_amd.nets import EFGHBackbone
 from efgh_amd.train import Trainer
 RAW, NPTS = (128, 256), 2048
-manifest = json.load(open('/root/repo/tests/golden/state_dict_manifest.json'))
+manifest = json.load(open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'tests', 'golden', 'state_dict_manifest.json')))
 args = syn.default_args(RAW, 'cuda')
 m = EFGHBackbone(args); m.load_state_dict(syn.synthetic_state_dict(manifest['state_dict'], 1))
 tr = Trainer(m.cuda(), EFGHCriterion(args), lr=float(sys.argv[1]) if len(sys.argv) > 1 else 1e-3)
