@@ -21,13 +21,49 @@
 //                  of a row; a lane reads TWO adjacent floats per ds_read_b64 (256 B contiguous per half-wave: conflict free)
 //                  and feeds them to two MFMA tiles whose rows / columns interleave (tile q holds n = 2 i + q): half the LDS
 //                  instructions of a ds_read_b32 per operand, and the epilogue stores 8 bytes per lane.
-// Arithmetic: v_mfma_f32_32x32x2_f32, exact fp32 products and accumulation, the same k order as the kernels they replace
-// (bit-identical results: tests/test_gpu_ops.py::test_plane_gemm_equals_gather_gemm).
+// Arithmetic (MATH_EXACT): v_mfma_f32_32x32x2_f32, exact fp32 products and accumulation, the same k order as the kernels they
+// replace (bit-identical results: tests/test_gpu_ops.py::test_plane_gemm_equals_gather_gemm).
+//
+// MATH_X6 (efgh_plane_gemm_x6 / efgh_plane_wgrad_x6_batched: PyTorch's fp32 'high' matmul precision): the same ring, images, tiles
+// and grid; after a fragment leaves LDS every fp32 operand is split into three round-to-nearest bf16 pieces x = x0 + x1 + x2
+// (x1 = bf16(x - x0), x2 = bf16(x - x0 - x1); both differences are exact in fp32) and six v_mfma_f32_32x32x16_bf16 products per
+// K16 block - a0 b0 into the main accumulators, a0 b1 + a1 b0 + a1 b1 + a0 b2 + a2 b0 into a second set - accumulate in fp32; the
+// two sets are added once in the epilogue (fixed order: bit-reproducible).  The dropped products (a1 b2, a2 b1, a2 b2) are below
+// 2^-24 of |a b|: fp32-level accuracy (tests/test_gpu_planes_x6.py, profiles/r07_split_accuracy.txt).  Non-finite inputs: a NaN
+// gives NaN outputs as in the exact form; an Inf gives NaN (the residual x - x0 is Inf - Inf), where the exact form gives +-Inf.
+// The bf16 K16 operand of lane l is A[l & 31][k = 8 (l >> 5) + j], j = 0..7; any k permutation shared by both operands is a
+// valid contraction, so the fragments are the exact form's LDS reads in a different register order (see each kernel).
 #include "common.h"
 
 namespace {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+
+enum { MATH_EXACT = 0, MATH_X6 = 1 };
+
+// x[j] = hi[j] + mid[j] + lo[j] to fp32 accuracy (v_cvt_pk_bf16_f32: round to nearest even; NaN stays NaN)
+__device__ __forceinline__ void split3(const float (&x)[8], bf16x8 &hi, bf16x8 &mid, bf16x8 &lo) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const __bf16 h = (__bf16)x[j];
+        const float r1 = x[j] - (float)h;
+        const __bf16 m = (__bf16)r1;
+        hi[j] = h;
+        mid[j] = m;
+        lo[j] = (__bf16)(r1 - (float)m);
+    }
+}
+
+// the six products of one K16 block of one 32 x 32 tile
+__device__ __forceinline__ void mfma_x6(const bf16x8 (&a)[3], const bf16x8 (&b)[3], f32x16 &acc, f32x16 &acc2) {
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[0], acc, 0, 0, 0);
+    acc2 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[1], acc2, 0, 0, 0);
+    acc2 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], b[0], acc2, 0, 0, 0);
+    acc2 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], b[1], acc2, 0, 0, 0);
+    acc2 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[2], acc2, 0, 0, 0);
+    acc2 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[2], b[0], acc2, 0, 0, 0);
+}
 
 constexpr int BM = 128, BN = 128, BK = 32;
 constexpr int STAGE = (BM + BN) * BK;            // floats per ring slot: 32 KiB
@@ -41,7 +77,7 @@ struct PArgs {
     unsigned nbx;
 };
 
-template <int NBUF>
+template <int NBUF, int MATH>
 __global__ void __launch_bounds__(256, NBUF == 2 ? 2 : 1) k_plane_gemm(const PArgs p0) {
     extern __shared__ __attribute__((aligned(1024))) float ring[];          // NBUF x STAGE floats
     PArgs p = p0;
@@ -93,6 +129,15 @@ __global__ void __launch_bounds__(256, NBUF == 2 ? 2 : 1) k_plane_gemm(const PAr
         for (int j = 0; j < 2; ++j)
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    f32x16 acc2[2][2];                          // (MATH_X6: the five small products)
+    if constexpr (MATH == MATH_X6) {
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int j = 0; j < 2; ++j)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) acc2[i][j][r] = 0.f;
+    }
 
     const int nch = p.K / BK;
 #pragma unroll
@@ -116,27 +161,55 @@ __global__ void __launch_bounds__(256, NBUF == 2 ? 2 : 1) k_plane_gemm(const PAr
 #pragma unroll
             for (int j = 0; j < 2; ++j) fb[j] = *reinterpret_cast<const float4 *>(buf + offW[j] + (((g * 2 + lh) ^ swW[j]) << 2));
         };
-        frag(0, a[0], b[0]);
+        if constexpr (MATH == MATH_EXACT) {
+            frag(0, a[0], b[0]);
 #pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            if (g < 3) frag(g + 1, a[(g + 1) & 1], b[(g + 1) & 1]);
-            __builtin_amdgcn_sched_barrier(0);
-            const float4 (&ca)[2] = a[g & 1];
-            const float4 (&cb)[2] = b[g & 1];
+            for (int g = 0; g < 4; ++g) {
+                if (g < 3) frag(g + 1, a[(g + 1) & 1], b[(g + 1) & 1]);
+                __builtin_amdgcn_sched_barrier(0);
+                const float4 (&ca)[2] = a[g & 1];
+                const float4 (&cb)[2] = b[g & 1];
 #pragma unroll
-            for (int i = 0; i < 2; ++i)
+                for (int i = 0; i < 2; ++i)
 #pragma unroll
-                for (int j = 0; j < 2; ++j) {
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(ca[i].x, cb[j].x, acc[i][j], 0, 0, 0);
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(ca[i].y, cb[j].y, acc[i][j], 0, 0, 0);
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(ca[i].z, cb[j].z, acc[i][j], 0, 0, 0);
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(ca[i].w, cb[j].w, acc[i][j], 0, 0, 0);
+                    for (int j = 0; j < 2; ++j) {
+                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(ca[i].x, cb[j].x, acc[i][j], 0, 0, 0);
+                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(ca[i].y, cb[j].y, acc[i][j], 0, 0, 0);
+                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(ca[i].z, cb[j].z, acc[i][j], 0, 0, 0);
+                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(ca[i].w, cb[j].w, acc[i][j], 0, 0, 0);
+                    }
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        } else {
+            // K16 block kb = the quads of groups 2 kb and 2 kb + 1: lane half lh holds quads 4 kb + lh (elements 0..3) and
+            // 4 kb + 2 + lh (elements 4..7) - the 16 k of the block once over the two halves, in the same order for A and W
+#pragma unroll
+            for (int kb = 0; kb < 2; ++kb) {
+                frag(2 * kb, a[0], b[0]);
+                frag(2 * kb + 1, a[1], b[1]);
+                bf16x8 sa[2][3], sb[2][3];
+#pragma unroll
+                for (int i = 0; i < 2; ++i) {
+                    const float xa[8] = {a[0][i].x, a[0][i].y, a[0][i].z, a[0][i].w, a[1][i].x, a[1][i].y, a[1][i].z, a[1][i].w};
+                    const float xb[8] = {b[0][i].x, b[0][i].y, b[0][i].z, b[0][i].w, b[1][i].x, b[1][i].y, b[1][i].z, b[1][i].w};
+                    split3(xa, sa[i][0], sa[i][1], sa[i][2]);
+                    split3(xb, sb[i][0], sb[i][1], sb[i][2]);
                 }
-            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int i = 0; i < 2; ++i)
+#pragma unroll
+                    for (int j = 0; j < 2; ++j) mfma_x6(sa[i], sb[j], acc[i][j], acc2[i][j]);
+            }
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // (the fragment reads of this step are retired before the next barrier)
     }
 
+    if constexpr (MATH == MATH_X6) {
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int j = 0; j < 2; ++j) acc[i][j] += acc2[i][j];
+    }
     // ---- epilogue: bare products, one 128-B row segment per half-wave and store.  A workgroup-uniform switch picks the body: a
     // whole tile walks its rows with one pointer add per row (register r -> row (r & 3) + 8 (r >> 2) + 4 lh: steps of 1, 1, 1, 5);
     // the last, ragged tile of a plane tests every row
@@ -184,7 +257,7 @@ constexpr int WSTAGE = TM * (TN + TK);            // 32 KiB per ring slot
 
 __device__ __attribute__((aligned(512))) float g_plane_zero[128];          // 512 B of zeros: the source of rows past the end of a row chunk
 
-template <int NBUF>
+template <int NBUF, int MATH>
 __global__ void __launch_bounds__(256, NBUF == 2 ? 2 : 1) k_plane_wgrad(const PWArgs p0) {
     extern __shared__ __attribute__((aligned(1024))) float ring[];
     PWArgs p = p0;
@@ -230,6 +303,15 @@ __global__ void __launch_bounds__(256, NBUF == 2 ? 2 : 1) k_plane_wgrad(const PW
         for (int j = 0; j < 2; ++j)
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    f32x16 acc2[2][2];                          // (MATH_X6: the five small products)
+    if constexpr (MATH == MATH_X6) {
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int j = 0; j < 2; ++j)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) acc2[i][j][r] = 0.f;
+    }
 
     const int nst = (int)((mend - mbeg + TM - 1) / TM);
 #pragma unroll
@@ -244,6 +326,32 @@ __global__ void __launch_bounds__(256, NBUF == 2 ? 2 : 1) k_plane_wgrad(const PW
         asm volatile("" ::: "memory");
         if (s + NBUF - 1 < nst) issue(mbeg + (long long)(s + NBUF - 1) * TM, (s + NBUF - 1) % NBUF);
         const float *Gs = ring + (s % NBUF) * WSTAGE + lh * 128;
+        if constexpr (MATH == MATH_X6) {
+            // K16 block kb = rows 16 kb .. 16 kb + 15 of the step: lane half lh gathers rows 16 kb + 2 j + lh (element j) of its two
+            // columns with the exact form's ds_read_b64s; .x feeds tile 0, .y tile 1 (n = 2 i + q / k = 2 j + q' as below)
+#pragma unroll
+            for (int kb = 0; kb < 2; ++kb) {
+                float xg[2][8], xa[2][8];
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    const float2 vg = *reinterpret_cast<const float2 *>(Gs + (8 * kb + j) * 256 + gx);
+                    const float2 va = *reinterpret_cast<const float2 *>(Gs + (8 * kb + j) * 256 + ax);
+                    xg[0][j] = vg.x; xg[1][j] = vg.y;
+                    xa[0][j] = va.x; xa[1][j] = va.y;
+                }
+                bf16x8 sg[2][3], sa[2][3];
+#pragma unroll
+                for (int q = 0; q < 2; ++q) {
+                    split3(xg[q], sg[q][0], sg[q][1], sg[q][2]);
+                    split3(xa[q], sa[q][0], sa[q][1], sa[q][2]);
+                }
+#pragma unroll
+                for (int q = 0; q < 2; ++q)
+#pragma unroll
+                    for (int r = 0; r < 2; ++r) mfma_x6(sg[q], sa[r], acc[q][r], acc2[q][r]);
+            }
+            continue;
+        }
         float2 g[2], a[2];
         g[0] = *reinterpret_cast<const float2 *>(Gs + gx);
         a[0] = *reinterpret_cast<const float2 *>(Gs + ax);
@@ -262,6 +370,12 @@ __global__ void __launch_bounds__(256, NBUF == 2 ? 2 : 1) k_plane_wgrad(const PW
             __builtin_amdgcn_sched_barrier(0);
         }
     }
+    if constexpr (MATH == MATH_X6) {
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int j = 0; j < 2; ++j) acc[i][j] += acc2[i][j];
+    }
     // tile (q, q'): D row i <-> n = 2 i + q, column j <-> k = 2 j + q' of the wave's 64 x 64 block; lanes run along k: 8 bytes each
 #pragma unroll
     for (int q = 0; q < 2; ++q) {
@@ -274,7 +388,7 @@ __global__ void __launch_bounds__(256, NBUF == 2 ? 2 : 1) k_plane_wgrad(const PW
     }
 }
 
-std::atomic<unsigned long long> g_raised[4];
+std::atomic<unsigned long long> g_raised[8];          // [MATH][0: gemm NBUF 2, 1: gemm NBUF 3, 2: wgrad NBUF 2, 3: wgrad NBUF 3]
 
 int plane_nbuf() { return 2; }          // two 32-KiB slots, two workgroups per CU: 7 % / 3 % faster than a three-slot ring with one (tools/bench_planes.py)
 
@@ -289,14 +403,8 @@ bool gemm_ok(const efgh_gemm_desc *d) {
     return true;
 }
 
-}  // namespace
-
-
-extern "C" int efgh_plane_gemm_supported(const efgh_gemm_desc *d) { return gemm_ok(d) ? 1 : 0; }
-
-/* out[b][m][n] = sum_k A[b][m][k] * W[b][n][k] for d->nbatch problems (mode 0, bare products): the LDS-DMA staged form of
- * efgh_gather_gemm for the launches efgh_plane_gemm_supported accepts; bit-identical results.  nbuf: ring slots (2 or 3; 0 = default) */
-extern "C" int efgh_plane_gemm(const efgh_gemm_desc *d, int32_t nbuf, void *stream_) {
+template <int MATH>
+int plane_gemm(const efgh_gemm_desc *d, int32_t nbuf, void *stream_) {
     hipStream_t st = (hipStream_t)stream_;
     EFGH_CHECK_ARG(gemm_ok(d));
     if (nbuf == 0) nbuf = plane_nbuf();
@@ -312,31 +420,32 @@ extern "C" int efgh_plane_gemm(const efgh_gemm_desc *d, int32_t nbuf, void *stre
     const dim3 grid((unsigned)(a.nbx * nby), (unsigned)nb);
     const size_t lds = (size_t)nbuf * STAGE * sizeof(float);
     if (nbuf == 2) {
-        if (!efgh_raise_lds_once(g_raised[0], (const void *)k_plane_gemm<2>, (int)lds)) {
+        if (!efgh_raise_lds_once(g_raised[4 * MATH + 0], (const void *)k_plane_gemm<2, MATH>, (int)lds)) {
             efgh_set_error("%s:%d: cannot raise the dynamic LDS limit of k_plane_gemm", __FILE__, __LINE__);
             return EFGH_E_LAUNCH;
         }
-        k_plane_gemm<2><<<grid, 256, lds, st>>>(a);
+        k_plane_gemm<2, MATH><<<grid, 256, lds, st>>>(a);
     } else {
-        if (!efgh_raise_lds_once(g_raised[1], (const void *)k_plane_gemm<3>, (int)lds)) {
+        if (!efgh_raise_lds_once(g_raised[4 * MATH + 1], (const void *)k_plane_gemm<3, MATH>, (int)lds)) {
             efgh_set_error("%s:%d: cannot raise the dynamic LDS limit of k_plane_gemm", __FILE__, __LINE__);
             return EFGH_E_LAUNCH;
         }
-        k_plane_gemm<3><<<grid, 256, lds, st>>>(a);
+        k_plane_gemm<3, MATH><<<grid, 256, lds, st>>>(a);
     }
     EFGH_CHECK_LAUNCH();
     return EFGH_OK;
 }
 
 // row chunks that fill rounds of the 512 resident workgroups (efgh_round_chunks, common.h): a 512 x 512-channel layer has 16 (n, c)
-// blocks x 36 planes = 576 workgroups per chunk - one chunk alone runs a round and an eighth
-static long long plane_wgrad_chunks(const efgh_gemm_desc *d, int nbatch, long long *chunk_out) {
+// blocks x 36 planes = 576 workgroups per chunk - one chunk alone runs a round and an eighth.  (Both precisions run at two workgroups
+// per CU and share these chunks, so efgh_plane_wgrad_workspace serves both.)
+long long plane_wgrad_chunks(const efgh_gemm_desc *d, int nbatch, long long *chunk_out) {
     const long long blocks = (long long)(d->C / TK) * (d->N / TN) * nbatch;
-    static const int occ = efgh_wg_per_cu((const void *)k_plane_wgrad<2>, 256, (size_t)2 * WSTAGE * sizeof(float));
+    static const int occ = efgh_wg_per_cu((const void *)k_plane_wgrad<2, MATH_EXACT>, 256, (size_t)2 * WSTAGE * sizeof(float));
     return efgh_round_chunks(d->M, blocks, occ, TM, 256, (double)nbatch * d->N * d->C, chunk_out);
 }
 
-static bool wgrad_ok(const efgh_gemm_desc *d, int64_t ldg) {
+bool wgrad_ok(const efgh_gemm_desc *d, int64_t ldg) {
     if (!d || d->mode != 0 || d->T != 1 || !d->A) return false;
     if (d->C % TK || d->N % TN || d->M < 1 || d->lda % 4 || ldg % 4) return false;
     if (((uintptr_t)d->A) & 15) return false;
@@ -344,21 +453,9 @@ static bool wgrad_ok(const efgh_gemm_desc *d, int64_t ldg) {
     return nb <= 65535 && (nb == 1 || d->batch_stride_a % 4 == 0);
 }
 
-extern "C" int efgh_plane_wgrad_supported(const efgh_gemm_desc *d, int64_t ldg) { return wgrad_ok(d, ldg) ? 1 : 0; }
-
-/* floats of scratch efgh_plane_wgrad_batched needs (0: a single row chunk writes dWp directly) */
-extern "C" int64_t efgh_plane_wgrad_workspace(const efgh_gemm_desc *d) {
-    if (!wgrad_ok(d, 4)) return 0;
-    const int nb = d->nbatch > 1 ? d->nbatch : 1;
-    const long long zs = plane_wgrad_chunks(d, nb, nullptr);
-    return zs > 1 ? zs * nb * (int64_t)d->N * d->C : 0;
-}
-
-/* dWp[b][n][c] = sum_m G[b][m][n] * A[b][m][c]: the LDS-DMA staged form of efgh_gather_wgrad_batched (same arguments, same
- * row-chunk partials folded in chunk order; the chunks are sized to fill rounds of resident workgroups) for the launches
- * efgh_plane_wgrad_supported accepts */
-extern "C" int efgh_plane_wgrad_batched(const efgh_gemm_desc *d, const float *G, int64_t ldg, int64_t batch_stride_g, float *dWp,
-                                        int64_t batch_stride_dw, float *workspace, int32_t nbuf, void *stream_) {
+template <int MATH>
+int plane_wgrad(const efgh_gemm_desc *d, const float *G, int64_t ldg, int64_t batch_stride_g, float *dWp, int64_t batch_stride_dw,
+                float *workspace, int32_t nbuf, void *stream_) {
     hipStream_t st = (hipStream_t)stream_;
     EFGH_CHECK_ARG(wgrad_ok(d, ldg) && G && dWp && (((uintptr_t)G) & 15) == 0 && (((uintptr_t)dWp) & 15) == 0);
     const int nb = d->nbatch > 1 ? d->nbatch : 1;
@@ -380,19 +477,55 @@ extern "C" int efgh_plane_wgrad_batched(const efgh_gemm_desc *d, const float *G,
     const dim3 grid((unsigned)(zs * a.kt * a.nt), (unsigned)nb);
     const size_t lds = (size_t)nbuf * WSTAGE * sizeof(float);
     if (nbuf == 2) {
-        if (!efgh_raise_lds_once(g_raised[2], (const void *)k_plane_wgrad<2>, (int)lds)) {
+        if (!efgh_raise_lds_once(g_raised[4 * MATH + 2], (const void *)k_plane_wgrad<2, MATH>, (int)lds)) {
             efgh_set_error("%s:%d: cannot raise the dynamic LDS limit of k_plane_wgrad", __FILE__, __LINE__);
             return EFGH_E_LAUNCH;
         }
-        k_plane_wgrad<2><<<grid, 256, lds, st>>>(a);
+        k_plane_wgrad<2, MATH><<<grid, 256, lds, st>>>(a);
     } else {
-        if (!efgh_raise_lds_once(g_raised[3], (const void *)k_plane_wgrad<3>, (int)lds)) {
+        if (!efgh_raise_lds_once(g_raised[4 * MATH + 3], (const void *)k_plane_wgrad<3, MATH>, (int)lds)) {
             efgh_set_error("%s:%d: cannot raise the dynamic LDS limit of k_plane_wgrad", __FILE__, __LINE__);
             return EFGH_E_LAUNCH;
         }
-        k_plane_wgrad<3><<<grid, 256, lds, st>>>(a);
+        k_plane_wgrad<3, MATH><<<grid, 256, lds, st>>>(a);
     }
     if (zs > 1) efgh_launch_fold_splits(workspace, (int)zs, plane, dWp, st);
     EFGH_CHECK_LAUNCH();
     return EFGH_OK;
+}
+
+}  // namespace
+
+
+extern "C" int efgh_plane_gemm_supported(const efgh_gemm_desc *d) { return gemm_ok(d) ? 1 : 0; }
+
+/* out[b][m][n] = sum_k A[b][m][k] * W[b][n][k] for d->nbatch problems (mode 0, bare products): the LDS-DMA staged form of
+ * efgh_gather_gemm for the launches efgh_plane_gemm_supported accepts; bit-identical results.  nbuf: ring slots (2 or 3; 0 = default) */
+extern "C" int efgh_plane_gemm(const efgh_gemm_desc *d, int32_t nbuf, void *stream_) { return plane_gemm<MATH_EXACT>(d, nbuf, stream_); }
+
+/* efgh_plane_gemm with the three-way bf16 split (MATH_X6, top of this file): the same arguments and launches */
+extern "C" int efgh_plane_gemm_x6(const efgh_gemm_desc *d, int32_t nbuf, void *stream_) { return plane_gemm<MATH_X6>(d, nbuf, stream_); }
+
+extern "C" int efgh_plane_wgrad_supported(const efgh_gemm_desc *d, int64_t ldg) { return wgrad_ok(d, ldg) ? 1 : 0; }
+
+/* floats of scratch efgh_plane_wgrad_batched / efgh_plane_wgrad_x6_batched need (0: a single row chunk writes dWp directly) */
+extern "C" int64_t efgh_plane_wgrad_workspace(const efgh_gemm_desc *d) {
+    if (!wgrad_ok(d, 4)) return 0;
+    const int nb = d->nbatch > 1 ? d->nbatch : 1;
+    const long long zs = plane_wgrad_chunks(d, nb, nullptr);
+    return zs > 1 ? zs * nb * (int64_t)d->N * d->C : 0;
+}
+
+/* dWp[b][n][c] = sum_m G[b][m][n] * A[b][m][c]: the LDS-DMA staged form of efgh_gather_wgrad_batched (same arguments, same
+ * row-chunk partials folded in chunk order; the chunks are sized to fill rounds of resident workgroups) for the launches
+ * efgh_plane_wgrad_supported accepts */
+extern "C" int efgh_plane_wgrad_batched(const efgh_gemm_desc *d, const float *G, int64_t ldg, int64_t batch_stride_g, float *dWp,
+                                        int64_t batch_stride_dw, float *workspace, int32_t nbuf, void *stream_) {
+    return plane_wgrad<MATH_EXACT>(d, G, ldg, batch_stride_g, dWp, batch_stride_dw, workspace, nbuf, stream_);
+}
+
+/* efgh_plane_wgrad_batched with the three-way bf16 split (MATH_X6): the same arguments, chunks and fold */
+extern "C" int efgh_plane_wgrad_x6_batched(const efgh_gemm_desc *d, const float *G, int64_t ldg, int64_t batch_stride_g, float *dWp,
+                                           int64_t batch_stride_dw, float *workspace, int32_t nbuf, void *stream_) {
+    return plane_wgrad<MATH_X6>(d, G, ldg, batch_stride_g, dWp, batch_stride_dw, workspace, nbuf, stream_);
 }

@@ -132,6 +132,17 @@ class GemmLayerFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, bias, gamma, beta, residual, spec, out_target=None):
+        # the plane-GEMM precision (ops.planes_split_active) is resolved ONCE per layer and step: the backward restores it, so the
+        # forward and backward of a step use one mode even if torch's switch changes in between
+        ctx.planes_split = ops.planes_split_active()
+        old, ops.TLS.planes_split = ops.TLS.planes_split, ctx.planes_split
+        try:
+            return GemmLayerFn._forward(ctx, x, weight, bias, gamma, beta, residual, spec, out_target)
+        finally:
+            ops.TLS.planes_split = old
+
+    @staticmethod
+    def _forward(ctx, x, weight, bias, gamma, beta, residual, spec, out_target=None):
         ctx.set_materialize_grads(False)      # an unused passthrough alias must arrive as None, not as a zero tensor to add
         ctx.xsrc = getattr(x, '_efgh_bnsrc', None)           # the BatchNorm layer that produced x (BnSrc), if any
         lazy = getattr(x, '_efgh_lazy', None)                # x is a RAW BatchNorm output whose activation this layer applies itself
@@ -260,10 +271,12 @@ class GemmLayerFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy, dskip=None):
         old, ops.TLS.train_step = ops.TLS.train_step, ctx.train_step
+        old_split, ops.TLS.planes_split = ops.TLS.planes_split, ctx.planes_split
         try:
             return GemmLayerFn._backward(ctx, dy, dskip)
         finally:
             ops.TLS.train_step = old
+            ops.TLS.planes_split = old_split
 
     @staticmethod
     def _backward(ctx, dy, dskip=None):

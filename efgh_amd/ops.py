@@ -69,12 +69,14 @@ def bump_epoch(holder=None):
 class _ThreadState(threading.local):
     """per-thread switches (two Python threads may drive two models on one GPU; autograd's device thread is a third):
     train_step - inside a training step (forward: set by EFGHBackbone.forward; backward: GemmLayerFn.backward restores the value
-    its forward saw); w2v_wanted - set by GemmLayerFn.forward around its launches when the weight gradient will be asked for"""
+    its forward saw); planes_split - the plane-GEMM precision of the layer being run (GemmLayerFn: resolved once in its forward,
+    restored in its backward); w2v_wanted - set by GemmLayerFn.forward around its launches when the weight gradient will be asked for"""
 
     def __init__(self):
         self.train_step = False
         self.w2v_wanted = False
         self.nbt_pending = None        # see bn_tick
+        self.planes_split = None       # see planes_split_active: the mode GemmLayerFn resolved for this layer (None: outside a layer)
 
 
 TLS = _ThreadState()
@@ -654,6 +656,24 @@ PLANE_DMA = True                # the 36 planes of a 2-D Winograd layer on the L
 PLANE_DMA_NBUF = 0              # ring slots (0: the library's default; 2 or 3 for A/B runs, tools/bench_planes.py)
 PROFILE_WINO2D = None           # bench.py: whole 2-D Winograd layers (three launches), direct-form FLOPs
 PROFILE_WINO2D_GEMM = None      # bench.py: their batched GEMM launches alone, EXECUTED FLOPs (2*36*T*C*N)
+PLANES_SPLIT = None             # the planes above with a three-way bf16 split (efgh_plane_gemm_x6 / efgh_plane_wgrad_x6_batched):
+                                # None follows torch's fp32 matmul precision switch, True / False force the mode (planes_split_active)
+PLANE_SPLIT_HITS = [0, 0]       # (tests: split plane launches - forward / data gradient, weight gradient)
+
+
+def planes_split_active():
+    """the plane-GEMM precision asked for now: ops.PLANES_SPLIT when set, else torch's fp32 matmul switch -
+    `torch.set_float32_matmul_precision('high' / 'medium')`, `torch.backends.fp32_precision = 'tf32'` and
+    `torch.backends.cuda.matmul.fp32_precision = 'tf32'` all leave torch.backends.cuda.matmul.fp32_precision == 'tf32'.
+    (Not torch.get_float32_matmul_precision(): it raises once both of torch's APIs have been used.)"""
+    if PLANES_SPLIT is not None:
+        return bool(PLANES_SPLIT)
+    return torch.backends.cuda.matmul.fp32_precision == 'tf32'
+
+
+def _planes_split_now():
+    m = TLS.planes_split
+    return planes_split_active() if m is None else m
 
 
 def _batched_plain_gemm(A3, W3, out3, rows, C, N):
@@ -667,7 +687,11 @@ def _batched_plain_gemm(A3, W3, out3, rows, C, N):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
     if PLANE_DMA and _L().efgh_plane_gemm_supported(ctypes.byref(g)):
-        _C.check(_L().efgh_plane_gemm(ctypes.byref(g), c_int32(PLANE_DMA_NBUF), _st()))      # LDS-DMA staged (planes.hip)
+        if _planes_split_now():
+            PLANE_SPLIT_HITS[0] += 1
+            _C.check(_L().efgh_plane_gemm_x6(ctypes.byref(g), c_int32(PLANE_DMA_NBUF), _st()))
+        else:
+            _C.check(_L().efgh_plane_gemm(ctypes.byref(g), c_int32(PLANE_DMA_NBUF), _st()))      # LDS-DMA staged (planes.hip)
     else:
         _C.check(_L().efgh_gather_gemm(ctypes.byref(g), _st()))
     if PROFILE_WINO2D_GEMM is not None:
@@ -1299,9 +1323,12 @@ def gather_wgrad(A, lda, C, T, N, M, G, ldg, dWp, mode=0, geom=None, table=None,
             f0, f1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             f0.record()
         if PLANE_DMA and _L().efgh_plane_wgrad_supported(ctypes.byref(g), c_int64(36 * N)):
-            _C.check(_L().efgh_plane_wgrad_batched(ctypes.byref(g), ptr(Gy), c_int64(36 * N), c_int64(N), ptr(S), c_int64(N * C),
-                                                   ptr(_scratch(_L().efgh_plane_wgrad_workspace(ctypes.byref(g)), dev)),
-                                                   c_int32(PLANE_DMA_NBUF), _st()))
+            split = _planes_split_now()
+            if split:
+                PLANE_SPLIT_HITS[1] += 1
+            fn = _L().efgh_plane_wgrad_x6_batched if split else _L().efgh_plane_wgrad_batched
+            _C.check(fn(ctypes.byref(g), ptr(Gy), c_int64(36 * N), c_int64(N), ptr(S), c_int64(N * C),
+                        ptr(_scratch(_L().efgh_plane_wgrad_workspace(ctypes.byref(g)), dev)), c_int32(PLANE_DMA_NBUF), _st()))
         else:
             _C.check(_L().efgh_gather_wgrad_batched(ctypes.byref(g), ptr(Gy), c_int64(36 * N), c_int64(N), ptr(S), c_int64(N * C),
                                                     ptr(_scratch(_L().efgh_gather_wgrad_workspace(ctypes.byref(g)), dev)), _st()))

@@ -2,6 +2,12 @@
 
     python -m efgh_amd.run [--device I | --all-devices] main.py configs/train_rellis.yaml        # one GPU
     python -m efgh_amd.run --gpus N main.py configs/train_rellis.yaml                            # N GPUs, one process each
+    python -m efgh_amd.run --fp32-precision high main.py configs/train_rellis.yaml               # fp32 'high' matmul precision
+
+`--fp32-precision {highest,high}` calls `torch.set_float32_matmul_precision(...)` in every process that runs the script (the
+`--gpus N` children included: they get the launcher's own arguments) before the script starts - what a script of one's own
+would do with one line.  Under 'high' the 36 Winograd-domain planes of the 2-D F(4x4,3x3) layers run on the split-bf16 kernels
+(ops.planes_split_active); without the flag torch's default ('highest': exact fp32) stays.
 
 The reference binds its model and criterion by module name (`import nets`, `import losses`, main.py:14-15;
 `nets.__dict__[arch + 'Backbone']`, `losses.__dict__[arch + 'Criterion']`, main.py:126,129).  This launcher installs
@@ -340,12 +346,35 @@ def child_setup(rest=()):
     return rank, world
 
 
+FP32_PRECISIONS = ('highest', 'high')
+
+
+def _fp32_precision(v):
+    if v not in FP32_PRECISIONS:
+        raise SystemExit('efgh_amd.run: --fp32-precision %s: expected one of %s' % (v, ', '.join(FP32_PRECISIONS)))
+    return v
+
+
+def apply_fp32_precision(precision):
+    """torch's fp32 matmul switch for this process (None: left as it is)"""
+    if precision is not None:
+        import torch
+        torch.set_float32_matmul_precision(precision)
+
+
 def parse(argv):
-    device, pin, gpus = 0, True, 1
+    """-> (device, pin, gpus, script, script arguments, fp32 precision or None)"""
+    device, pin, gpus, precision = 0, True, 1, None
     i = 0
     while i < len(argv):
         a = argv[i]
-        if a in ('--device', '--gpus') and i + 1 < len(argv):
+        if a == '--fp32-precision' and i + 1 < len(argv):
+            precision = _fp32_precision(argv[i + 1])
+            i += 2
+        elif a.startswith('--fp32-precision='):
+            precision = _fp32_precision(a.split('=', 1)[1])
+            i += 1
+        elif a in ('--device', '--gpus') and i + 1 < len(argv):
             if a == '--device':
                 device = int(argv[i + 1])
             else:
@@ -366,13 +395,14 @@ def parse(argv):
         else:
             break
     if i >= len(argv):
-        raise SystemExit('usage: python -m efgh_amd.run [--gpus N | --device I | --all-devices] <script.py> [script arguments...]')
-    return device, pin, gpus, argv[i], argv[i + 1:]
+        raise SystemExit('usage: python -m efgh_amd.run [--gpus N | --device I | --all-devices] [--fp32-precision {highest,high}] '
+                         '<script.py> [script arguments...]')
+    return device, pin, gpus, argv[i], argv[i + 1:], precision
 
 
 def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
-    device, pin, gpus, script, rest = parse(argv)
+    device, pin, gpus, script, rest, precision = parse(argv)
     if not os.path.isfile(script):
         raise SystemExit('efgh_amd.run: no such script: %s' % script)
     child = os.environ.get('EFGH_RUN_CHILD') == '1' and 'RANK' in os.environ
@@ -387,6 +417,7 @@ def main(argv=None):
         pin_one_device(device)
     install_aliases()
     install_loop_rebinds()
+    apply_fp32_precision(precision)
     script = os.path.abspath(script)
     sys.argv = [script] + list(rest)
     sys.path.insert(0, os.path.dirname(script))

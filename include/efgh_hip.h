@@ -47,7 +47,9 @@ const char *efgh_last_error(void);
  *      EFGH_WROTE_OUT when they left the gradient in the caller's layout themselves; efgh_fold_unpack_arm / _disarm (a thread-local
  *      descriptor consumed by the NEXT call: hidden state in an interface that promises none) are removed.  New:
  *      efgh_wino2d_input_act, efgh_wino2d_bwd_transforms(_pooled) (BatchNorm apply / backward apply inside the 2-D Winograd
- *      transforms); efgh_splat_gather / efgh_splat_bwd take `normalize` (args['bcn_use_norm'] of the reference's E net). */
+ *      transforms); efgh_splat_gather / efgh_splat_bwd take `normalize` (args['bcn_use_norm'] of the reference's E net).
+ *      Added later WITHOUT moving the number (no existing signature or struct changed): efgh_plane_gemm_x6,
+ *      efgh_plane_wgrad_x6_batched (the plane GEMMs with a three-way bf16 split: fp32 'high' matmul precision). */
 #define EFGH_ABI_VERSION 3
 int efgh_version(void);
 
@@ -610,6 +612,15 @@ int efgh_plane_wgrad_supported(const efgh_gemm_desc *d, int64_t ldg);
 int64_t efgh_plane_wgrad_workspace(const efgh_gemm_desc *d);
 int efgh_plane_wgrad_batched(const efgh_gemm_desc *d, const float *G, int64_t ldg, int64_t batch_stride_g, float *dWp,
                              int64_t batch_stride_dw, float *workspace, int32_t nbuf, void *stream);
+
+/* The same two GEMMs with every fp32 operand split into three round-to-nearest bf16 pieces (x = x0 + x1 + x2) and six
+ * v_mfma_f32_32x32x16_bf16 products per 16-deep block (a0b0 | a0b1 a1b0 a1b1 a0b2 a2b0, two fp32 accumulator sets added in a
+ * fixed order): fp32-level accuracy, bit-reproducible run to run, NOT bit-identical to the exact forms.  They accept exactly the
+ * launches efgh_plane_gemm_supported / efgh_plane_wgrad_supported accept; the weight gradient uses efgh_plane_wgrad_workspace.
+ * Non-finite inputs: a NaN gives NaN outputs; an Inf gives NaN where the exact forms give +-Inf (its residual is Inf - Inf). */
+int efgh_plane_gemm_x6(const efgh_gemm_desc *d, int32_t nbuf, void *stream);
+int efgh_plane_wgrad_x6_batched(const efgh_gemm_desc *d, const float *G, int64_t ldg, int64_t batch_stride_g, float *dWp,
+                                int64_t batch_stride_dw, float *workspace, int32_t nbuf, void *stream);
 
 /* stride-2 3x3 transposed conv with <= 4 output channels (G's depth / mask heads, gnet.py:56-68) as
  * ONE gather-GEMM over the input pixels (Y [B*Hin*Win][ldy], column (kh*3+kw)*O+o) + this fold:
