@@ -34,6 +34,8 @@ struct KArgs {
     int Ho, Wo, osh, osw, oh0, ow0;
     const int *table;
     const float *W; int N;
+    int tld;                   // mode 4: row stride of the neighbour table (efgh_blur_r_gemm; in the padding in front of M: the
+                               // layout of every other field, and the code of the other modes, stay as they were)
     long long M; const int *M_dev;
     const float *bias, *scale, *shift, *residual; int64_t ldr;
     int act; float slope;
@@ -190,6 +192,7 @@ k_gather_gemm(const KArgs p_in) {
         amask[q] = 0;
         if (ok) {
             if (MODE == 0) { abase[q] = m * p.lda; amask[q] = 1; }
+            else if (MODE == 4) { abase[q] = m * p.tld; amask[q] = 1; }
             else if (MODE == 2) {
                 abase[q] = m * 16;
                 amask[q] = 0xFFFFu;
@@ -260,7 +263,7 @@ k_gather_gemm(const KArgs p_in) {
 #pragma unroll
             for (int q = 0; q < NA; ++q) {
                 float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-                if (kin && (MODE == 2 ? ((amask[q] >> t) & 1u) : amask[q])) {
+                if (kin && (MODE == 2 ? ((amask[q] >> t) & 1u) : amask[q])) {      // (mode 4: every tap of the F-wide row)
                     if (MODE == 0) {
                         v = *reinterpret_cast<const float4 *>(p.A + abase[q] + kk);
                     } else {
@@ -644,9 +647,10 @@ extern "C" int32_t efgh_gather_gemm_grid_m(int64_t M, int32_t N) {
     return (int32_t)((M + bm - 1) / bm);
 }
 
-static int fill_args(const efgh_gemm_desc *d, KArgs &a) {
+// tld > 0: a blur through a neighbour table of F = d->T taps and row stride tld (efgh_blur_r_gemm: mode 4, any tap count)
+static int fill_args(const efgh_gemm_desc *d, KArgs &a, int tld = 0) {
     EFGH_CHECK_ARG(d && d->A && d->W && d->out);
-    EFGH_CHECK_ARG(d->C > 0 && d->C % 4 == 0 && d->T >= 1 && (d->T <= 16 || d->mode == 3));
+    EFGH_CHECK_ARG(d->C > 0 && d->C % 4 == 0 && d->T >= 1 && (d->T <= 16 || d->mode == 3 || tld > 0));
     EFGH_CHECK_ARG(d->N >= 1 && d->M >= 1 && d->lda % 4 == 0);
     EFGH_CHECK_ARG((((uintptr_t)d->A) & 15) == 0 && (((uintptr_t)d->W) & 15) == 0);
     EFGH_CHECK_ARG(d->mode >= 0 && d->mode <= 3);
@@ -674,7 +678,9 @@ static int fill_args(const efgh_gemm_desc *d, KArgs &a) {
         EFGH_CHECK_ARG(d->M == (int64_t)d->B * d->Hv * d->Wv);
         EFGH_CHECK_ARG(d->osh >= 1 && d->osw >= 1 && d->Ho > 0 && d->Wo > 0);
     }
-    if (d->mode == 2) EFGH_CHECK_ARG(d->table != nullptr && d->batch_stride_table >= 0 && (int64_t)d->batch_stride_table * (a.nbatch - 1) + d->T <= 16);
+    a.tld = tld;
+    if (tld > 0) EFGH_CHECK_ARG(d->mode == 2 && d->table != nullptr && tld >= d->T && a.nbatch == 1 && !d->table_alias_mask);
+    else if (d->mode == 2) EFGH_CHECK_ARG(d->table != nullptr && d->batch_stride_table >= 0 && (int64_t)d->batch_stride_table * (a.nbatch - 1) + d->T <= 16);
     if (d->mode == 0) EFGH_CHECK_ARG(d->T == 1);
     if (d->mode == 3) EFGH_CHECK_ARG(d->B > 0 && d->Hin == d->T && d->Win > 0 && d->Wv > 0 && d->M == (int64_t)d->B * d->Wv);
     return EFGH_OK;
@@ -689,6 +695,20 @@ extern "C" int efgh_gather_gemm(const efgh_gemm_desc *d, void *stream_) {
     else if (d->mode == 1) rc = dispatch<1>(a, st);
     else if (d->mode == 2) rc = dispatch<2>(a, st);
     else rc = dispatch<3>(a, st);
+    if (rc != EFGH_OK) return rc;
+    EFGH_CHECK_LAUNCH();
+    return EFGH_OK;
+}
+
+/* the BCL blur at any neighbourhood radius (bilateralNN.py:240-246 with filter size F = (r+1)^4 - r^4, generate_data.py:44-52):
+ * out[m][n] = act(sum_{t<F,c<C} A[table[m*ld + t]][c] * W[n][t*C + c] + bias[n]), a missing neighbour (-1) reads zeros.  The
+ * register-staged gather-GEMM of mode 2 with the table row stride as a parameter (mode 4); d->mode must be 2, d->T = F. */
+extern "C" int efgh_blur_r_gemm(const efgh_gemm_desc *d, int32_t ld, void *stream_) {
+    KArgs a;
+    EFGH_CHECK_ARG(d && ld > 0);
+    int rc = fill_args(d, a, ld);
+    if (rc != EFGH_OK) return rc;
+    rc = dispatch<4>(a, (hipStream_t)stream_);
     if (rc != EFGH_OK) return rc;
     EFGH_CHECK_LAUNCH();
     return EFGH_OK;

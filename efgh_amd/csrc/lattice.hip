@@ -30,6 +30,7 @@
 // reference's MKL sgemm (FMA chain in column order).
 #include "common.h"
 #include <string.h>
+#include <limits.h>
 
 namespace {
 
@@ -617,6 +618,120 @@ k_neighbors(const int4 *__restrict__ vkeys, const int *__restrict__ mm, const un
                 const int k_ = base + __popcll(am & ((1ULL << lane) - 1ULL));
                 if (k_ < alias_cap) alist[k_] = make_int2((int)g, res);
                 else atomicOr(&info[EFGH_LATTICE_INFO_ERR], 2);
+            }
+        }
+    }
+}
+
+// =====================================================================================================================
+// Blur neighbours at any neighbourhood radius (transforms.py:168-180 with bcn_filter_offsets = radius2offset[r],
+// generate_data.py:44-52): F = (r+1)^4 - r^4 probes per vertex.  A stage of its own behind whichever build served the level
+// (hash, partitioned, big-bucket): it needs only what every build leaves - the vertex lists (`list` / `vseg`: the head of a list is
+// the vertex's first-seen flat position 4p + rem, so its key is recomputed from point p) and the vertex samples - and keeps its own
+// hash table of the vertex key integers.  Table row: F neighbour columns, then ceil(F/32) alias-mask words (bit t of word t/32 =
+// tap t is an aliased hit of key2int, see k_neighbors), zero padding up to the row stride ld.
+//   k_rn_init    empty table, per-sample key extrema reset
+//   k_rn_keys    vertex keys + per-sample extrema (one atomic per wave and bound when the wave lies in one sample)
+//   k_rn_insert  key integer * nsamples + sample -> vertex number (keys are distinct: one CAS per vertex)
+//   k_rn_probe   32 lanes per (vertex, mask word): F probes, the mask words from one ballot
+__global__ void __launch_bounds__(TPB)
+k_rn_init(unsigned long long *__restrict__ hkeys, int64_t hslots, int *__restrict__ mm, int nsamples) {
+    for (int64_t i = (int64_t)blockIdx.x * TPB + threadIdx.x; i < hslots; i += (int64_t)gridDim.x * TPB) hkeys[i] = EMPTY;
+    const int64_t g = (int64_t)blockIdx.x * TPB + threadIdx.x;
+    if (g < (int64_t)nsamples * 8) mm[g] = (g & 7) < 4 ? INT_MAX : INT_MIN;
+}
+
+__global__ void __launch_bounds__(TPB)
+k_rn_keys(const float *__restrict__ pts, int64_t cstride, const int *__restrict__ sid, int pps, float scale32, float std32,
+          const int *__restrict__ list, const int2 *__restrict__ vseg, const int *__restrict__ vsid, const int *__restrict__ info,
+          int h_cap, int4 *__restrict__ vkeys, int *__restrict__ mm) {
+    int H = info[EFGH_LATTICE_INFO_H];
+    if (H > h_cap) H = h_cap;
+    const int h = blockIdx.x * TPB + threadIdx.x;
+    const bool ok = h < H;
+    int k[4] = {0, 0, 0, 0}, b = -1;
+    if (ok) {
+        const int f = list[vseg[h].x];
+        const int p = f >> 2;
+        PointKeys pk;
+        point_keys(pts[p], pts[cstride + p], pts[2 * cstride + p], scale32, std32, pk);
+        entry_key(pk, f & 3, k);
+        vkeys[h] = make_int4(k[0], k[1], k[2], k[3]);
+        b = vsid[h];
+    }
+    const int b0 = __shfl(b, 0);
+    if (__ballot(ok && b != b0) == 0ULL && b0 >= 0) {           // the wave's vertices lie in one sample: reduce, then one atomic per bound
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            int lo = ok ? k[c] : INT_MAX, hi = ok ? k[c] : INT_MIN;
+            for (int o = 32; o > 0; o >>= 1) { lo = min(lo, __shfl_xor(lo, o)); hi = max(hi, __shfl_xor(hi, o)); }
+            if ((threadIdx.x & 63) == 0) { atomicMin(&mm[8 * b0 + c], lo); atomicMax(&mm[8 * b0 + 4 + c], hi); }
+        }
+    } else if (ok) {
+#pragma unroll
+        for (int c = 0; c < 4; ++c) { atomicMin(&mm[8 * b + c], k[c]); atomicMax(&mm[8 * b + 4 + c], k[c]); }
+    }
+}
+
+__global__ void __launch_bounds__(TPB)
+k_rn_insert(const int4 *__restrict__ vkeys, const int *__restrict__ mm, const int *__restrict__ vsid, const int *__restrict__ info,
+            int h_cap, int nsamples, unsigned long long *__restrict__ hkeys, int *__restrict__ hvals, int64_t hmask) {
+    int H = info[EFGH_LATTICE_INFO_H];
+    if (H > h_cap) H = h_cap;
+    const int h = blockIdx.x * TPB + threadIdx.x;
+    if (h >= H) return;
+    const int4 kk = vkeys[h];
+    const int k[4] = {kk.x, kk.y, kk.z, kk.w};
+    const int b = vsid[h];
+    const unsigned long long ki = (unsigned long long)(key2int(k, mm + 8 * b) * nsamples + b);
+    uint64_t s = mix64(ki) & (uint64_t)hmask;
+    while (true) {
+        const unsigned long long prev = atomicCAS(&hkeys[s], EMPTY, ki);
+        if (prev == EMPTY) { hvals[s] = h; return; }
+        s = (s + 1) & (uint64_t)hmask;             // (keys are distinct: an occupied slot is someone else's)
+    }
+}
+
+__global__ void __launch_bounds__(TPB)
+k_rn_probe(const int4 *__restrict__ vkeys, const int *__restrict__ mm, const int *__restrict__ vsid, const int *__restrict__ info,
+           int h_cap, int nsamples, const unsigned long long *__restrict__ hkeys, const int *__restrict__ hvals, int64_t hmask,
+           const int4 *__restrict__ offs, int F, int nw, int ld, int *__restrict__ nbr) {
+    int H = info[EFGH_LATTICE_INFO_H];
+    if (H > h_cap) H = h_cap;
+    const int lane = threadIdx.x & 63;
+    const int64_t per = (int64_t)nw * 32;
+    for (int64_t g0 = (int64_t)blockIdx.x * TPB; g0 < (int64_t)H * per; g0 += (int64_t)gridDim.x * TPB) {
+        const int64_t g = g0 + threadIdx.x;
+        const int h = (int)(g / per), t = (int)(g - (int64_t)h * per);
+        int res = -1;
+        bool aliased = false;
+        if (h < H && t < F) {
+            const int4 kk = vkeys[h], o = offs[t];
+            const int k[4] = {kk.x + o.x, kk.y + o.y, kk.z + o.z, kk.w + o.w};
+            const int b = vsid[h];
+            const int *m8 = mm + 8 * b;
+            int64_t ki = key2int(k, m8);
+            if (ki >= 0) {   // every inserted key integer is >= 0
+                ki = ki * nsamples + b;
+                uint64_t s = mix64((uint64_t)ki) & (uint64_t)hmask;
+                for (int64_t probe = 0; probe <= hmask; ++probe) {
+                    const unsigned long long cur = hkeys[s];
+                    if (cur == EMPTY) break;
+                    if (cur == (unsigned long long)ki) { res = hvals[s]; break; }
+                    s = (s + 1) & (uint64_t)hmask;
+                }
+            }
+            aliased = res >= 0 && (k[1] < m8[1] || k[1] > m8[5] || k[2] < m8[2] || k[2] > m8[6] || k[3] < m8[3] || k[3] > m8[7]);
+        }
+        const unsigned long long am = __ballot(aliased);     // (per is a multiple of 32: a half-wave is one mask word of one row)
+        if (h < H) {
+            int *row = nbr + (int64_t)h * ld;
+            if (t < F) row[t] = res;
+            if ((t & 31) == 0) {
+                const int w = t >> 5;
+                row[F + w] = (int)(unsigned)(am >> (lane & 32));
+                if (w == nw - 1)
+                    for (int c = F + nw; c < ld; ++c) row[c] = 0;
             }
         }
     }
@@ -1795,6 +1910,62 @@ extern "C" int efgh_lattice_level_neighbors(const void *workspace, int32_t n_cap
     k_neighbors<<<grid, TPB, 0, st>>>((const int4 *)(ws + w.vkeys), (const int *)(ws + w.mm),
                                       (const unsigned long long *)(ws + w.hkeys), (const int *)(ws + w.hvals), hcap - 1, info,
                                       h_cap, nbr, vsid, nsamples, (int2 *)alist, alias_cap);
+    EFGH_CHECK_LAUNCH();
+    return EFGH_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// blur neighbours at any radius: host side
+namespace {
+int64_t rn_slots(int32_t h_cap) { int64_t c = 4096; while (c < 2LL * h_cap) c <<= 1; return c; }
+struct RnLayout { int64_t hkeys, hvals, vkeys, mm, total; };
+RnLayout rn_layout(int32_t h_cap, int32_t nsamples) {
+    RnLayout w;
+    const int64_t hs = rn_slots(h_cap);
+    int64_t o = 0;
+    w.hkeys = o; o += align256(hs * 8);
+    w.hvals = o; o += align256(hs * 4);
+    w.vkeys = o; o += align256((int64_t)h_cap * 16);
+    w.mm = o;    o += align256((int64_t)nsamples * 32);
+    w.total = o;
+    return w;
+}
+}  // namespace
+
+extern "C" int64_t efgh_lattice_neighbors_r_workspace(int32_t h_cap, int32_t nsamples) {
+    if (h_cap <= 0 || nsamples <= 0) return 0;
+    return rn_layout(h_cap, nsamples).total;
+}
+
+extern "C" int efgh_lattice_neighbors_r(const float *pts, int64_t pts_cstride, const int32_t *sid, int32_t pts_per_sample,
+                                        int32_t nsamples, float scale32, const int32_t *list, const int32_t *vseg,
+                                        const int32_t *vsid, const int32_t *info, int32_t h_cap, const int32_t *offsets, int32_t F,
+                                        int32_t ld, int32_t *nbr, void *workspace, void *stream_) {
+    hipStream_t st = (hipStream_t)stream_;
+    EFGH_CHECK_ARG(pts && list && vseg && vsid && info && offsets && nbr && workspace && (sid || pts_per_sample > 0));
+    EFGH_CHECK_ARG(h_cap > 0 && nsamples >= 1 && nsamples <= EFGH_LATTICE_MAX_SAMPLES && F >= 1 && F <= 1024);
+    const int nw = (F + 31) / 32;
+    EFGH_CHECK_ARG(ld >= F + nw && (((uintptr_t)offsets) & 15) == 0);
+    const RnLayout w = rn_layout(h_cap, nsamples);
+    const int64_t hs = rn_slots(h_cap);
+    char *ws = (char *)workspace;
+    unsigned long long *hkeys = (unsigned long long *)(ws + w.hkeys);
+    int *hvals = (int *)(ws + w.hvals), *mm = (int *)(ws + w.mm);
+    int4 *vkeys = (int4 *)(ws + w.vkeys);
+    const uint32_t std_bits = 0x405105ECu;         // float32(4*sqrt(2/3)), generate_data.py:19
+    float std32;
+    memcpy(&std32, &std_bits, 4);
+    const int pps = sid ? 1 : pts_per_sample;
+    int gi = cdiv(hs, TPB * 4);
+    if (gi < cdiv((int64_t)nsamples * 8, TPB)) gi = cdiv((int64_t)nsamples * 8, TPB);
+    if (gi > 8192) gi = 8192;
+    k_rn_init<<<gi, TPB, 0, st>>>(hkeys, hs, mm, nsamples);
+    k_rn_keys<<<cdiv(h_cap, TPB), TPB, 0, st>>>(pts, pts_cstride, sid, pps, scale32, std32, list, (const int2 *)vseg, vsid, info, h_cap,
+                                                vkeys, mm);
+    k_rn_insert<<<cdiv(h_cap, TPB), TPB, 0, st>>>(vkeys, mm, vsid, info, h_cap, nsamples, hkeys, hvals, hs - 1);
+    int gp = cdiv((int64_t)h_cap * nw * 32, TPB);
+    if (gp > 16384) gp = 16384;
+    k_rn_probe<<<gp, TPB, 0, st>>>(vkeys, mm, vsid, info, h_cap, nsamples, hkeys, hvals, hs - 1, (const int4 *)offsets, F, nw, ld, nbr);
     EFGH_CHECK_LAUNCH();
     return EFGH_OK;
 }

@@ -29,6 +29,7 @@ struct WArgs {
     const int *table;
     const float *G; int64_t ldg;     // upstream gradient rows [orow][ldg], first N used
     int N;
+    int tld;                         // mode 4: row stride of the neighbour table (efgh_blur_r_wgrad; in the padding in front of M)
     long long M; int mchunk;
     float *dW;                       // [N][K] (one row chunk only) or the partial planes [zs][nbatch][N][K] (zstride apart)
     long long zstride;
@@ -133,7 +134,7 @@ k_gather_wgrad(const WArgs p0) {
                 } else {
                     long long arow = -1;
                     if (MODE == 0) arow = m;
-                    else if (kin) arow = p.table[m * 16 + t];
+                    else if (kin) arow = p.table[m * (MODE == 4 ? p.tld : 16) + t];
                     if (TN == 128 && nin) g = *reinterpret_cast<const float4 *>(p.G + m * p.ldg + n0 + c4);
                     if (kin && arow >= 0) a = *reinterpret_cast<const float4 *>(p.A + arow * p.lda + c);
                 }
@@ -303,7 +304,7 @@ bool efgh_launch_fold_splits(const float *part, int zs, long long total, float *
 }
 
 static int gather_wgrad_impl(const efgh_gemm_desc *d, const float *G, int64_t ldg, float *dWp, float *workspace, int nbatch,
-                             int64_t bsG, int64_t bsD, const efgh_wgrad_out_desc *out, void *stream_);
+                             int64_t bsG, int64_t bsD, const efgh_wgrad_out_desc *out, void *stream_, int tld = 0);
 
 
 // the rows m are cut into `zs` chunks that fill whole rounds of resident workgroups (efgh_round_chunks, common.h; round 5 - rounds
@@ -343,10 +344,11 @@ extern "C" int efgh_gather_wgrad_batched(const efgh_gemm_desc *d, const float *G
 }
 
 static int gather_wgrad_impl(const efgh_gemm_desc *d, const float *G, int64_t ldg, float *dWp, float *workspace, int nbatch,
-                             int64_t bsG, int64_t bsD, const efgh_wgrad_out_desc *out, void *stream_) {
+                             int64_t bsG, int64_t bsD, const efgh_wgrad_out_desc *out, void *stream_, int tld) {
     hipStream_t st = (hipStream_t)stream_;
     EFGH_CHECK_ARG(d && d->A && G && dWp);
-    EFGH_CHECK_ARG(d->C > 0 && d->C % 4 == 0 && d->T >= 1 && d->T <= 16 && d->N >= 1 && d->M >= 1);
+    EFGH_CHECK_ARG(d->C > 0 && d->C % 4 == 0 && d->T >= 1 && (d->T <= 16 || tld > 0) && d->N >= 1 && d->M >= 1);
+    EFGH_CHECK_ARG(tld == 0 || (d->mode == 2 && d->table != nullptr && tld >= d->T && nbatch == 1 && !out));
     EFGH_CHECK_ARG(d->lda % 4 == 0 && ldg % 4 == 0 && d->N % 4 == 0);
     EFGH_CHECK_ARG((((uintptr_t)d->A) & 15) == 0 && (((uintptr_t)G) & 15) == 0 && (((uintptr_t)dWp) & 15) == 0);
     EFGH_CHECK_ARG((int64_t)d->T * d->C < 65536 && d->mode >= 0 && d->mode <= 2);
@@ -362,7 +364,7 @@ static int gather_wgrad_impl(const efgh_gemm_desc *d, const float *G, int64_t ld
     }
     a.Ho = d->Ho; a.Wo = d->Wo; a.osh = d->osh; a.osw = d->osw; a.oh0 = d->oh0; a.ow0 = d->ow0;
     a.table = d->table; a.G = G; a.ldg = ldg; a.N = d->N; a.M = d->M;
-    a.bsA = nbatch > 1 ? d->batch_stride_a : 0; a.bsG = bsG; a.bsD = bsD;
+    a.bsA = nbatch > 1 ? d->batch_stride_a : 0; a.bsG = bsG; a.bsD = bsD; a.tld = tld;
     if (d->mode == 1) EFGH_CHECK_ARG(d->M == (int64_t)d->B * d->Hv * d->Wv && d->osh >= 1 && d->osw >= 1);
     if (d->mode == 2) EFGH_CHECK_ARG(d->table != nullptr);
     const int TN = a.N <= 64 ? 64 : 128;
@@ -379,7 +381,10 @@ static int gather_wgrad_impl(const efgh_gemm_desc *d, const float *G, int64_t ld
     a.dW = zs > 1 ? workspace : dWp;
     a.zstride = zs > 1 ? plane : 0;
     const dim3 grid((unsigned)(zs * kt * nt), (unsigned)nbatch);
-    if (TN == 128) {
+    if (tld > 0) {
+        if (TN == 128) k_gather_wgrad<4, 128><<<grid, 256, 0, st>>>(a);
+        else k_gather_wgrad<4, 64><<<grid, 256, 0, st>>>(a);
+    } else if (TN == 128) {
         if (d->mode == 0) k_gather_wgrad<0, 128><<<grid, 256, 0, st>>>(a);
         else if (d->mode == 1) k_gather_wgrad<1, 128><<<grid, 256, 0, st>>>(a);
         else k_gather_wgrad<2, 128><<<grid, 256, 0, st>>>(a);
@@ -392,6 +397,17 @@ static int gather_wgrad_impl(const efgh_gemm_desc *d, const float *G, int64_t ld
     if (zs > 1) wrote = efgh_launch_fold_splits(workspace, (int)zs, plane, dWp, st, nbatch == 1 ? out : nullptr);       // (N % 4 == 0)
     EFGH_CHECK_LAUNCH();
     return wrote ? EFGH_WROTE_OUT : EFGH_OK;
+}
+
+/* weight gradient of the BCL blur at any neighbourhood radius (autograd of bilateralNN.py:240-246):
+ *   dWp[n][t*C + c] = sum_m G[m][n] * A[table[m*ld + t]][c]    (t < F = d->T; a missing neighbour contributes nothing)
+ * k_gather_wgrad with the table row stride as a parameter (mode 4); d->mode must be 2.  `workspace`: efgh_gather_wgrad_workspace(d)
+ * floats (row-chunk partials, folded in a fixed order). */
+extern "C" int efgh_blur_r_wgrad(const efgh_gemm_desc *d, int32_t ld, const float *G, int64_t ldg, float *dWp, float *workspace,
+                                 void *stream_) {
+    EFGH_CHECK_ARG(ld > 0);
+    const int rc = gather_wgrad_impl(d, G, ldg, dWp, workspace, 1, 0, 0, nullptr, stream_, ld);
+    return rc == EFGH_WROTE_OUT ? EFGH_OK : rc;
 }
 
 extern "C" int efgh_unpack_weight(const float *Wp, float *W, int32_t N, int32_t T, int32_t C, int32_t Cp,

@@ -43,6 +43,71 @@ _CLEAN = {}             # the same key -> consecutive clean speculative builds s
 ESCALATION_DECAY = 64
 STATS = {'speculative': 0, 'level_by_level': 0, 'reenqueued': 0}      # pyramids by path (tests, bench --rotate-inputs)
 _log = logging.getLogger('efgh_amd.lattice')
+RADII = (1, 2, 3)                              # BCL neighbourhood radii served (the second column of scale_map)
+
+
+def filter_size(r):
+    """taps of a radius-r BCL filter: (r+1)^4 - r^4 (bilateralNN.py get_filter_size, d = 3)"""
+    return (r + 1) ** 4 - r ** 4
+
+
+def table_ld(F):
+    """row stride of a neighbour table of F taps: F neighbour columns + ceil(F/32) alias-mask words, rounded up to 4 (16 at F = 15)"""
+    return (F + (F + 31) // 32 + 3) // 4 * 4
+
+
+_OFFSETS = {}
+
+
+def filter_offsets(r):
+    """(off [F][4] int32, inv [F] int64) of a radius-r filter in the reference's tap order (generate_data.py:44-52).
+
+    A tap is a vector of step counts i = (i0, i1, i2, i3), 0 <= i_d <= r, along the four lattice directions 4 e_d - (1,1,1,1);
+    i3 may only be nonzero when one of i0..i2 is zero (the cuboid walk takes one step along the last direction otherwise), so
+    the taps are the (r+1)^4 - r^4 such vectors in lexicographic order of (i0, i1, i2, i3), and off = 4 i - sum(i).
+    inv[t] is the tap with off[inv[t]] = -off[t] (the set is symmetric)"""
+    r = int(r)
+    got = _OFFSETS.get(r)
+    if got is None:
+        rows = []
+        for i0 in range(r + 1):
+            for i1 in range(r + 1):
+                for i2 in range(r + 1):
+                    for i3 in range(r + 1 if 0 in (i0, i1, i2) else 1):
+                        i = np.array([i0, i1, i2, i3])
+                        rows.append(4 * i - i.sum())
+        off = np.array(rows, dtype=np.int32)
+        assert len(off) == filter_size(r)
+        pos = {tuple(o): t for t, o in enumerate(off.tolist())}
+        inv = np.array([pos[tuple((-off[t]).tolist())] for t in range(len(off))], dtype=np.int64)
+        got = _OFFSETS[r] = (off, inv)
+    return got
+
+
+def check_radii(radii, nlevels):
+    """radii per level (None: all 1) as a tuple of ints; anything outside RADII raises EfghError naming the level"""
+    if radii is None:
+        return (1,) * nlevels
+    radii = list(radii)
+    if len(radii) != nlevels:
+        raise _C.EfghError('BCL radii: %d values for %d levels' % (len(radii), nlevels))
+    out = []
+    for l, r in enumerate(radii):
+        if isinstance(r, bool) or not isinstance(r, (int, float, np.integer, np.floating)) or r != int(r) or int(r) not in RADII:
+            raise _C.EfghError('BCL neighbourhood radius %r on level %d: radius 1, 2 or 3 is served' % (r, l))
+        out.append(int(r))
+    return tuple(out)
+
+
+_DEV_OFFSETS = {}
+
+
+def _dev_offsets(r, dev):
+    k = (r, dev)
+    t = _DEV_OFFSETS.get(k)
+    if t is None:
+        t = _DEV_OFFSETS[k] = torch.from_numpy(filter_offsets(r)[0]).to(dev)
+    return t
 
 
 class LatticeLevel:
@@ -50,10 +115,10 @@ class LatticeLevel:
     points / vertices (host lists, len B+1).
 
     point-major device arrays (16 B per point): bary_pm, emg_pm (float32 [n][4]), off_pm (int32 [n][4]);
-    per vertex: nbr [H][16] (15 neighbours + alias mask), vseg [H][2] + list [4n] (vertex -> ascending flat positions
+    per vertex: nbr [H][ld] (F = filter_size(radius) neighbours + alias-mask words; [H][16] at radius 1), vseg [H][2] + list [4n] (vertex -> ascending flat positions
     4p + r), pts_next [3][H]; info = the level's device counters (INFO_*), alist = aliased neighbour records."""
     __slots__ = ('n_in', 'H', 'bary_pm', 'emg_pm', 'off_pm', 'nbr', 'vseg', 'list', 'pts_next_buf', 'info', 'alist',
-                 'seg_in', 'seg', 'vsid', '_ws', '_caps', '_mode', '_geom', '_zeroed', 'n_alias')
+                 'seg_in', 'seg', 'vsid', '_ws', '_caps', '_mode', '_geom', '_zeroed', 'n_alias', 'radius', 'F', 'ld')
 
     # the reference's (4, n) / (3, H) arrays as views
     @property
@@ -82,7 +147,7 @@ class LatticeLevel:
         out.bary = self.bary[:, p0:p1]
         out.emg = self.emg[:, p0:p1]
         out.off = self.off[:, p0:p1] - h0
-        nb = self.nbr[h0:h1, :15]
+        nb = self.nbr[h0:h1, :self.F]
         out.nbr = torch.where(nb >= 0, nb - h0, nb)
         out.pts_next = self.pts_next[:, h0:h1]
         return out
@@ -158,6 +223,7 @@ def _level_arrays(L, dev, n_cap, h_cap, B, mode=('hash', 0), ctrl=None, need_off
     None = allocate and zero one here.  need_off=False (partitioned build only): lattice_offset is not produced"""
     lv = LatticeLevel()
     lv._mode = mode
+    lv.radius, lv.F, lv.ld = 1, 15, 16
     lv.bary_pm = torch.empty((n_cap, 4), dtype=torch.float32, device=dev)
     lv.emg_pm = torch.empty((n_cap, 4), dtype=torch.float32, device=dev)
     lv.off_pm = torch.empty((n_cap, 4), dtype=torch.int32, device=dev) if (need_off or mode[0] == 'hash') else None
@@ -204,6 +270,9 @@ def _launch_build(L, lv, pts, cstride, n_dev, sid, pps, B, s, st):
 def _launch_neighbors(L, lv, B, h_rows, st):
     n_cap, h_cap = lv._caps
     lv.nbr = torch.empty((h_rows, 16), dtype=torch.int32, device=lv.info.device)
+    if lv.radius != 1 and lv._mode[0] != 'part':
+        _launch_neighbors_r(L, lv, B, h_rows, st)          # (the hash build left its vertex records: its radius-1 probes are not needed)
+        return
     if lv._mode[0] == 'part':
         pts, cstride, n_dev, sid, pps, s = lv._geom
         _C.check(L.efgh_lattice_part_neighbors(
@@ -211,10 +280,26 @@ def _launch_neighbors(L, lv, B, h_rows, st):
             _C.c_int32(B), _C.c_float(np.float32(s)), _C.c_float(np.float32(EXPECTED_STD * s)), _C.c_int32(h_cap), _C.ptr(lv.info),
             _C.c_int32(h_rows), _C.ptr(lv.nbr), _C.ptr(lv.alist), _C.c_int32(ALIAS_CAP), _C.ptr(lv.off_pm), _C.ptr(lv.vseg),
             _C.ptr(lv.pts_next_buf), _C.ptr(lv.vsid), _C.c_int32(lv._mode[1]), _C.c_int32(lv._mode[2]), st))
+        if lv.radius != 1:              # (that launch also emitted the vertex records the radius-r probes start from)
+            _launch_neighbors_r(L, lv, B, h_rows, st)
+            return
     else:
         _C.check(L.efgh_lattice_level_neighbors(_C.ptr(lv._ws), _C.c_int32(n_cap), _C.c_int32(h_cap), _C.c_int32(B), _C.ptr(lv.info),
                                                 _C.ptr(lv.vsid), _C.c_int32(h_rows), _C.ptr(lv.nbr), _C.ptr(lv.alist),
                                                 _C.c_int32(ALIAS_CAP), _C.c_int64(lv._mode[1]), st))
+    lv._geom = lv._zeroed = None
+
+
+def _launch_neighbors_r(L, lv, B, h_rows, st):
+    """the F = filter_size(radius) blur neighbours of a level (efgh_lattice_neighbors_r), behind whichever build served it"""
+    pts, cstride, n_dev, sid, pps, s = lv._geom
+    dev = lv.info.device
+    lv.nbr = torch.empty((h_rows, lv.ld), dtype=torch.int32, device=dev)
+    ws = torch.empty(L.efgh_lattice_neighbors_r_workspace(_C.c_int32(h_rows), _C.c_int32(B)), dtype=torch.uint8, device=dev)
+    _C.check(L.efgh_lattice_neighbors_r(_C.ptr(pts), _C.c_int64(cstride), _C.ptr(sid), _C.c_int32(pps), _C.c_int32(B),
+                                        _C.c_float(np.float32(s)), _C.ptr(lv.list), _C.ptr(lv.vseg), _C.ptr(lv.vsid), _C.ptr(lv.info),
+                                        _C.c_int32(h_rows), _C.ptr(_dev_offsets(lv.radius, dev)), _C.c_int32(lv.F), _C.c_int32(lv.ld),
+                                        _C.ptr(lv.nbr), _C.ptr(ws), st))
     lv._geom = lv._zeroed = None
 
 
@@ -230,10 +315,13 @@ def _finish(lv, host, n_in, seg_in, B):
         lv.nbr = lv.nbr[:H]
 
 
-def build_pyramid_batched(pc, scales, need_off=True):
-    """pc: (B,3,N) fp32 CUDA tensor -> list of LatticeLevel (one per scale).  need_off=False: lattice_offset (`off`) is left out -
-    the splat walks the vertex lists, only its backward reads `off` (inference saves a gather pass and three arrays per level)."""
+def build_pyramid_batched(pc, scales, radii=None, need_off=True):
+    """pc: (B,3,N) fp32 CUDA tensor -> list of LatticeLevel (one per scale).  radii: the BCL neighbourhood radius per level
+    (scale_map's second column; None = 1 everywhere): a level of radius r gets a neighbour table of filter_size(r) taps.
+    need_off=False: lattice_offset (`off`) is left out - the splat walks the vertex lists, only its backward reads `off` (inference
+    saves a gather pass and three arrays per level)."""
     _C.require_cuda(pc)
+    radii = check_radii(radii, len(scales))
     L = _C.lib()
     dev = pc.device
     B, _, N = pc.shape
@@ -259,8 +347,8 @@ def build_pyramid_batched(pc, scales, need_off=True):
         # level-by-level path below
         caps, nc = [], n_cap
         tail = _tail_plan(L, key, B, N, len(prev))
-        if tail is not None and any(l in forced or l in bigl for l in range(tail[0], len(prev))):
-            tail = None
+        if tail is not None and any(l in forced or l in bigl or radii[l] != 1 for l in range(tail[0], len(prev))):
+            tail = None                 # (the one-launch tail probes the 15 radius-1 taps only: such levels keep the per-level kernels)
         for l, hp in enumerate(prev):
             hc = min(4 * nc, hp + hp // 4 + 1024)
             md = _plan(L, nc, hc)
@@ -276,8 +364,9 @@ def build_pyramid_batched(pc, scales, need_off=True):
         ctrl = torch.zeros(sum(a + b for a, b in sizes), dtype=torch.uint8, device=dev)
         coff = 0
         tail_lvs = []
-        for s, (n_cap, h_cap, mode), (ib, zb) in zip(scales, caps, sizes):
+        for s, r, (n_cap, h_cap, mode), (ib, zb) in zip(scales, radii, caps, sizes):
             lv = _level_arrays(L, dev, n_cap, h_cap, B, mode, ctrl[coff:coff + ib + zb], need_off)
+            _set_radius(lv, r)
             coff += ib + zb
             if mode[0] == 'tail':
                 lv.nbr = torch.empty((h_cap, 16), dtype=torch.int32, device=dev)
@@ -363,6 +452,7 @@ def build_pyramid_batched(pc, scales, need_off=True):
             while True:
                 mode = modes[i]
                 lv = _level_arrays(L, dev, n, 4 * n, B, mode, None, need_off)
+                _set_radius(lv, radii[l])
                 _launch_build(L, lv, pts, cstride, None, sid, N, B, s, st)
                 head = lv.info[:2].tolist()           # host sync (sizes the next level)
                 if not head[INFO_ERR] & 4 or mode == ('hash', 0):
@@ -390,12 +480,17 @@ def build_pyramid_batched(pc, scales, need_off=True):
             e1.record()
         by = 0.0
         for lv in out:          # reads N*3*4, writes N*(4*4 + 4*4 + 4*8) + 15*H*8 + 4*H*4
-            by += lv.n_in * 12.0 + lv.n_in * 64.0 + lv.H * (15 * 8 + 16.0)
+            by += lv.n_in * 12.0 + lv.n_in * 64.0 + lv.H * (lv.F * 8 + 16.0)
         PROFILE.append((e0, e1, by, 'lattice build'))
     return out
 
 
-def build_pyramid(pc, scales):
+def _set_radius(lv, r):
+    lv.radius, lv.F = r, filter_size(r)
+    lv.ld = table_ld(lv.F)
+
+
+def build_pyramid(pc, scales, radii=None):
     """pc: (3,N) fp32 CUDA tensor (one sample).  Returns a list of LatticeLevel."""
     assert pc.dim() == 2 and pc.size(0) == 3
-    return build_pyramid_batched(pc.unsqueeze(0), scales)
+    return build_pyramid_batched(pc.unsqueeze(0), scales, radii)

@@ -88,14 +88,18 @@ def resnet18_layers():
 
 
 class BilateralConvFlex(nn.Module):
-    """parameter layout of nets/bilateralNN.py:55-139 for do_splat=True, do_slice=False, two outputs"""
+    """parameter layout of nets/bilateralNN.py:55-139 for do_splat=True, do_slice=False, two outputs; neighborhood_size = the
+    radius r of the blur, (r+1)^4 - r^4 taps (bilateralNN.py get_filter_size)"""
 
-    def __init__(self, num_input, num_output):
+    def __init__(self, num_input, num_output, neighborhood_size=1):
         super().__init__()
         import torch
+        from ..lattice import check_radii, filter_size
+        self.neighborhood_size = check_radii([neighborhood_size], 1)[0]
+        F = filter_size(self.neighborhood_size)
         self.num_input, self.num_output = num_input, list(num_output)
         self.register_buffer('feat_indices', torch.arange(num_input, dtype=torch.long))
-        self.blur_conv = nn.Sequential(nn.Conv2d(num_input, num_output[0], (15, 1), 1, 0, bias=True),
+        self.blur_conv = nn.Sequential(nn.Conv2d(num_input, num_output[0], (F, 1), 1, 0, bias=True),
                                        nn.ReLU(inplace=False),
                                        nn.Conv2d(num_output[0], num_output[1], (1, 1)))
         self.blur_conv.apply(init_small)

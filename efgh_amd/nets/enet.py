@@ -4,6 +4,7 @@ import torch.nn as nn
 
 from .. import lattice, ops
 from ..common import pose
+from .._C import EfghError
 from ..ops import ACT_LEAKY, ACT_RELU
 from . import fn as FN
 from . import layers as L
@@ -15,7 +16,10 @@ class Enet(nn.Module):
         super().__init__()
         dim = args['dim']
         self.scale_map = args['scale_map']
-        assert dim == 3 and all(int(r) == 1 for _, r in self.scale_map), 'd=3, radius-1 BCL only'
+        if dim != 3:
+            raise EfghError('Enet: dim = %r; the permutohedral lattice is built for d = 3 only' % (dim,))
+        # the second column of scale_map: the neighbourhood radius of each level's BilateralConvFlex (enet.py:30-83), 1, 2 or 3
+        self.radii = lattice.check_radii([r for _, r in self.scale_map], len(self.scale_map))
         # the reference's E-net switches (enet.py:25-83 -> net_utils.py:6-11, bilateralNN.py:121-135,196): the shipped configurations
         # set use_leaky / bcn_use_norm and clear last_relu (configs/train_rellis.yaml:8-12); the other values are honoured as well
         self.use_leaky, self.use_norm, self.last_relu = bool(args['use_leaky']), bool(args['bcn_use_norm']), bool(args['last_relu'])
@@ -24,11 +28,12 @@ class Enet(nn.Module):
             pass
         self.device = args['DEVICE']
         self.conv_in = nn.Sequential(conv_1x1(dim, 32, True), conv_1x1(32, 32, True), conv_1x1(32, 32, True))
-        self.bcn1 = BilateralConvFlex(32 + dim + 1, [32, 32])          # enet.py:30-83
-        self.bcn2 = BilateralConvFlex(32 + dim + 1, [64, 64])
-        self.bcn3 = BilateralConvFlex(64 + dim + 1, [128, 128])
-        self.bcn4 = BilateralConvFlex(128 + dim + 1, [256, 256])
-        self.bcn5 = BilateralConvFlex(256 + dim + 1, [256, 256])
+        rr = self.radii
+        self.bcn1 = BilateralConvFlex(32 + dim + 1, [32, 32], rr[0])          # enet.py:30-83
+        self.bcn2 = BilateralConvFlex(32 + dim + 1, [64, 64], rr[1])
+        self.bcn3 = BilateralConvFlex(64 + dim + 1, [128, 128], rr[2])
+        self.bcn4 = BilateralConvFlex(128 + dim + 1, [256, 256], rr[3])
+        self.bcn5 = BilateralConvFlex(256 + dim + 1, [256, 256], rr[4])
         self.conv_gn_1 = nn.Conv1d(256, 128, 1)
         self.conv_gn_2 = nn.Conv1d(128, 128, 1)
         self.conv_gn_3 = nn.Conv1d(128, 128, 1)
@@ -52,7 +57,7 @@ class Enet(nn.Module):
         cins = [m.num_input for m in bcns]
         # all samples in one launch sequence per level, all five levels enqueued before the one read-back of their sizes
         # (every sample keeps its own lattice)
-        lv = lattice.build_pyramid_batched(pc, scales, need_off=ctx.grad or keep is not None)      # (`off` serves the splat's backward only)
+        lv = lattice.build_pyramid_batched(pc, scales, self.radii, need_off=ctx.grad or keep is not None)      # (`off` serves the splat's backward only)
         if keep is not None:
             keep['lattice'] = lv
         # conv_in on [B*N][4] (x,y,z,0)

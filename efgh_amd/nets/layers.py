@@ -289,6 +289,19 @@ def blur_conv(ctx, splat, H, C, table, conv0, conv1, out=None, last_act=ACT_NONE
     lv = table if hasattr(table, 'nbr') else None
     if lv is not None:
         table = lv.nbr
+    if lv is not None and lv.radius != 1:
+        # radius 2 / 3 (scale_map's second column): F = 65 / 175 taps through the level's [H][ld] table
+        if conv0.kernel_size != (lv.F, 1):
+            raise ops._C.EfghError('BCL blur weight %s does not match the radius-%d lattice level (F = %d taps)'
+                                   % (tuple(conv0.weight.shape), lv.radius, lv.F))
+        if ctx.grad:
+            assert out is None
+            mid = _blur_grad_r(ctx, splat, H, C, lv, conv0)
+            return linear_rows(ctx, mid, H, C0, conv1.weight, conv1.bias, act=last_act, slope=last_slope)
+        mid = torch.empty((H, C0), dtype=torch.float32, device=splat.device)
+        ops.blur_r_gemm(splat, C, C, lv.F, ops.blur_r_pack(conv0.weight), C0, H, mid, C0, lv.nbr, bias=conv0.bias.detach(),
+                        act=ACT_RELU, flops=2.0 * H * lv.F * C * C0)
+        return linear_rows(ctx, mid, H, C0, conv1.weight, conv1.bias, out=out, act=last_act, slope=last_slope)
     if ctx.grad:
         assert out is None
         mid = _blur_grad(ctx, splat, H, C, table, conv0, lv)
@@ -767,5 +780,24 @@ def _blur_grad(ctx, splat, H, C, table, conv0, lv=None):
         return dsplat
 
     spec = FN.LayerSpec(C0, C, 15, 2, [(None, H)], H, (H,), pack_fwd, dgrad, unpack, act=ACT_RELU, table=table,
+                        c_real=C)
+    return FN.GemmLayerFn.apply(splat, conv0.weight, conv0.bias, None, None, None, spec)
+
+
+def _blur_grad_r(ctx, splat, H, C, lv, conv0):
+    """training form of the radius-r blur: GemmLayerFn on the mode-MODE_BLUR_R launches (forward, data gradient through the same
+    table with mirrored taps, weight gradient [C0][F][C] -> (C0, C, F, 1))"""
+    C0, F = conv0.out_channels, lv.F
+
+    def pack_fwd(w, i):
+        return ops.blur_r_pack(w)
+
+    def unpack(dWp, i, dW):
+        dW.copy_(dWp[:C0].permute(0, 2, 1).unsqueeze(-1))
+
+    def dgrad(spec, w, draw, xin):
+        return ops.blur_r_dgrad(lv, draw, C0, w, C)
+
+    spec = FN.LayerSpec(C0, C, F, ops.MODE_BLUR_R, [(None, H)], H, (H,), pack_fwd, dgrad, unpack, act=ACT_RELU, table=lv.nbr,
                         c_real=C)
     return FN.GemmLayerFn.apply(splat, conv0.weight, conv0.bias, None, None, None, spec)

@@ -541,6 +541,12 @@ def gather_gemm(A, lda, C, T, Wp, N, M, out, ldo, mode=0, geom=None, table=None,
     made (wino2d_bwd_transforms: the data gradient of a layer whose draw is never stored); A may then be None."""
     if (lazy is not None or pre_v is not None) and not (M_dev is None and batch is None and lazy_capable(mode, C, N, geom)):
         raise _C.EfghError('gather_gemm(lazy= / pre_v=) on a launch the 2-D Winograd path does not serve (ask lazy_capable() first)')
+    if mode == MODE_BLUR_R:
+        if (geom is not None or batch is not None or M_dev is not None or scale is not None or shift is not None or residual is not None
+                or stats is not None or alias_mask or pool or bn_bwd is not None):
+            raise _C.EfghError('gather_gemm(mode=MODE_BLUR_R) takes a plain blur launch: bias and activation only')
+        blur_r_gemm(A, lda, C, T, Wp, N, M, out, ldo, table, bias=bias, act=act, slope=slope, a_off=a_off, out_off=out_off, flops=flops)
+        return None
     if (KSPLIT_MAX_ROWS and mode == 2 and M <= KSPLIT_MAX_ROWS and T == 15 and N % 4 == 0 and T * C >= 1024 and batch is None
             and scale is None and shift is None and residual is None and stats is None and M_dev is None
             and (bias is None or bias.numel() == N)):
@@ -1067,6 +1073,78 @@ def blur_dgrad(lv, draw, C0, w, C):
 
 
 # ----------------------------------------------------------------------------------------------
+# BCL blur at neighbourhood radius 2 and 3 (F = 65 / 175 taps through a [H][ld] table, lattice.filter_offsets)
+# ----------------------------------------------------------------------------------------------
+MODE_BLUR_R = 4                 # gather_gemm / gather_wgrad mode of those launches (a lattice table of any width: efgh_blur_r_*)
+BLUR_R_HITS = [0, 0, 0]         # (tests: radius-r blur launches - forward, data gradient, weight gradient)
+
+
+def _blur_r_desc(A, lda, C, F, N, M, table, a_off=0):
+    ld = table.shape[1]
+    if table.dtype != torch.int32 or table.dim() != 2 or table.shape[0] < M or ld < F + (F + 31) // 32 or not table.is_contiguous():
+        raise _C.EfghError('blur table: [>= %d][>= F + ceil(F/32)] int32 expected for F = %d, got %s %s' % (M, F, tuple(table.shape), table.dtype))
+    d = _C.GemmDesc()
+    d.A = A.data_ptr() + 4 * a_off
+    d.lda, d.C, d.T, d.mode = lda, C, F, 2
+    d.table = table.data_ptr()
+    d.N, d.M = N, M
+    return d, ld
+
+
+def blur_r_gemm(A, lda, C, F, Wp, N, M, out, ldo, table, bias=None, act=ACT_NONE, slope=0.0, a_off=0, out_off=0, flops=None, hit=0):
+    """out[m][n] = act(sum_{t<F,c<C} A[table[m][t]][c] * Wp[n][t*C + c] + bias[n]) through a radius-r neighbour table
+    (efgh_blur_r_gemm; a missing neighbour reads zeros).  hit: which BLUR_R_HITS counter the launch counts in"""
+    d, ld = _blur_r_desc(A, lda, C, F, N, M, table, a_off)
+    d.W = Wp.data_ptr()
+    d.bias = 0 if bias is None else bias.data_ptr()
+    d.act, d.slope = act, slope
+    d.out, d.ldo = out.data_ptr() + 4 * out_off, ldo
+    if PROFILE is not None:
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+    _C.check(_L().efgh_blur_r_gemm(ctypes.byref(d), c_int32(ld), _st()))
+    BLUR_R_HITS[hit] += 1
+    if PROFILE is not None:
+        e1.record()
+        PROFILE.append((e0, e1, float(flops) if flops is not None else 2.0 * M * N * F * C, (MODE_BLUR_R, M, N, F, C)))
+
+
+def blur_r_wgrad(A, lda, C, F, N, M, G, ldg, dWp, table):
+    """dWp[n][t*C + c] = sum_m G[m][n] * A[table[m][t]][c]   (efgh_blur_r_wgrad; dWp [N][F][C], N % 4 == 0)"""
+    d, ld = _blur_r_desc(A, lda, C, F, N, M, table)
+    if PROFILE_WGRAD is not None:
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+    _C.check(_L().efgh_blur_r_wgrad(ctypes.byref(d), c_int32(ld), ptr(G), c_int64(ldg), ptr(dWp),
+                                    ptr(_scratch(_L().efgh_gather_wgrad_workspace(ctypes.byref(d)), dWp.device)), _st()))
+    BLUR_R_HITS[2] += 1
+    if PROFILE_WGRAD is not None:
+        e1.record()
+        PROFILE_WGRAD.append((e0, e1, 2.0 * M * N * F * C, (MODE_BLUR_R, M, N, F, C)))
+
+
+def blur_r_pack(w, inv=None):
+    """Conv2d weight (C0, C, F, 1) -> [C0][F*C] (forward); with inv (lattice.filter_offsets): the data-gradient weight
+    [C][F*C0], element [c][t*C0 + o] = w[o][c][inv[t]] - the adjoint of the gather is the same table with mirrored taps"""
+    w = w.detach()
+    if inv is None:
+        return w[..., 0].permute(0, 2, 1).contiguous().view(w.shape[0], -1)
+    return w[:, :, torch.as_tensor(inv, device=w.device), 0].permute(1, 2, 0).contiguous().view(w.shape[1], -1)
+
+
+def blur_r_dgrad(lv, draw, C0, w, C):
+    """data gradient of a radius-r BCL blur (F-neighbour gather + Conv2d(C, C0, (F,1))) w.r.t. the splatted rows: draw [H][>= C0]
+    -> [H][C].  The neighbour relation of the table is symmetric, aliased hits included (include/efgh_hip.h), so
+    dx[h] = sum_t W_{inv t}^T draw[nbr[h][t]]: the forward kernel on the gradient, no scatter, no atomics, no fix-up pass"""
+    from .lattice import filter_offsets
+    H = lv.H
+    Wd = blur_r_pack(w, filter_offsets(lv.radius)[1])
+    dx = torch.empty((H, C), dtype=torch.float32, device=draw.device)
+    blur_r_gemm(draw, draw.stride(0), C0, lv.F, Wd, C, H, dx, C, lv.nbr, flops=2.0 * H * lv.F * C * C0, hit=1)
+    return dx
+
+
+# ----------------------------------------------------------------------------------------------
 # rasterisers, rotate
 # ----------------------------------------------------------------------------------------------
 def range_image(pc, e_l, H, W, fov_up, fov_down):
@@ -1237,11 +1315,14 @@ def wgrad_lazy_capable(mode, C, N, geom):
 def gather_wgrad(A, lda, C, T, N, M, G, ldg, dWp, mode=0, geom=None, table=None, unpack=None, lazy=None, pre_gy=None):
     """unpack: (dW, N_real, T, C_real, Cp, sn, sc, st, taps, accumulate) - where the gradient belongs in the reference layout
     (ops.unpack_weight's arguments).  -> True when the launch left it there itself (its final fold did the unpack: dWp is then
-    NOT written), False when dWp holds the packed gradient and the caller has to unpack it.
+    NOT written), False when dWp holds the packed gradient and the caller has to unpack it (always so for mode MODE_BLUR_R).
     lazy: A is a raw BatchNorm output with a pending activation (LazyAct; 2-D Winograd path only: the kept forward transform already has
     it applied, a re-transform applies it again).  pre_gy: the gradient-side transform, already made (wino2d_bwd_transforms); G may be None"""
     if (lazy is not None or pre_gy is not None) and not wgrad_lazy_capable(mode, C, N, geom):
         raise _C.EfghError('gather_wgrad(lazy= / pre_gy=) on a launch the 2-D Winograd weight gradient does not serve')
+    if mode == MODE_BLUR_R:
+        blur_r_wgrad(A, lda, C, T, N, M, G, ldg, dWp, table)
+        return False
     od = None                # efgh_wgrad_out_desc: the entry points that can leave the reference layout themselves take it explicitly
     if unpack is not None and FOLD_UNPACK and unpack[4] % 4 == 0 and unpack[2] <= 16:
         dW_, n_, t_, c_, cp_, sn_, sc_, st_, taps_, acc_ = unpack

@@ -417,6 +417,34 @@ int efgh_gather_wgrad(const efgh_gemm_desc *d, const float *G, int64_t ldg, floa
 int efgh_gather_wgrad_batched(const efgh_gemm_desc *d, const float *G, int64_t ldg, int64_t batch_stride_g, float *dWp,
                               int64_t batch_stride_dw, float *workspace, void *stream);
 
+/* ------------------------------------------------------------------ BCL at neighbourhood radius r = 2, 3 ------
+ * The reference's BilateralConvFlex takes its filter size from the second column of scale_map: F = (r+1)^4 - r^4 taps
+ * (nets/bilateralNN.py:56-146, 228-246), the offsets of nets/generate_data.py:44-52 (Traverse, transforms.py:104-129) and one
+ * hash probe per tap in build_it (transforms.py:168-180).  Radius 1 keeps efgh_lattice_level_neighbors /
+ * efgh_lattice_part_neighbors and gather-GEMM mode 2 above; these entry points serve any F.
+ *
+ * Neighbour table [H][ld], ld >= F + ceil(F/32): columns 0..F-1 = neighbour vertex or -1, then ceil(F/32) alias-mask words (bit
+ * t & 31 of word t >> 5 = tap t is an aliased hit of key2int, as efgh_lattice_level_neighbors marks them), zeros up to ld.  The
+ * relation is symmetric INCLUDING the aliased hits: key2int is affine in the key, so key(m) + off[t] hits h exactly when
+ * key(h) - off[t] = key(h) + off[inv(t)] hits m - the adjoint of the gather is the same table with its taps permuted.
+ * Runs behind whichever build served the level (efgh_lattice_level_build or efgh_lattice_part_build, before their workspace is
+ * reused): pts / pts_cstride / sid / pts_per_sample / nsamples / scale32 as passed to that build, list / vseg / vsid / info as it
+ * left them, h_cap rows of nbr.  offsets: [F][4] int32 (16-byte aligned) in the reference's tap order.
+ * workspace: efgh_lattice_neighbors_r_workspace(h_cap, nsamples) bytes, 256-byte aligned.                                        */
+int64_t efgh_lattice_neighbors_r_workspace(int32_t h_cap, int32_t nsamples);
+int efgh_lattice_neighbors_r(const float *pts, int64_t pts_cstride, const int32_t *sid, int32_t pts_per_sample, int32_t nsamples,
+                             float scale32, const int32_t *list, const int32_t *vseg, const int32_t *vsid, const int32_t *info,
+                             int32_t h_cap, const int32_t *offsets, int32_t F, int32_t ld, int32_t *nbr, void *workspace,
+                             void *stream);
+/* blur Conv2d(C, N, (F, 1)) through that table (replaces bilateralNN.py:240-246 at any F): as efgh_gather_gemm mode 2 with
+ * d->mode = 2, d->T = F, the table row stride `ld`; no batching, no alias masking (d->table_alias_mask = 0).  The data gradient is
+ * the same call on the upstream gradient with the taps permuted by inv and the weight transposed. */
+int efgh_blur_r_gemm(const efgh_gemm_desc *d, int32_t ld, void *stream);
+/* its weight gradient dWp[n][t*C + c] = sum_m G[m][n] * A[table[m*ld + t]][c]  (d as for efgh_blur_r_gemm; workspace:
+ * efgh_gather_wgrad_workspace(d) floats) */
+int efgh_blur_r_wgrad(const efgh_gemm_desc *d, int32_t ld, const float *G, int64_t ldg, float *dWp, float *workspace,
+                      void *stream);
+
 /* ------------------------------------------------------------------ Winograd F(4x4,3x3) --------
  * the 3x3 / stride 1 / pad 1 convolutions with >= 128 channels (nets/vgg.py:77, nets/resnet.py:22-30), their data and weight
  * gradients, as input transform -> 36 batched GEMMs (efgh_gather_gemm, mode 0) -> output transform; fp32 throughout.
