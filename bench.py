@@ -1,6 +1,6 @@
 """EFGHNet hot-path benchmark on MI355X (contract: task statement / DESIGN.md §5).
 
-    python bench.py --gpus N --steps K --warmup W [--mode train|fwd] [--batch B]
+    python bench.py --gpus N --steps K --warmup W [--mode train|fwd] [--batch B] [--full]
 
 One process per GPU.  The driver launches N>1 through torch.distributed.run; run bare (`python bench.py --gpus N`, no
 WORLD_SIZE in the environment) the parent starts that launcher itself as a child process BEFORE anything touches the GPU,
@@ -9,8 +9,12 @@ and rank 0 of the children prints the JSON line.
 * default `--mode train` = BASELINE.json's metric: frame-pairs/s of EFGHNet fwd+bwd (efghloss, gradient
   all-reduce, fused Adam) on synthetic 384x1280 RGB + 64x2048-point sweeps, batch 8 per GPU
   (configs[2]); a step = one training step on one batch, inputs resident in HBM.
-* the same run also times the forward-only workload (configs[1], eval, batch 4) and reports it under
-  "forward_only" (the north star's 40 frame-pairs/s/GPU target is stated on it).
+* a plain run does what that figure needs and no more: set-up, warm-up, the timed steps, the outputs when `--dump-outputs`
+  asks for them, the result line.  It reports `outside_steps_s`, the seconds it spent on anything but its steps.
+* `--full` adds every side measurement, each of which can be taken out again with its `--no-...` option: the forward-only
+  workload (configs[1], eval, batch 4; "forward_only": the north star's 40 frame-pairs/s/GPU target is stated on it), the
+  roofline objects of every kernel family with the single-stream pass they are measured in, the ResNet-branch span, the CPU
+  baseline and the reference's own configuration and loop (config_r).
 Rank 0 prints ONE compact JSON line (< 8 KB, `compact_line`) as the only stdout line; the full object with every per-family
 figure goes to bench_detail.json.
 """
@@ -20,6 +24,7 @@ import os
 import sys
 import time
 
+T_START = time.perf_counter()
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
@@ -37,11 +42,16 @@ def parse():
     ap.add_argument('--warmup', type=int, default=2)
     ap.add_argument('--mode', default='train', choices=['train', 'fwd'])
     ap.add_argument('--batch', type=int, default=None, help='frame-pairs per GPU per step (8 train / 4 fwd)')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-forward-section', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='also take the side measurements, each in a run of its own around the timed steps: the forward-only workload, '
+                         'the per-kernel rooflines (single-stream pass), the ResNet-branch span, the CPU baseline, config_r.  Without '
+                         'it the run does only what the headline figure needs')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baseline')
+    ap.add_argument('--no-forward-section', action='store_true',
+                    help='skip the forward-only workload (--mode train times it under --full, and under --dump-outputs for its arrays)')
     ap.add_argument('--small', action='store_true', help='debug: 128x256 / 2048 points')
-    ap.add_argument('--no-config-r', action='store_true', help='skip the batch-1 reference-loop section (config_r)')
-    ap.add_argument('--no-branch-section', action='store_true', help='skip roofline_resnet_branch (profiler passes: its G-only spans would count as launches of the steps)')
+    ap.add_argument('--no-config-r', action='store_true', help='with --full: skip the batch-1 reference-loop section (config_r)')
+    ap.add_argument('--no-branch-section', action='store_true', help='with --full: skip roofline_resnet_branch (profiler passes: its G-only spans would count as launches of the steps)')
     ap.add_argument('--rotate-inputs', type=int, default=4,
                     help='cycle this many resident batches of DIFFERENT synthetic frame-pairs through the steps (1 = the same batch '
                          'every step): every sweep has its own lattice sizes, so the speculative sizing of the pyramid (previous '
@@ -523,7 +533,12 @@ def compact_line(out):
         if k in out:
             c[k] = out[k]
     c['scale'] = 'unmeasured: the pool has no multi-GPU node' if (out.get('n_gpus') or 1) == 1 else 'this line'
-    c['roofline'] = _rl(out.get('roofline'), ('avg_launch_ms', 'launches_per_step', 'kernel_ms_per_step'))
+    for k in ('full', 'outside_steps_s'):
+        if k in out:
+            c[k] = _r(out[k], 2)
+    full = out.get('full', True)        # (objects written before --full existed hold every side measurement)
+    if full:
+        c['roofline'] = _rl(out.get('roofline'), ('avg_launch_ms', 'launches_per_step', 'kernel_ms_per_step'))
     fr = {}
     for name, key in (('bcl', 'roofline_bcl'), ('gemm', 'roofline_gemm'), ('wgrad', 'roofline_wgrad'), ('wino', 'roofline_wino'),
                       ('wino_wgrad', 'roofline_wino_wgrad'), ('wino2d_gemm', 'roofline_wino2d_gemm'), ('hbm_convs', 'roofline_hbm_convs'),
@@ -535,7 +550,8 @@ def compact_line(out):
     for name, tag in (('wino2d_gemm', 'k_plane_gemm'), ('wino', 'k_wino43')):
         if name not in fr and str(top.get('kernel', '')).startswith(tag):
             fr[name] = _r(top.get('frac'))
-    c['roofline_fracs'] = fr
+    if full:
+        c['roofline_fracs'] = fr
     b = out.get('roofline_bcl')
     if isinstance(b, dict):
         c['roofline_bcl'] = _rl(b, ('kernel_ms_per_step', 'algorithmic_mb_per_step'))
@@ -560,7 +576,8 @@ def compact_line(out):
             o = fo.get(key)
             if isinstance(o, dict) and 'frac' in o:
                 ff[name] = _r(o['frac'])
-        c['forward_fracs'] = ff
+        if full:
+            c['forward_fracs'] = ff
     cr = out.get('config_r')
     if isinstance(cr, dict):
         if 'error' in cr:
@@ -818,7 +835,9 @@ def main():
 
     out = None
     fwd = None
-    run_fwd = a.mode == 'fwd' or not a.no_forward_section
+    # --mode train: the forward-only workload is a side measurement (--full).  --dump-outputs times it as well, because the arrays
+    # it writes are those of both workloads, each cut to its half of DUMP_BYTES
+    run_fwd = a.mode == 'fwd' or ((a.full or bool(a.dump_outputs)) and not a.no_forward_section)
     dumps = {}                                            # --dump-outputs: each timed workload gets an equal share of DUMP_BYTES
     dump_budget = DUMP_BYTES // (int(run_fwd) + int(a.mode == 'train'))
     if run_fwd:
@@ -839,11 +858,12 @@ def main():
                'value': world * Bf * a.steps / dt, 'unit': 'frame-pairs/s', 'ms_per_step': dt / a.steps * 1e3,
                'workload': 'BASELINE.json configs[1]: EFGHNet forward only (eval), batch=%d per GPU' % Bf,
                }
-        fwd.update(rooflines(prof, a.steps, 'fwd'))
-        fwd['mfma_step_utilisation'] = mfma_step_utilisation(prof, a.steps, fwd['ms_per_step'])
-        attach_serialized(fwd, fstep, 'fwd')
-        if not a.no_branch_section:
-            fwd['roofline_resnet_branch'] = resnet_branch(fsets[0][0], None, False)
+        if a.full:
+            fwd.update(rooflines(prof, a.steps, 'fwd'))
+            fwd['mfma_step_utilisation'] = mfma_step_utilisation(prof, a.steps, fwd['ms_per_step'])
+            attach_serialized(fwd, fstep, 'fwd')
+            if not a.no_branch_section:
+                fwd['roofline_resnet_branch'] = resnet_branch(fsets[0][0], None, False)
         del fsets
     if a.mode == 'train':
         Bt = a.batch or 8
@@ -880,8 +900,9 @@ def main():
                            'note': 'warm-up + timed steps; speculative = all five levels enqueued from the previous sizes with ONE '
                                    'read-back, level_by_level = the five-sync fallback, reenqueued = escalated rebuilds'},
             }
-            out.update(rooflines(prof, a.steps))
-            out['mfma_step_utilisation'] = mfma_step_utilisation(prof, a.steps, out['ms_per_step'])
+            if a.full:
+                out.update(rooflines(prof, a.steps))
+                out['mfma_step_utilisation'] = mfma_step_utilisation(prof, a.steps, out['ms_per_step'])
             out['peak_hbm_gb_per_gpu'] = torch.cuda.max_memory_allocated() / 1e9      # of 288 GB
         if world > 1:
             # data parallelism keeps the replicas identical: same start (broadcast), same all-reduced gradients, same Adam.  Two
@@ -894,8 +915,9 @@ def main():
             if rank == 0:
                 out['replicas_identical'] = bool(torch.equal(hi, lo))
                 out['compute_streams'] = 1 + len(ops.side_streams())
-        attach_serialized(out, tstep, 'train')
-        if rank == 0 and not a.no_branch_section:
+        if a.full:
+            attach_serialized(out, tstep, 'train')
+        if a.full and rank == 0 and not a.no_branch_section:
             out['roofline_resnet_branch'] = resnet_branch(tsets[0][0], tsets[0][1], True)
     elif rank == 0:
         out = {'metric': fwd['metric'], 'value': fwd['value'], 'unit': 'frame-pairs/s', 'n_gpus': world,
@@ -910,9 +932,9 @@ def main():
     if rank == 0:
         if a.dump_outputs:
             write_outputs(dumps, a.dump_outputs)
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             out['cpu_baseline'] = cpu_baseline(raw, npts, a.mode)
-        if world == 1 and not a.small and not a.no_config_r:
+        if a.full and world == 1 and not a.small and not a.no_config_r:
             # the reference's own configuration and loop (batch 1): everything of the main measurement is released first
             fsets = tsets = trainer = model = None
             import gc
@@ -928,9 +950,14 @@ def main():
             # small copies at the END of the line (a log tail keeps them): the forward-only workload, BASELINE configs[1]
             out['forward_value'] = fwd['value']
             out['forward_ms_per_step'] = fwd['ms_per_step']
-            out['forward_mfma_frac'] = fwd['mfma_step_utilisation']['frac']
-            out['forward_roofline_frac'] = fwd.get('roofline', {}).get('frac')
-            out['forward_roofline_bcl_frac'] = fwd.get('roofline_bcl', {}).get('frac')
+            if a.full:
+                out['forward_mfma_frac'] = fwd['mfma_step_utilisation']['frac']
+                out['forward_roofline_frac'] = fwd.get('roofline', {}).get('frac')
+                out['forward_roofline_bcl_frac'] = fwd.get('roofline_bcl', {}).get('frac')
+        out['full'] = bool(a.full)
+        # everything this process did besides its steps, from the first line of this file to this one: imports, inputs, the first launches
+        # of every kernel, the dump, the side measurements of --full (and the forward-only workload whenever it ran)
+        out['outside_steps_s'] = time.perf_counter() - T_START - (a.steps + a.warmup) * out['ms_per_step'] * 1e-3
         emit(out, a.detail)
     if world > 1:
         dist.destroy_process_group()

@@ -445,3 +445,33 @@ def test_bench_line_is_compact(capsys, tmp_path):
     for k in ('bcl', 'gemm', 'wgrad', 'wino', 'wino_wgrad', 'wino2d_gemm', 'hbm_convs', 'resnet_branch', 'mfma_step'):
         assert 0 < c['roofline_fracs'][k] <= 1, k
     assert json.load(open(detail)) == full
+
+
+def test_bench_plain_line_names_no_side_measurement(capsys, tmp_path, monkeypatch):
+    """`--full` is off by default, and the line of a plain run carries the headline and what describes the run - no roofline,
+    CPU-baseline, forward-only or config_r entry, which only `--full` measures."""
+    import importlib.util
+    import json
+    import sys
+    spec = importlib.util.spec_from_file_location('bench_under_test', os.path.join(ROOT, 'bench.py'))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    monkeypatch.setattr(sys, 'argv', ['bench.py', '--gpus', '1', '--steps', '7', '--warmup', '2'])
+    a = bench.parse()
+    assert a.full is False and (a.steps, a.warmup, a.dump_outputs) == (7, 2, None)
+    monkeypatch.setattr(sys, 'argv', ['bench.py', '--full'])
+    assert bench.parse().full is True
+    full = json.load(open(os.path.join(ROOT, 'profiles', 'r05_bench_default.json')))
+    head = ('metric', 'value', 'unit', 'n_gpus', 'steps', 'warmup', 'ms_per_step', 'higher_is_better', 'scaling', 'vs_baseline', 'dtype',
+            'data', 'config')
+    plain = {k: full[k] for k in head}
+    plain.update(full=False, outside_steps_s=4.25)
+    bench.emit(plain, str(tmp_path / 'detail.json'))
+    lines = [l for l in capsys.readouterr().out.splitlines() if l.strip()]
+    assert len(lines) == 1
+    c = json.loads(lines[0])
+    for k in head:
+        assert k in c, k
+    assert c['full'] is False and c['outside_steps_s'] == 4.25
+    assert abs(c['value'] - full['value']) < 1e-3 and abs(c['ms_per_step'] - full['ms_per_step']) < 1e-3
+    assert not [k for k in c if k.startswith(('roofline', 'forward', 'cpu_baseline', 'config_r'))], sorted(c)

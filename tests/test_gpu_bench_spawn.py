@@ -14,7 +14,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def test_bench_spawns_its_own_ranks():
     env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT')}
     r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--small', '--steps', '3', '--warmup', '1',
-                        '--no-cpu-baseline'], env=env, capture_output=True, text=True, timeout=900)
+                        '--full', '--no-cpu-baseline'], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith('{')]
     assert len(lines) == 1, r.stdout[-2000:]
@@ -31,6 +31,30 @@ def test_bench_spawns_its_own_ranks():
     for k in ('roofline', 'forward_value', 'roofline_fracs'):
         assert k in out
     assert out['roofline']['frac'] <= 1.0 and len(lines[0]) < 8192
+
+
+def test_a_plain_run_is_lean():
+    """`bench.py --gpus 1 --steps N --warmup W` at full size, in a process of its own: everything besides the N + W steps - imports,
+    inputs, the first launch of every kernel, the result line - takes at most 30 s of the whole run, and the line names no side
+    measurement (those are `--full`'s)."""
+    import time
+    env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT')}
+    n, w = 2, 1
+    t0 = time.perf_counter()
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', str(n), '--warmup', str(w)],
+                       env=env, capture_output=True, text=True, timeout=600)
+    wall = time.perf_counter() - t0
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, r.stdout[-2000:]
+    out = json.loads(lines[0])
+    assert out['full'] is False and out['steps'] == n and out['warmup'] == w and out['value'] > 0 and out['dtype'] == 'f32'
+    outside = wall - (n + w) * out['ms_per_step'] * 1e-3
+    print('whole run %.1f s, %d steps of %.1f ms: %.1f s outside the steps (its own count: %.1f s)'
+          % (wall, n + w, out['ms_per_step'], outside, out['outside_steps_s']))
+    assert outside <= 30.0, outside
+    assert out['outside_steps_s'] <= outside
+    assert not [k for k in out if k.startswith(('roofline', 'forward', 'cpu_baseline', 'config_r'))], sorted(out)
 
 
 def test_bench_rejects_a_mismatched_launcher():

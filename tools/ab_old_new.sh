@@ -1,6 +1,6 @@
 #!/bin/bash
 # same-box A/B of the committed tree (ab_old/: `git archive HEAD` + its own build) against the working tree: bench lines alternately
-# usage (GPU box): bash tools/ab_old_new.sh [rounds] [bench args...]
+# usage (GPU box): bash tools/ab_old_new.sh [rounds] [bench args...]   (--full among them fills the forward and config_r columns)
 R=${1:-2}; shift
 for i in $(seq 1 $R); do
   (cd ab_old && python bench.py --no-branch-section "$@" > ../gpurun_out/ab_old_$i.json 2> ../gpurun_out/ab_old_$i.err)

@@ -6,7 +6,7 @@ import collections, csv, glob, json, sys
 FAMILIES = {'k_wino43': 'k_wino43<', 'k_wino_wgrad_rows': 'k_wino_wgrad_rows(', 'k_gather_gemm_dma<1>': 'k_gather_gemm_dma<1,',
             'k_plane_gemm': 'k_plane_gemm<', 'k_plane_wgrad': 'k_plane_wgrad<', 'k_gather_wgrad<1>': 'k_gather_wgrad<1,'}
 out = {'command': sys.argv[2], 'note': 'per family: counter / SQ_WAVE_CYCLES of the same pass (`per_wave_cycle`) and raw sums; launches of one '
-                                       'training step (bench.py --steps 1 --warmup 1 => 2 steps + the single-stream pass)', 'families': {}}
+                                       'training step (a plain bench.py --steps 1 --warmup 1 => 2 steps)', 'families': {}}
 per = {k: {} for k in FAMILIES}
 raw = {k: {} for k in FAMILIES}
 for d in sys.argv[3:]:

@@ -1,5 +1,5 @@
 """how much of a training step runs with 1 / 2 / 3 / 4 streams busy, and which kernels run alone?
-    python tools/stream_overlap.py <rocprofv3 kernel_trace.csv of `bench.py --no-forward-section`>"""
+    python tools/stream_overlap.py <rocprofv3 kernel_trace.csv of `bench.py --full --no-forward-section`>"""
 import collections
 import csv
 import sys
@@ -7,7 +7,7 @@ import sys
 rows = list(csv.DictReader(open(sys.argv[1])))
 rows.sort(key=lambda r: int(r['Start_Timestamp']))
 n = len(rows)
-rows = rows[n // 4: n * 5 // 8]                            # steady-state steps of the timed region (bench.py --steps 6 --warmup 2: 12 steps in the trace, the last 4 are the single-stream pass)
+rows = rows[n // 4: n * 5 // 8]                            # steady-state steps of the timed region (bench.py --full --steps 6 --warmup 2: 12 steps in the trace, the last 4 are the single-stream pass)
 ev = []
 for r in rows:
     ev.append((int(r['Start_Timestamp']), 1, r))
