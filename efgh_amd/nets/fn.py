@@ -162,8 +162,7 @@ class GemmLayerFn(torch.autograd.Function):
         mean = invstd = raw = None
         need_stats = bn is not None and spec.train
         stats = None
-        thin = spec.custom_forward is not None or all(
-            ops.thin_eligible(spec.mode, spec.C, Np, spec.T if g is None else len(g[7])) for g, _ in spec.launches)
+        thin = spec.custom_forward is not None or ops.no_stats_epilogue(spec.mode, spec.C, Np, spec.T, spec.launches)
         if need_stats and not thin:
             gs = [ops.stats_rows(spec.mode, spec.C, Np, g, m) for (g, m) in spec.launches]
             stats = torch.empty((sum(gs), 2, Np), dtype=torch.float32, device=dev)
@@ -294,11 +293,9 @@ class GemmLayerFn(torch.autograd.Function):
         dev = x.device
         fused_pool = spec.pool and has_bn and spec.train and not has_res and Np == N
         if TRACE is not None:
-            g0 = spec.launches[0][0] if spec.launches else None
+            g0, m0 = spec.launches[0] if spec.launches else (None, M)
             TRACE.append(dict(M=M, N=N, C=spec.C, T=spec.T, mode=spec.mode, bn=has_bn, res=has_res, pool=spec.pool, act=spec.act,
-                              nl=len(spec.launches), wino=bool(g0 is not None and ops.wino_eligible(spec.mode, spec.C, Np, g0)),
-                              wino2d=bool(g0 is not None and ops.wino2d_eligible(spec.mode, spec.C, Np, g0)),
-                              c4=bool(g0 is not None and ops.c4_eligible(spec.mode, spec.C, Np, g0)),
+                              nl=len(spec.launches), route=ops.gemm_route(spec.mode, spec.C, Np, spec.T if g0 is None else len(g0[7]), g0, m0),
                               x_from=getattr(x, '_efgh_src', None), dx=bool(ctx.needs_input_grad[0]),
                               in_elems=int(x.numel()), custom=spec.custom_forward is not None))
         if spec.pool and not fused_pool:    # pooled gradient -> full resolution (window recomputed from raw*scale+shift)

@@ -109,8 +109,7 @@ def _run(ctx, x, lda, C, T, Wp, N, M, mode, geoms, out_t, ldo, coff, bias, bn, a
         return
     assert not pool
     # train-mode BatchNorm: raw conv output + per-block column statistics, then normalise in place
-    thin = all(ops.thin_eligible(mode, C, Np, T if geom is None else len(geom[7])) for geom, _, _ in geoms)
-    if thin:       # VALU kernels carry no statistics epilogue: one extra streaming pass over the (small) output
+    if ops.no_stats_epilogue(mode, C, Np, T, [(geom, m) for geom, _, m in geoms]):      # one extra streaming pass over the (small) output
         for geom, wp, m in geoms:
             ops.gather_gemm(x, lda, C, len(geom[7]), wp, Np, m, out_t, ldo, mode=mode, geom=geom, bias=b,
                             act=ACT_NONE, a_off=a_off, out_off=coff, flops=fl(geom, m))
@@ -327,8 +326,7 @@ def _pool_fusable_eval(x, conv):
     B, H, W, ldx = x.shape
     if ldx != ceil4(conv.in_channels):
         return False
-    geom = (B, H, W, H, W, 1, 1, [t // 3 - 1 for t in range(9)], [t % 3 - 1 for t in range(9)], H, W, 1, 1, 0, 0)
-    return ops.pool_fusable(1, ldx, ceil4(conv.out_channels), geom)
+    return ops.pool_fusable(1, ldx, ceil4(conv.out_channels), _same3x3_geom(B, H, W))
 
 
 def run_vgg(ctx, features, x):

@@ -3,6 +3,7 @@ the stream only; every arithmetic op below runs in libefgh_hip.so.  No CPU fallb
 import ctypes
 import os as _os
 import threading
+import weakref
 
 import torch
 
@@ -291,7 +292,6 @@ def _sentinel_stale(holder, device):
 def pack_weight(w, N, T, C, sn, sc, st, taps=None, Np=None, Cp=None, key=None):
     """Wp[n][t][c] = w.flat[n*sn + c*sc + taps[t]*st]; optionally zero-padded to (Np, T, Cp).  With a `key` the layout gets a
     persistent buffer on the weight that is re-packed IN PLACE when the weight changes (derived caches see `_efgh_gen` move)."""
-    import weakref
     Np = Np or N
     Cp = Cp or C
     prm = (N, T, C, Np, Cp, sn, sc, st, None if taps is None else tuple(int(t) for t in taps))
@@ -356,7 +356,7 @@ def gemm_grid_m(M, N):
 USE_WINO = True  # Winograd F(4,3) kernel for the "same" 3x3 convolutions
 
 
-def wino_eligible(mode, C, N, geom, T=None):
+def wino_eligible(mode, C, N, geom):
     """the layers efgh_wino_conv3x3 serves (mirror of efgh_wino_supported): 3x3, stride 1, pad 1, C%16 == N%64 == 0"""
     if not USE_WINO or mode != 1 or geom is None or C % 16 or N % 64:
         return False
@@ -448,19 +448,6 @@ def _sc_aligned(d, lda, ldo, residual, ldr, stats):
     return ok
 
 
-def stats_rows(mode, C, N, geom, M):
-    """rows of the per-tile BatchNorm statistics buffer the GEMM launch for this layer writes"""
-    if sc_eligible(mode, C, N, geom):
-        return _L().efgh_sc_stats_rows(c_int32(geom[0]), c_int32(geom[1]), c_int32(geom[2]))
-    if c4_eligible(mode, C, N, geom):
-        return _L().efgh_c4_stats_rows(c_int32(geom[0]), c_int32(geom[9]), c_int32(geom[10]))
-    if wino2d_eligible(mode, C, N, geom):
-        return _L().efgh_wino2d_stats_rows(c_int32(geom[0]), c_int32(geom[1]), c_int32(geom[2]), c_int32(N))
-    if wino_eligible(mode, C, N, geom):
-        return _L().efgh_wino_grid_m(c_int32(geom[0]), c_int32(geom[1]), c_int32(geom[2]))
-    return gemm_grid_m(M, N)
-
-
 def wino_weight(Wp, N, C):
     """U = G w of a packed [N][9][C] weight (efgh_wino_pack), cached on the packed tensor"""
     def make():
@@ -507,6 +494,137 @@ PROFILE = None          # bench.py sets this to a list: (start_event, end_event,
 KSPLIT_MAX_ROWS = 16384
 
 
+# ----------------------------------------------------------------------------------------------
+# which kernel serves a launch: the order of preference, once per side ("Which kernel serves a launch")
+# ----------------------------------------------------------------------------------------------
+def gemm_route(mode, C, N, T, geom, M, stats=False, M_dev=False, batch=False, pool=False, plain=True, aligned=True):
+    """the kernel family that serves a forward / data-gradient launch - the first match below - from what is known before any pointer
+    exists (stats / M_dev / batch: given or not; pool: as asked for; plain: no scale, shift or residual and a bias of N values or
+    none).  'sc' moves 16-byte vectors: when its launch-time check (_sc_aligned) fails, gather_gemm asks again with aligned=False."""
+    if mode == MODE_BLUR_R:
+        return 'blur_r'
+    if (KSPLIT_MAX_ROWS and mode == 2 and M <= KSPLIT_MAX_ROWS and T == 15 and N % 4 == 0 and T * C >= 1024 and plain
+            and not (stats or M_dev or batch)):
+        return 'ksplit'
+    if not (stats or M_dev) and thin_eligible(mode, C, N, T):
+        return 'thin'
+    if M_dev or batch:
+        return 'gemm'
+    if c4_eligible(mode, C, N, geom):
+        return 'c4'
+    if aligned and sc_eligible(mode, C, N, geom):
+        return 'sc'
+    if wino2d_eligible(mode, C, N, geom):
+        return 'wino2d'
+    if wino_eligible(mode, C, N, geom):
+        return 'wino_hpool' if pool == 'h' else 'wino'
+    return 'gemm'
+
+
+def wgrad_route(mode, C, N, T, geom, aligned=True):
+    """the weight-gradient twin of gemm_route.  'c4n4', 'sc_c4' and 'sc' have a launch-time check (_wgrad_aligned): when it fails,
+    gather_wgrad asks again with aligned=False"""
+    if mode == MODE_BLUR_R:
+        return 'blur_r'
+    if aligned and C == 4 and N == 4 and T == 9 and mode == 1:
+        return 'c4n4'       # the 1- / 2-channel 3x3 convolutions behind G's transposed heads: column-walking stencil
+    if thin_eligible(mode, C, N, T) and (N == 4 or (T in (1, 2, 4, 9) and _pow2(N // 4))):
+        return 'thin'
+    if (aligned and USE_SMALLC and C == 4 and N in (32, 64) and geom is not None and geom[5] == 1
+            and sc_eligible(mode, 16, 16, geom, wgrad=True)):
+        return 'sc_c4'      # 4-channel input layers at stride 1 on the small-channel kernel (16-byte G loads) instead of k_c4_wgrad
+    if c4_eligible(mode, C, N, geom, wgrad=True):
+        return 'c4'
+    if aligned and sc_eligible(mode, C, N, geom, wgrad=True):
+        return 'sc'
+    if USE_WINO_WGRAD and wino2d_eligible(mode, C, N, geom, wgrad=True):
+        return 'wino2d'
+    if USE_WINO_WGRAD and C % 64 == 0 and wino_eligible(mode, C, N, geom):
+        return 'wino'
+    return 'gemm'
+
+
+def stats_rows(mode, C, N, geom, M):
+    """rows of the per-tile BatchNorm statistics buffer the GEMM launch for this layer writes"""
+    route = gemm_route(mode, C, N, 1 if geom is None else len(geom[7]), geom, M, stats=True)
+    if route == 'sc':
+        return _L().efgh_sc_stats_rows(c_int32(geom[0]), c_int32(geom[1]), c_int32(geom[2]))
+    if route == 'c4':
+        return _L().efgh_c4_stats_rows(c_int32(geom[0]), c_int32(geom[9]), c_int32(geom[10]))
+    if route == 'wino2d':
+        return _L().efgh_wino2d_stats_rows(c_int32(geom[0]), c_int32(geom[1]), c_int32(geom[2]), c_int32(N))
+    if route == 'wino':
+        return _L().efgh_wino_grid_m(c_int32(geom[0]), c_int32(geom[1]), c_int32(geom[2]))
+    return gemm_grid_m(M, N)
+
+
+def no_stats_epilogue(mode, C, N, T, launches):
+    """`launches`: the [(geom, M)] of one layer.  True when every one of them lands on the thin kernels, which carry no statistics
+    epilogue: the layer passes no `stats` (with `stats` the launch goes to another family) and calls col_stats on its output"""
+    return all(gemm_route(mode, C, N, T if g is None else len(g[7]), g, m) == 'thin' for g, m in launches)
+
+
+def _desc(A, lda, C, T, mode, N, M, geom=None, table=None, a_off=0, Wp=None, out=None, ldo=0, out_off=0, bias=None, scale=None,
+          shift=None, residual=None, ldr=0, res_off=0, act=ACT_NONE, slope=0.0, stats=None, M_dev=None, batch=None):
+    """efgh_gemm_desc of a launch: geometry, element offsets of the channel slices, epilogue pointers, batch strides"""
+    d = _C.GemmDesc()            # (zero-filled: only what a launch has is set - every field assignment costs host time)
+    if A is not None:
+        d.A = A.data_ptr() + 4 * a_off
+    d.lda, d.C, d.T, d.mode, d.N, d.M = lda, C, T, mode, N, M
+    if geom is not None:
+        (d.B, d.Hin, d.Win, d.Hv, d.Wv, d.sh, d.sw, dh, dw, d.Ho, d.Wo, d.osh, d.osw, d.oh0, d.ow0) = geom
+        for i, (a, b) in enumerate(zip(dh, dw)):
+            d.dh[i], d.dw[i] = a, b
+    for field, t in (('table', table), ('W', Wp), ('bias', bias), ('scale', scale), ('shift', shift), ('stats', stats), ('M_dev', M_dev)):
+        if t is not None:
+            setattr(d, field, t.data_ptr())
+    if out is not None:
+        d.out, d.ldo = out.data_ptr() + 4 * out_off, ldo
+    if residual is not None:
+        d.residual = residual.data_ptr() + 4 * res_off
+    d.ldr, d.act, d.slope = ldr, act, slope
+    if batch is not None:
+        d.nbatch, d.batch_stride_a, d.batch_stride_w, d.batch_stride_out = batch[:4]
+        if len(batch) > 4:
+            d.batch_stride_table = batch[4]
+    return d
+
+
+_DEDICATED = ('thin', 'c4', 'c4n4', 'sc_c4')      # HBM-bound launches on a dedicated kernel: never part of the MFMA GEMM families
+
+
+def _prof_start(on):
+    """bench.py only: the event pair around a launch when the profile list `on` is set, the first one recorded"""
+    if on is None:
+        return None
+    ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+    ev[0].record()
+    return ev
+
+
+def _prof_end(ev, route, shape, flops, plain, wino_list=None, batched=False):
+    """close the pair and append (e0, e1, flops or bytes, (mode, M, N, T, C)): HBM-bound launches (the dedicated kernels, and what
+    hbm_bound() says of the rest) to PROFILE_THIN with their bytes, the dedicated and small-channel ones to PROFILE_DED as well;
+    the others with their flops to PROFILE_WINO2D, to `wino_list` (1-D Winograd) or to `plain`"""
+    if ev is None:
+        return
+    ev[1].record()
+    if route in ('blur_r', 'planes'):
+        plain.append(ev + (flops, shape))
+        return
+    nbytes = conv_bytes(*shape[1:])
+    if PROFILE_DED is not None and (route in _DEDICATED or route == 'sc'):
+        PROFILE_DED.append(ev + (nbytes, shape))
+    wino = route in ('wino2d', 'wino', 'wino_hpool')
+    if route in _DEDICATED or (not wino and not batched and hbm_bound(*shape[1:])):
+        if PROFILE_THIN is not None:
+            PROFILE_THIN.append(ev + (nbytes, shape))
+    elif route == 'wino2d' and PROFILE_WINO2D is not None:
+        PROFILE_WINO2D.append(ev + (flops, shape))
+    else:
+        (wino_list if (wino and wino_list is not None) else plain).append(ev + (flops, shape))
+
+
 def _blur_gemm_ksplit(A, lda, C, Wp, N, M, out, ldo, table, bias, act, slope, a_off, out_off, flops, alias_mask=False):
     """BCL blur on a level with few vertices (M <= 16 k rows: 9-75 workgroups each walking K = 15*C serially, 6-23 TFLOP/s): the
     15 neighbour taps are split over 5 problems of ONE batched launch (3 taps each, their own columns of the neighbour table and
@@ -539,115 +657,73 @@ def gather_gemm(A, lda, C, T, Wp, N, M, out, ldo, mode=0, geom=None, table=None,
     lazy: a LazyAct - A is the RAW output of a train-mode BatchNorm layer and act(A*scale + shift) is applied by the consumer (only the
     2-D Winograd input transform can: the caller asks lazy_capable() first).  pre_v: the input transform of the launch, already
     made (wino2d_bwd_transforms: the data gradient of a layer whose draw is never stored); A may then be None."""
-    if (lazy is not None or pre_v is not None) and not (M_dev is None and batch is None and lazy_capable(mode, C, N, geom)):
+    key = (mode, C, N, T, geom, M, stats is not None, M_dev is not None, batch is not None, pool,
+           scale is None and shift is None and residual is None and (bias is None or bias.numel() == N))
+    route = gemm_route(*key)
+    if (lazy is not None or pre_v is not None) and not (route == 'wino2d' and min(C, N) >= 64):
         raise _C.EfghError('gather_gemm(lazy= / pre_v=) on a launch the 2-D Winograd path does not serve (ask lazy_capable() first)')
-    if mode == MODE_BLUR_R:
+    if route == 'blur_r':
         if (geom is not None or batch is not None or M_dev is not None or scale is not None or shift is not None or residual is not None
                 or stats is not None or alias_mask or pool or bn_bwd is not None):
             raise _C.EfghError('gather_gemm(mode=MODE_BLUR_R) takes a plain blur launch: bias and activation only')
         blur_r_gemm(A, lda, C, T, Wp, N, M, out, ldo, table, bias=bias, act=act, slope=slope, a_off=a_off, out_off=out_off, flops=flops)
         return None
-    if (KSPLIT_MAX_ROWS and mode == 2 and M <= KSPLIT_MAX_ROWS and T == 15 and N % 4 == 0 and T * C >= 1024 and batch is None
-            and scale is None and shift is None and residual is None and stats is None and M_dev is None
-            and (bias is None or bias.numel() == N)):
+    if route == 'ksplit':
         return _blur_gemm_ksplit(A, lda, C, Wp, N, M, out, ldo, table, bias, act, slope, a_off, out_off, flops, alias_mask)
-    if PROFILE is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    bn_stats = None
-    d = _C.GemmDesc()
-    es = 4
-    d.A = (A.data_ptr() + a_off * es) if A is not None else 0
-    d.lda, d.C, d.T, d.mode = lda, C, T, mode
-    if geom is not None:
-        (d.B, d.Hin, d.Win, d.Hv, d.Wv, d.sh, d.sw, dh, dw, d.Ho, d.Wo, d.osh, d.osw, d.oh0, d.ow0) = geom
-        for i, (a, b) in enumerate(zip(dh, dw)):
-            d.dh[i], d.dw[i] = a, b
-    d.table = 0 if table is None else table.data_ptr()
-    d.W, d.N, d.M = Wp.data_ptr(), N, M
-    d.M_dev = 0 if M_dev is None else M_dev.data_ptr()
-    d.bias = 0 if bias is None else bias.data_ptr()
-    d.scale = 0 if scale is None else scale.data_ptr()
-    d.shift = 0 if shift is None else shift.data_ptr()
-    d.residual = 0 if residual is None else residual.data_ptr() + res_off * es
-    d.ldr, d.act, d.slope = ldr, act, slope
-    d.out = out.data_ptr() + out_off * es
-    d.ldo = ldo
-    d.stats = 0 if stats is None else stats.data_ptr()
-    if batch is not None:
-        d.nbatch, d.batch_stride_a, d.batch_stride_w, d.batch_stride_out = batch[:4]
-        d.batch_stride_table = batch[4] if len(batch) > 4 else 0
+    d = _desc(A, lda, C, T, mode, N, M, geom, table, a_off, Wp, out, ldo, out_off, bias, scale, shift, residual, ldr, res_off, act, slope,
+              stats, M_dev, batch)
     d.table_alias_mask = 1 if (alias_mask and mode == 2) else 0
-    thin = stats is None and M_dev is None and thin_eligible(mode, C, N, T)
-    wino = sc = False
-    if thin:
+    if route == 'sc' and not _sc_aligned(d, lda, ldo, residual, ldr, stats):
+        route = gemm_route(*key, aligned=False)
+    if pool and route not in ('c4', 'wino2d', 'wino_hpool'):
+        raise _C.EfghError('gather_gemm(pool=True) on a launch no pooling epilogue serves (ask pool_fusable() first)')
+    ev = _prof_start(PROFILE)
+    bn_stats = None
+    if route == 'thin':
         if TRACE_THIN is not None:
             TRACE_THIN.append(int(_L().efgh_thin_supported(ctypes.byref(d))))      # (tests: which form serves the launch)
         _C.check(_L().efgh_thin_gemm(ctypes.byref(d), _st()))
-    elif M_dev is None and batch is None and c4_eligible(mode, C, N, geom):
+    elif route == 'c4':
         assert lda % 4 == 0
-        thin = True             # (for the profile lists: an HBM-bound launch, not part of the MFMA GEMM family)
-        if pool:
-            _C.check(_L().efgh_c4_conv3x3_pooled(ctypes.byref(d), _st()))
-            pool = False
-        else:
-            _C.check(_L().efgh_c4_conv3x3(ctypes.byref(d), _st()))
-    elif M_dev is None and batch is None and sc_eligible(mode, C, N, geom) and _sc_aligned(d, lda, ldo, residual, ldr, stats):
-        sc = True
+        _C.check((_L().efgh_c4_conv3x3_pooled if pool else _L().efgh_c4_conv3x3)(ctypes.byref(d), _st()))
+    elif route == 'sc':
         _C.check(_L().efgh_sc_conv3x3(ctypes.byref(d), _st()))
-    elif M_dev is None and batch is None and wino2d_eligible(mode, C, N, geom):
-        wino = '2d'
+    elif route == 'wino2d':
         if (bn_bwd is not None and stats is None and BN_BWD_FUSED_2D and out_off == 0 and not pool and bn_bwd.fits(M, N)
                 and bn_bwd.y is None and bn_bwd.raw.stride(-2) % 4 == 0):
             # the BatchNorm-backward sums of the layer whose activation gradient this launch writes, in its output transform: that
-            # layer's reduction pass (a read of dy and of raw) is not run (efgh_gemm_desc.stats_mode 1)
+            # layer's reduction pass (a read of dy and of raw) is not run
             rows = _L().efgh_wino2d_stats_rows(c_int32(geom[0]), c_int32(geom[1]), c_int32(geom[2]), c_int32(N))
-            bn_stats = torch.empty((rows, 2, N), dtype=torch.float32, device=out.device)
-            d.stats, d.stats_mode = bn_stats.data_ptr(), 1
-            d.bn_raw, d.bn_ldraw = bn_bwd.raw.data_ptr(), bn_bwd.raw.stride(-2)
-            d.bn_pscale, d.bn_pshift = bn_bwd.psc.data_ptr(), bn_bwd.psh.data_ptr()
-            d.bn_mean, d.bn_invstd = bn_bwd.mean.data_ptr(), bn_bwd.invstd.data_ptr()
-            d.bn_act, d.bn_slope = bn_bwd.act, bn_bwd.slope
+            bn_stats = _bn_bwd_sums(d, bn_bwd, rows, N, out.device)
         _wino2d_forward(d, A, a_off, lda, C, N, geom, Wp, pool=pool, lazy=lazy, pre_v=pre_v)
-        pool = False
-    elif M_dev is None and batch is None and wino_eligible(mode, C, N, geom) and pool == 'h':
-        wino = True
-        pool = False
+    elif route == 'wino_hpool':
         _C.check(_L().efgh_wino_conv3x3_hpool(ctypes.byref(d), ptr(wino_weight(Wp, N, C)), _st()))
-    elif M_dev is None and batch is None and wino_eligible(mode, C, N, geom):
-        wino = True
+    elif route == 'wino':
         if bn_bwd is not None and stats is None and BN_BWD_FUSED and out_off == 0 and bn_bwd.fits(M, N):
             rows = _L().efgh_wino_grid_m(c_int32(geom[0]), c_int32(geom[1]), c_int32(geom[2]))
-            bn_stats = torch.empty((rows, 2, N), dtype=torch.float32, device=out.device)
-            d.stats, d.stats_mode = bn_stats.data_ptr(), 1
-            d.bn_raw, d.bn_ldraw = bn_bwd.raw.data_ptr(), bn_bwd.raw.stride(-2)
-            if bn_bwd.y is not None:
-                d.bn_y, d.bn_ldy = bn_bwd.y.data_ptr(), bn_bwd.y.stride(-2)
-            else:
-                d.bn_pscale, d.bn_pshift = bn_bwd.psc.data_ptr(), bn_bwd.psh.data_ptr()
-            d.bn_mean, d.bn_invstd = bn_bwd.mean.data_ptr(), bn_bwd.invstd.data_ptr()
-            d.bn_act, d.bn_slope = bn_bwd.act, bn_bwd.slope
+            bn_stats = _bn_bwd_sums(d, bn_bwd, rows, N, out.device)
         _C.check(_L().efgh_wino_conv3x3(ctypes.byref(d), ptr(wino_weight(Wp, N, C)), _st()))
     else:
         _C.check(_L().efgh_gather_gemm(ctypes.byref(d), _st()))
-    if pool:
-        raise _C.EfghError('gather_gemm(pool=True) on a launch no pooling epilogue serves (ask pool_fusable() first)')
-    if PROFILE is not None and (thin or (not wino and batch is None and hbm_bound(M, N, T, C))):
-        e1.record()
-        if PROFILE_THIN is not None:
-            PROFILE_THIN.append((e0, e1, conv_bytes(M, N, T, C), (mode, M, N, T, C)))
-        if PROFILE_DED is not None and (thin or sc):      # every launch a dedicated kernel (thin / 4-channel / small-channel) served
-            PROFILE_DED.append((e0, e1, conv_bytes(M, N, T, C), (mode, M, N, T, C)))
-    elif PROFILE is not None:
-        e1.record()
-        if PROFILE_DED is not None and sc:
-            PROFILE_DED.append((e0, e1, conv_bytes(M, N, T, C), (mode, M, N, T, C)))
-        rec = (e0, e1, float(flops) if flops is not None else 2.0 * M * N * T * C, (mode, M, N, T, C))
-        if wino == '2d' and PROFILE_WINO2D is not None:
-            PROFILE_WINO2D.append(rec)
-        else:
-            (PROFILE_WINO if (wino and PROFILE_WINO is not None) else PROFILE).append(rec)
+    if ev is not None:
+        _prof_end(ev, route, (mode, M, N, T, C), float(flops) if flops is not None else 2.0 * M * N * T * C, PROFILE, PROFILE_WINO,
+                  batched=batch is not None)
     return bn_stats
+
+
+def _bn_bwd_sums(d, src, rows, N, device):
+    """the column sums of the BatchNorm backward of `src` (a BnSrc) in the epilogue of launch `d` (efgh_gemm_desc.stats_mode 1)
+    -> the [rows][2][N] partials the launch leaves"""
+    part = torch.empty((rows, 2, N), dtype=torch.float32, device=device)
+    d.stats, d.stats_mode = part.data_ptr(), 1
+    d.bn_raw, d.bn_ldraw = src.raw.data_ptr(), src.raw.stride(-2)
+    if src.y is not None:
+        d.bn_y, d.bn_ldy = src.y.data_ptr(), src.y.stride(-2)
+    else:
+        d.bn_pscale, d.bn_pshift = src.psc.data_ptr(), src.psh.data_ptr()
+    d.bn_mean, d.bn_invstd = src.mean.data_ptr(), src.invstd.data_ptr()
+    d.bn_act, d.bn_slope = src.act, src.slope
+    return part
 
 
 GEMM_DMA = True                 # eligible efgh_gather_gemm launches on the LDS-DMA staged instances (a process-wide switch of the library)
@@ -684,14 +760,8 @@ def _planes_split_now():
 
 def _batched_plain_gemm(A3, W3, out3, rows, C, N):
     """out3[a] = A3[a] @ W3[a]^T for the 36 alpha planes: k_gather_gemm, mode 0, one launch"""
-    g = _C.GemmDesc()
-    g.A, g.lda, g.C, g.T, g.mode = A3.data_ptr(), 36 * C, C, 1, 0          # activations are tile-major [rows][36][C]
-    g.W, g.N, g.M = W3.data_ptr(), N, rows
-    g.out, g.ldo = out3.data_ptr(), 36 * N
-    g.nbatch, g.batch_stride_a, g.batch_stride_w, g.batch_stride_out = 36, C, N * C, N
-    if PROFILE_WINO2D_GEMM is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
+    g = _desc(A3, 36 * C, C, 1, 0, N, rows, Wp=W3, out=out3, ldo=36 * N, batch=(36, C, N * C, N))      # tile-major [rows][36][C]
+    ev = _prof_start(PROFILE_WINO2D_GEMM)
     if PLANE_DMA and _L().efgh_plane_gemm_supported(ctypes.byref(g)):
         if _planes_split_now():
             PLANE_SPLIT_HITS[0] += 1
@@ -700,9 +770,7 @@ def _batched_plain_gemm(A3, W3, out3, rows, C, N):
             _C.check(_L().efgh_plane_gemm(ctypes.byref(g), c_int32(PLANE_DMA_NBUF), _st()))      # LDS-DMA staged (planes.hip)
     else:
         _C.check(_L().efgh_gather_gemm(ctypes.byref(g), _st()))
-    if PROFILE_WINO2D_GEMM is not None:
-        e1.record()
-        PROFILE_WINO2D_GEMM.append((e0, e1, 2.0 * 36 * rows * C * N, (0, rows, N, 36, C)))
+    _prof_end(ev, 'planes', (0, rows, N, 36, C), 2.0 * 36 * rows * C * N, PROFILE_WINO2D_GEMM)
 
 
 W2V_CACHE = {}          # training: B^T x B of a layer's input, kept from the forward for the layer's weight gradient
@@ -729,17 +797,12 @@ def pool_fusable(mode, C, N, geom, residual=None, stats=None):
     path); 'h': the horizontal half (1-D Winograd path; `out` is [B][Ho][Wo/2][ldo], maxpool_v2 follows); False: no"""
     if not (POOL_FUSED and residual is None and stats is None and geom is not None and geom[1] >= 2 and geom[2] >= 2):
         return False
-    if thin_eligible(mode, C, N, len(geom[7])):
-        return False
-    if c4_eligible(mode, C, N, geom):                    # (gather_gemm's order of preference)
+    route = gemm_route(mode, C, N, len(geom[7]), geom, geom[0] * geom[3] * geom[4], pool='h')
+    if route == 'c4':
         return geom[5] == 1 and geom[6] == 1
-    if sc_eligible(mode, C, N, geom):
-        return False
-    if wino2d_eligible(mode, C, N, geom):
+    if route == 'wino2d':
         return True
-    if POOL_HALF and wino_eligible(mode, C, N, geom) and geom[2] >= 2:
-        return 'h'              # 1-D Winograd: the horizontal half in its epilogue, maxpool_v2 finishes the window
-    return False
+    return 'h' if (route == 'wino_hpool' and POOL_HALF) else False      # 1-D Winograd: maxpool_v2 finishes the window
 
 
 class LazyAct:
@@ -759,9 +822,10 @@ LAZY_HITS = [0, 0]              # (tests: deferred activations consumed, fused b
 
 
 def lazy_capable(mode, C, N, geom):
-    """does gather_gemm serve this launch on the 2-D Winograd path (whose input transform can apply a pending BatchNorm + activation)?
-    (>= 128 channels on both sides: none of the kernels gather_gemm prefers - thin, 4-channel, small-channel - overlaps)"""
-    return geom is not None and wino2d_eligible(mode, C, N, geom) and min(C, N) >= 64
+    """does gather_gemm serve this launch on the 2-D Winograd path (whose input transform can apply a pending BatchNorm + activation),
+    with at least 64 channels on both sides?  (One condition on top of the route: under the default thresholds the route itself asks
+    for 128; with WINO2D_MIN_C* lowered it sends narrower layers there too, and their producers go on materialising the activation.)"""
+    return geom is not None and min(C, N) >= 64 and gemm_route(mode, C, N, len(geom[7]), geom, 0) == 'wino2d'
 
 
 def wino2d_input(A, a_off, lda, C, B, H, W, V, lazy=None):
@@ -1079,48 +1143,31 @@ MODE_BLUR_R = 4                 # gather_gemm / gather_wgrad mode of those launc
 BLUR_R_HITS = [0, 0, 0]         # (tests: radius-r blur launches - forward, data gradient, weight gradient)
 
 
-def _blur_r_desc(A, lda, C, F, N, M, table, a_off=0):
+def _blur_r_desc(A, lda, C, F, N, M, table, **epilogue):
     ld = table.shape[1]
     if table.dtype != torch.int32 or table.dim() != 2 or table.shape[0] < M or ld < F + (F + 31) // 32 or not table.is_contiguous():
         raise _C.EfghError('blur table: [>= %d][>= F + ceil(F/32)] int32 expected for F = %d, got %s %s' % (M, F, tuple(table.shape), table.dtype))
-    d = _C.GemmDesc()
-    d.A = A.data_ptr() + 4 * a_off
-    d.lda, d.C, d.T, d.mode = lda, C, F, 2
-    d.table = table.data_ptr()
-    d.N, d.M = N, M
-    return d, ld
+    return _desc(A, lda, C, F, 2, N, M, table=table, **epilogue), ld
 
 
 def blur_r_gemm(A, lda, C, F, Wp, N, M, out, ldo, table, bias=None, act=ACT_NONE, slope=0.0, a_off=0, out_off=0, flops=None, hit=0):
     """out[m][n] = act(sum_{t<F,c<C} A[table[m][t]][c] * Wp[n][t*C + c] + bias[n]) through a radius-r neighbour table
     (efgh_blur_r_gemm; a missing neighbour reads zeros).  hit: which BLUR_R_HITS counter the launch counts in"""
-    d, ld = _blur_r_desc(A, lda, C, F, N, M, table, a_off)
-    d.W = Wp.data_ptr()
-    d.bias = 0 if bias is None else bias.data_ptr()
-    d.act, d.slope = act, slope
-    d.out, d.ldo = out.data_ptr() + 4 * out_off, ldo
-    if PROFILE is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
+    d, ld = _blur_r_desc(A, lda, C, F, N, M, table, a_off=a_off, Wp=Wp, out=out, ldo=ldo, out_off=out_off, bias=bias, act=act, slope=slope)
+    ev = _prof_start(PROFILE)
     _C.check(_L().efgh_blur_r_gemm(ctypes.byref(d), c_int32(ld), _st()))
     BLUR_R_HITS[hit] += 1
-    if PROFILE is not None:
-        e1.record()
-        PROFILE.append((e0, e1, float(flops) if flops is not None else 2.0 * M * N * F * C, (MODE_BLUR_R, M, N, F, C)))
+    _prof_end(ev, 'blur_r', (MODE_BLUR_R, M, N, F, C), float(flops) if flops is not None else 2.0 * M * N * F * C, PROFILE)
 
 
 def blur_r_wgrad(A, lda, C, F, N, M, G, ldg, dWp, table):
     """dWp[n][t*C + c] = sum_m G[m][n] * A[table[m][t]][c]   (efgh_blur_r_wgrad; dWp [N][F][C], N % 4 == 0)"""
     d, ld = _blur_r_desc(A, lda, C, F, N, M, table)
-    if PROFILE_WGRAD is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
+    ev = _prof_start(PROFILE_WGRAD)
     _C.check(_L().efgh_blur_r_wgrad(ctypes.byref(d), c_int32(ld), ptr(G), c_int64(ldg), ptr(dWp),
                                     ptr(_scratch(_L().efgh_gather_wgrad_workspace(ctypes.byref(d)), dWp.device)), _st()))
     BLUR_R_HITS[2] += 1
-    if PROFILE_WGRAD is not None:
-        e1.record()
-        PROFILE_WGRAD.append((e0, e1, 2.0 * M * N * F * C, (MODE_BLUR_R, M, N, F, C)))
+    _prof_end(ev, 'blur_r', (MODE_BLUR_R, M, N, F, C), 2.0 * M * N * F * C, PROFILE_WGRAD)
 
 
 def blur_r_pack(w, inv=None):
@@ -1308,8 +1355,21 @@ FOLD_UNPACK_HITS = [0]   # (tests: how many weight gradients took that route)
 
 
 def wgrad_lazy_capable(mode, C, N, geom):
-    """does gather_wgrad serve this launch on the 2-D Winograd path?"""
-    return bool(USE_WINO_WGRAD and geom is not None and wino2d_eligible(mode, C, N, geom, wgrad=True) and min(C, N) >= 64)
+    """does gather_wgrad serve this launch on the 2-D Winograd path, with at least 64 channels on both sides (see lazy_capable)?"""
+    return geom is not None and min(C, N) >= 64 and wgrad_route(mode, C, N, len(geom[7]), geom) == 'wino2d'
+
+
+# the families whose entry point takes (desc, G, ldg, dWp, workspace, out desc): the entry point and its workspace query
+_WGRAD_ENTRY = {'c4n4': ('efgh_c4n4_wgrad', 'efgh_c4n4_wgrad_workspace'), 'thin': ('efgh_thin_wgrad', 'efgh_thin_wgrad_workspace'),
+                'sc_c4': ('efgh_sc_wgrad', 'efgh_sc_wgrad_workspace'), 'c4': ('efgh_c4_wgrad', 'efgh_c4_wgrad_workspace'),
+                'sc': ('efgh_sc_wgrad', 'efgh_sc_wgrad_workspace'), 'gemm': ('efgh_gather_wgrad', 'efgh_gather_wgrad_workspace')}
+
+
+def _wgrad_aligned(route, d, lda, ldg, G, dWp):
+    """launch-time half of the weight-gradient route: the stencil and the small-channel kernel move 16-byte vectors"""
+    if route == 'c4n4':
+        return lda % 4 == 0 and ldg % 4 == 0 and dWp.data_ptr() % 16 == 0 and _L().efgh_c4n4_supported(ctypes.byref(d))
+    return lda % 4 == 0 and ldg % 4 == 0 and d.A % 16 == 0 and G.data_ptr() % 16 == 0
 
 
 def gather_wgrad(A, lda, C, T, N, M, G, ldg, dWp, mode=0, geom=None, table=None, unpack=None, lazy=None, pre_gy=None):
@@ -1318,9 +1378,10 @@ def gather_wgrad(A, lda, C, T, N, M, G, ldg, dWp, mode=0, geom=None, table=None,
     NOT written), False when dWp holds the packed gradient and the caller has to unpack it (always so for mode MODE_BLUR_R).
     lazy: A is a raw BatchNorm output with a pending activation (LazyAct; 2-D Winograd path only: the kept forward transform already has
     it applied, a re-transform applies it again).  pre_gy: the gradient-side transform, already made (wino2d_bwd_transforms); G may be None"""
-    if (lazy is not None or pre_gy is not None) and not wgrad_lazy_capable(mode, C, N, geom):
+    route = wgrad_route(mode, C, N, T, geom)
+    if (lazy is not None or pre_gy is not None) and not (route == 'wino2d' and min(C, N) >= 64):
         raise _C.EfghError('gather_wgrad(lazy= / pre_gy=) on a launch the 2-D Winograd weight gradient does not serve')
-    if mode == MODE_BLUR_R:
+    if route == 'blur_r':
         blur_r_wgrad(A, lda, C, T, N, M, G, ldg, dWp, table)
         return False
     od = None                # efgh_wgrad_out_desc: the entry points that can leave the reference layout themselves take it explicitly
@@ -1332,52 +1393,14 @@ def gather_wgrad(A, lda, C, T, N, M, G, ldg, dWp, mode=0, geom=None, table=None,
             od.taps[i_] = int(t__)
         od.accumulate = 1 if acc_ else 0
     odp = None if od is None else ctypes.byref(od)
-    done = False
-    if PROFILE_WGRAD is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    d = _C.GemmDesc()
-    d.A = A.data_ptr()
-    d.lda, d.C, d.T, d.mode = lda, C, T, mode
-    if geom is not None:
-        (d.B, d.Hin, d.Win, d.Hv, d.Wv, d.sh, d.sw, dh, dw, d.Ho, d.Wo, d.osh, d.osw, d.oh0, d.ow0) = geom
-        for i, (a, b) in enumerate(zip(dh, dw)):
-            d.dh[i], d.dw[i] = a, b
-    d.table = 0 if table is None else table.data_ptr()
-    d.N, d.M = N, M
-    # (round 4: no weight-gradient kernel combines partial sums with atomics any more - the thin and the stride-2 4-channel kernels
-    # leave per-workgroup / per-wave partial planes that are folded in a fixed order, like every other one: all 353 gradients of a
-    # training step are bit-reproducible run to run by default, and EFGH_DETERMINISTIC has nothing left to switch)
-    nq = N // 4
-    thin = thin_eligible(mode, C, N, T) and (N == 4 or (T in (1, 2, 4, 9) and nq & (nq - 1) == 0))
-    wino = sc = False
-    if (C == 4 and N == 4 and T == 9 and mode == 1 and lda % 4 == 0 and ldg % 4 == 0 and dWp.data_ptr() % 16 == 0
-            and _L().efgh_c4n4_supported(ctypes.byref(d))):
-        # the 1- / 2-channel 3x3 convolutions behind G's transposed heads: column-walking stencil, per-workgroup partial planes folded
-        # in a fixed order (also under EFGH_DETERMINISTIC: no atomics)
-        thin = True             # (profile lists: an HBM-bound launch)
-        done = _C.check_wrote(_L().efgh_c4n4_wgrad(ctypes.byref(d), ptr(G), c_int64(ldg), ptr(dWp),
-                                                   ptr(_scratch(_L().efgh_c4n4_wgrad_workspace(ctypes.byref(d)), dWp.device)), odp, _st()))
-    elif thin:
-        done = _C.check_wrote(_L().efgh_thin_wgrad(ctypes.byref(d), ptr(G), c_int64(ldg), ptr(dWp),
-                                                   ptr(_scratch(_L().efgh_thin_wgrad_workspace(ctypes.byref(d)), dWp.device)), odp, _st()))
-    elif (USE_SMALLC and C == 4 and N in (32, 64) and lda % 4 == 0 and ldg % 4 == 0 and d.A % 16 == 0 and G.data_ptr() % 16 == 0
-          and geom is not None and geom[5] == 1 and sc_eligible(mode, 16, 16, geom, wgrad=True)):
-        # 4-channel input layers at stride 1: the small-channel weight-gradient kernel (G staged by 16-byte loads, per-wave partial
-        # planes folded in a fixed order) instead of k_c4_wgrad (4-byte G loads, fp32 atomics)
-        thin = True             # (profile lists: an HBM-bound launch)
-        done = _C.check_wrote(_L().efgh_sc_wgrad(ctypes.byref(d), ptr(G), c_int64(ldg), ptr(dWp),
-                                                 ptr(_scratch(_L().efgh_sc_wgrad_workspace(ctypes.byref(d)), dWp.device)), odp, _st()))
-    elif c4_eligible(mode, C, N, geom, wgrad=True):
-        thin = True             # (profile lists, as above)
-        done = _C.check_wrote(_L().efgh_c4_wgrad(ctypes.byref(d), ptr(G), c_int64(ldg), ptr(dWp),
-                                                 ptr(_scratch(_L().efgh_c4_wgrad_workspace(ctypes.byref(d)), dWp.device)), odp, _st()))
-    elif sc_eligible(mode, C, N, geom, wgrad=True) and lda % 4 == 0 and ldg % 4 == 0 and d.A % 16 == 0 and G.data_ptr() % 16 == 0:
-        sc = True
-        done = _C.check_wrote(_L().efgh_sc_wgrad(ctypes.byref(d), ptr(G), c_int64(ldg), ptr(dWp),
-                                                 ptr(_scratch(_L().efgh_sc_wgrad_workspace(ctypes.byref(d)), dWp.device)), odp, _st()))
-    elif USE_WINO_WGRAD and wino2d_eligible(mode, C, N, geom, wgrad=True):
-        wino = '2d'
+    ev = _prof_start(PROFILE_WGRAD)
+    d = _desc(A, lda, C, T, mode, N, M, geom, table)
+    if route in ('c4n4', 'sc_c4', 'sc') and not _wgrad_aligned(route, d, lda, ldg, G, dWp):
+        route = wgrad_route(mode, C, N, T, geom, aligned=False)
+    # (round 4: no weight-gradient kernel combines partial sums with atomics any more - every family leaves per-workgroup / per-wave
+    # partial planes that are folded in a fixed order: all 353 gradients of a training step are bit-reproducible run to run by
+    # default, and EFGH_DETERMINISTIC has nothing left to switch)
+    if route == 'wino2d':
         B, H, W = geom[0], geom[1], geom[2]
         T2 = _L().efgh_wino2d_tiles(c_int32(B), c_int32(H), c_int32(W))
         dev = dWp.device
@@ -1397,12 +1420,8 @@ def gather_wgrad(A, lda, C, T, N, M, G, ldg, dWp, mode=0, geom=None, table=None,
         else:
             Gy = torch.empty((T2, 36, N), dtype=torch.float32, device=dev)
             _C.check(_L().efgh_wino2d_dy(ptr(G), c_int64(ldg), c_int32(N), c_int32(B), c_int32(H), c_int32(W), ptr(Gy), _st()))
-        g = _C.GemmDesc()
-        g.A, g.lda, g.C, g.T, g.mode, g.N, g.M = V.data_ptr(), 36 * C, C, 1, 0, N, T2
-        g.nbatch, g.batch_stride_a = 36, C
-        if PROFILE_WINO2D_GEMM is not None:
-            f0, f1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            f0.record()
+        g = _desc(V, 36 * C, C, 1, 0, N, T2, batch=(36, C, 0, 0))
+        pv = _prof_start(PROFILE_WINO2D_GEMM)
         if PLANE_DMA and _L().efgh_plane_wgrad_supported(ctypes.byref(g), c_int64(36 * N)):
             split = _planes_split_now()
             if split:
@@ -1413,34 +1432,19 @@ def gather_wgrad(A, lda, C, T, N, M, G, ldg, dWp, mode=0, geom=None, table=None,
         else:
             _C.check(_L().efgh_gather_wgrad_batched(ctypes.byref(g), ptr(Gy), c_int64(36 * N), c_int64(N), ptr(S), c_int64(N * C),
                                                     ptr(_scratch(_L().efgh_gather_wgrad_workspace(ctypes.byref(g)), dev)), _st()))
-        if PROFILE_WINO2D_GEMM is not None:
-            f1.record()
-            PROFILE_WINO2D_GEMM.append((f0, f1, 2.0 * 36 * T2 * C * N, (0, T2, N, 36, C)))
+        _prof_end(pv, 'planes', (0, T2, N, 36, C), 2.0 * 36 * T2 * C * N, PROFILE_WINO2D_GEMM)
         done = _C.check_wrote(_L().efgh_wino2d_wfinish(ptr(S), ptr(dWp), c_int32(N), c_int32(C), odp, _st()))      # (only the finish kernel may write the reference layout)
-    elif USE_WINO_WGRAD and C % 64 == 0 and wino_eligible(mode, C, N, geom):
-        wino = True
+    elif route == 'wino':
         S = _scratch(_L().efgh_wino_wgrad_workspace(ctypes.byref(d)), dWp.device)    # per-tile-range partials
         done = _C.check_wrote(_L().efgh_wino_wgrad(ctypes.byref(d), ptr(G), c_int64(ldg), ptr(S), ptr(dWp), odp, _st()))
     else:
-        done = _C.check_wrote(_L().efgh_gather_wgrad(ctypes.byref(d), ptr(G), c_int64(ldg), ptr(dWp),
-                                                     ptr(_scratch(_L().efgh_gather_wgrad_workspace(ctypes.byref(d)), dWp.device)), odp, _st()))
+        entry, workspace = _WGRAD_ENTRY[route]
+        S = _scratch(getattr(_L(), workspace)(ctypes.byref(d)), dWp.device)          # partial planes, folded in a fixed order
+        done = _C.check_wrote(getattr(_L(), entry)(ctypes.byref(d), ptr(G), c_int64(ldg), ptr(dWp), ptr(S), odp, _st()))
     if done:
         FOLD_UNPACK_HITS[0] += 1
-    if PROFILE_WGRAD is not None and (thin or (not wino and hbm_bound(M, N, T, C))):
-        e1.record()
-        if PROFILE_THIN is not None:
-            PROFILE_THIN.append((e0, e1, conv_bytes(M, N, T, C), (mode, M, N, T, C)))
-        if PROFILE_DED is not None and (thin or sc):
-            PROFILE_DED.append((e0, e1, conv_bytes(M, N, T, C), (mode, M, N, T, C)))
-    elif PROFILE_WGRAD is not None:
-        e1.record()
-        if PROFILE_DED is not None and sc:
-            PROFILE_DED.append((e0, e1, conv_bytes(M, N, T, C), (mode, M, N, T, C)))
-        rec = (e0, e1, 2.0 * M * N * T * C, (mode, M, N, T, C))
-        if wino == '2d' and PROFILE_WINO2D is not None:
-            PROFILE_WINO2D.append(rec)
-        else:
-            (PROFILE_WINO_WGRAD if (wino and PROFILE_WINO_WGRAD is not None) else PROFILE_WGRAD).append(rec)
+    if ev is not None:
+        _prof_end(ev, route, (mode, M, N, T, C), 2.0 * M * N * T * C, PROFILE_WGRAD, PROFILE_WINO_WGRAD)
     return done
 
 

@@ -437,8 +437,8 @@ def _desc(_C, C, N, geom):
 
 
 def test_dispatch_predicates_mirror_the_library(monkeypatch):
-    """over a grid of descriptors every Python *_eligible that ops.gather_gemm / gather_wgrad routes on implies the C predicate
-    of the kernel it routes to (Python never routes a launch the kernel refuses); those whose docstring claims a mirror are equal
+    """over a grid of descriptors every Python *_eligible that ops.gemm_route / wgrad_route decide on, and the family they name,
+    implies the C predicate of the kernel it routes to (Python never routes a launch the kernel refuses); those whose docstring claims a mirror are equal
     to it once the Python-only thresholds are 0 (WINO2D_MIN_C*, SC_MIN_PIXELS_32).  The 2-D Winograd form is a mirror only where
     the model can use it: maps of at least 8 x 8 and >= 64 channels on both sides (below, wino2d_eligible inherits the 1-D form's
     C % 16 / N % 64 and the map-size floor, which efgh_wino2d_supported does not ask for - stricter, never looser)"""
@@ -447,6 +447,10 @@ def test_dispatch_predicates_mirror_the_library(monkeypatch):
     lib = _C.lib()
     by = ctypes.byref
     chans = (1, 2, 3, 4, 16, 32, 64, 128, 256, 512)
+    FWD = {'thin': 'efgh_thin_supported', 'c4': 'efgh_c4_supported', 'sc': 'efgh_sc_supported', 'wino2d': 'efgh_wino2d_supported',
+           'wino': 'efgh_wino_supported'}
+    WGRAD = {'sc_c4': 'efgh_sc_wgrad_supported', 'sc': 'efgh_sc_wgrad_supported', 'c4': 'efgh_c4_wgrad_supported',
+             'wino2d': 'efgh_wino2d_supported', 'wino': 'efgh_wino_supported'}
     for thr in (False, True):
         if thr:
             for k in ('WINO2D_MIN_C', 'WINO2D_MIN_C_WGRAD', 'WINO2D_MIN_C_TRAIN', 'SC_MIN_PIXELS_32'):
@@ -456,6 +460,7 @@ def test_dispatch_predicates_mirror_the_library(monkeypatch):
             d = _desc(_C, C, N, geom)
             T = len(geom[7])
             w2d_exact = geom[1] >= 8 and geom[2] >= 8 and min(C, N) >= 64
+            fwd, wg = ops.gemm_route(1, C, N, T, geom, d.M), ops.wgrad_route(1, C, N, T, geom)
             pairs = [
                 ('wino', ops.wino_eligible(1, C, N, geom), lib.efgh_wino_supported(by(d)), True),
                 ('wino2d', ops.wino2d_eligible(1, C, N, geom), lib.efgh_wino2d_supported(by(d)), w2d_exact),
@@ -463,17 +468,20 @@ def test_dispatch_predicates_mirror_the_library(monkeypatch):
                 ('c4', ops.c4_eligible(1, C, N, geom), lib.efgh_c4_supported(by(d)), True),
                 ('c4 wgrad', ops.c4_eligible(1, C, N, geom, wgrad=True), lib.efgh_c4_wgrad_supported(by(d)), True),
                 ('sc', ops.sc_eligible(1, C, N, geom), lib.efgh_sc_supported(by(d)), True),
-                # (gather_wgrad also sends the 4-channel input layers at stride 1 to efgh_sc_wgrad)
-                ('sc wgrad', ops.sc_eligible(1, C, N, geom, wgrad=True) or (C == 4 and N in (32, 64) and geom[5] == 1 and
-                                                                          ops.sc_eligible(1, 16, 16, geom, wgrad=True)),
-                 lib.efgh_sc_wgrad_supported(by(d)), True),
+                # (the weight-gradient route also sends the 4-channel input layers at stride 1 to efgh_sc_wgrad: 'sc_c4')
+                ('sc wgrad', wg in ('sc', 'sc_c4'), lib.efgh_sc_wgrad_supported(by(d)), True),
                 ('thin', ops.thin_eligible(1, C, N, T), lib.efgh_thin_supported(by(d)), False),
             ]
+            # the family each route names implies the C predicate of the kernel that serves it
+            if fwd in FWD:
+                pairs.append(('route ' + fwd, True, getattr(lib, FWD[fwd])(by(d)), False))
+            if wg in WGRAD:
+                pairs.append(('wgrad route ' + wg, True, getattr(lib, WGRAD[wg])(by(d)), False))
             pf = ops.pool_fusable(1, C, N, geom)
-            if pf is True and ops.c4_eligible(1, C, N, geom):
+            if pf is True and fwd == 'c4':
                 pairs.append(('c4 pooled', True, lib.efgh_c4_pooled_supported(by(d)), False))
             elif pf is True:
-                pairs.append(('wino2d pooled', ops.wino2d_eligible(1, C, N, geom), lib.efgh_wino2d_supported(by(d)), False))
+                pairs.append(('wino2d pooled', fwd == 'wino2d', lib.efgh_wino2d_supported(by(d)), False))
             elif pf == 'h':
                 pairs.append(('wino hpool', True, lib.efgh_wino_supported(by(d)), False))
             for name, py, c, exact in pairs:

@@ -22,7 +22,7 @@ rows = FN.TRACE
 FN.TRACE = None
 agg = collections.OrderedDict()
 for r in rows:
-    kind = 'wino2d' if r['wino2d'] else 'wino' if r['wino'] else 'c4' if r['c4'] else 'custom' if r['custom'] else 'gemm%d' % r['mode']
+    kind = r['route'] if r['route'] in ('wino2d', 'wino', 'c4') else 'custom' if r['custom'] else 'gemm%d' % r['mode']
     key = (r['M'], r['C'], r['N'], r['T'], kind, r['bn'], r['res'], r['pool'], r['x_from'], r['dx'])
     agg[key] = agg.get(key, 0) + 1
 print('M C N T kernel bn res pool x_from dx | layers | act MB (out) | in MB')
