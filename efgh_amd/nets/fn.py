@@ -32,21 +32,29 @@ def ld_of(t):
 
 
 class LayerSpec:
-    """Static description of one GEMM layer (built by layers.py).
+    """Description of one GEMM layer, built once by its layer function in layers.py and run by either path: the no-tape executor
+    (layers._run) or GemmLayerFn.
 
-    launches: [(geom | None, M_launch)] forward launches (several for a transposed conv);
-    pack_fwd(weight, i) -> packed forward weight of launch i;
-    dgrad(spec, weight, draw, x) -> gradient w.r.t. x;
-    wgrad_unpack(dWp, i, dW): scatter launch i's packed weight gradient into the reference layout."""
+    N, C, T, mode, table: the gather-GEMM's (N the real output channel count, C the padded input one, c_real the real one);
+    launches: [(geom | None, M_launch)] forward launches (several for a transposed conv), layouts: one ops.WeightLayout per launch
+    (pack(weight) -> its packed forward weight, unpack / fold_args: where its packed weight gradient belongs);
+    M, out_shape: rows and leading shape of the output; bn, train, act, slope: the epilogue.
+    What only the tape path reads is set by for_tape()."""
+    dgrad = custom_forward = custom_wgrad = None
+    takes_bnsrc = passthrough = pool = defer_act = bwd_fusable = False
 
-    def __init__(self, N, C, T, mode, launches, M, out_shape, pack_fwd, dgrad, wgrad_unpack, bn=None,
-                 train=False, act=ACT_NONE, slope=0.0, table=None, c_real=None, custom_forward=None,
-                 custom_wgrad=None, passthrough=False, pool=False, defer_act=False, bwd_fusable=False):
+    def __init__(self, N, C, T, mode, launches, layouts, M, out_shape, bn=None, train=False, act=ACT_NONE, slope=0.0, table=None,
+                 c_real=None):
         self.N, self.C, self.T, self.mode, self.M = N, C, T, mode, M
-        self.launches, self.out_shape = launches, out_shape
-        self.pack_fwd, self.dgrad, self.wgrad_unpack = pack_fwd, dgrad, wgrad_unpack
+        self.launches, self.layouts, self.out_shape = launches, layouts, out_shape
         self.bn, self.train, self.act, self.slope, self.table = bn, train, act, slope, table
         self.c_real = c_real if c_real is not None else C
+
+    def for_tape(self, dgrad, takes_bnsrc=False, custom_forward=None, custom_wgrad=None, passthrough=False, pool=False,
+                 defer_act=False, bwd_fusable=False):
+        # dgrad(spec, weight, draw, x[, add=]) -> gradient w.r.t. x; takes_bnsrc: it also takes bnsrc= (the BnSrc of the layer that
+        # produced x) and pre_v=
+        self.dgrad, self.takes_bnsrc = dgrad, takes_bnsrc
         # optional replacements of the launch loop / weight gradient (e.g. transposed conv as GEMM + col2im)
         self.custom_forward, self.custom_wgrad = custom_forward, custom_wgrad
         # passthrough: forward also returns an alias of x for a skip connection; the gradient arriving on that alias is added
@@ -61,6 +69,58 @@ class LayerSpec:
         # bwd_fusable: the layer's data AND weight gradient both run on the 2-D Winograd path, so the BatchNorm backward's apply
         # pass can ride in their gradient-side transforms (ops.wino2d_bwd_transforms); its dgrad takes pre_v=
         self.bwd_fusable = bwd_fusable
+        return self
+
+
+def run_launches(spec, x, lda, weight, out, ldo, bias, want_stats, a_off=0, out_off=0, lazy=None, pool=False, w2v=None, **epilogue):
+    """the launch stage of both paths: pack each launch's weight and run the launches of `spec` (or its custom_forward) into `out`.
+    want_stats: train-mode BatchNorm follows - the per-column statistics [G][2][Np] are returned, taken in the launches' epilogues or,
+    for the kernels without one (ops.no_stats_epilogue) and for a custom_forward, by one ops.col_stats pass over the output;
+    the caller then passes no `epilogue` (scale / shift / residual / act: the raw output is wanted).
+    w2v: tape path only - TLS.w2v_wanted around the launches"""
+    Np = ceil4(spec.N)
+    wps = [lay.pack(weight) for lay in spec.layouts]
+    custom = spec.custom_forward
+    stats, thin = None, False
+    if want_stats:
+        thin = custom is not None or ops.no_stats_epilogue(spec.mode, spec.C, Np, spec.T, spec.launches)
+        if not thin:
+            gs = [ops.stats_rows(spec.mode, spec.C, Np, g, m) for g, m in spec.launches]
+            stats = torch.empty((sum(gs), 2, Np), dtype=torch.float32, device=x.device)
+    if custom is not None:
+        custom(x, weight, out)
+    if w2v is not None:
+        ops.TLS.w2v_wanted = w2v
+    g0 = 0
+    for li, (geom, m) in enumerate(spec.launches if custom is None else ()):
+        T = ops.taps_of(spec.T, geom)
+        st = None
+        if stats is not None:
+            st = stats[g0:g0 + gs[li]]
+            g0 += gs[li]
+        ops.gather_gemm(x, lda, spec.C, T, wps[li], Np, m, out, ldo, mode=spec.mode, geom=geom, table=spec.table, bias=bias, stats=st,
+                        a_off=a_off, out_off=out_off, flops=2.0 * m * spec.N * T * spec.c_real, lazy=lazy, pool=pool, **epilogue)
+    if w2v is not None:
+        ops.TLS.w2v_wanted = False
+    if thin:
+        stats, _ = ops.col_stats(out, spec.M, Np, ldo, x_off=out_off)
+    return stats
+
+
+def bn_batch_stats(bn, stats, Np, count, save=False):
+    """the batch-statistics stage of both paths: train-mode BatchNorm from the column statistics of the raw output
+    -> (scale, shift, mean, invstd), the last two None without `save`.  Ticks num_batches_tracked and updates the running
+    statistics in place - through padded temporaries when the channel count was padded to Np (tiny layers)"""
+    N = bn.num_features
+    ops.bn_tick(bn)          # num_batches_tracked += 1, batched per forward / per step
+    momentum = bn.momentum if bn.momentum is not None else 0.1
+    rm, rv = ops.pad_vec(bn.running_mean, Np), ops.pad_vec(bn.running_var, Np, 1.0)
+    res = ops.bn_finalize(stats, stats.shape[0], Np, count, ops.pad_vec(bn.weight, Np), ops.pad_vec(bn.bias, Np), rm, rv, momentum,
+                          bn.eps, save=save)
+    if Np != N:
+        bn.running_mean.copy_(rm[:N])
+        bn.running_var.copy_(rv[:N])
+    return res
 
 
 def materialize(x, lazy):
@@ -161,51 +221,18 @@ class GemmLayerFn(torch.autograd.Function):
         res = None if residual is None else as_rows(residual)
         mean = invstd = raw = None
         need_stats = bn is not None and spec.train
-        stats = None
-        thin = spec.custom_forward is not None or ops.no_stats_epilogue(spec.mode, spec.C, Np, spec.T, spec.launches)
-        if need_stats and not thin:
-            gs = [ops.stats_rows(spec.mode, spec.C, Np, g, m) for (g, m) in spec.launches]
-            stats = torch.empty((sum(gs), 2, Np), dtype=torch.float32, device=dev)
-        fused_plain = bn is None            # bias (+residual) (+act) straight in the epilogue
-        g0 = 0
-        if spec.custom_forward is not None:
-            assert bn is not None and bias is None
-            spec.custom_forward(x, weight, out)
-        ops.TLS.w2v_wanted = bool(ctx.needs_input_grad[1])
-        for li, (geom, m) in enumerate(spec.launches if spec.custom_forward is None else []):
-            wp = spec.pack_fwd(weight, li)
-            T = spec.T if geom is None else len(geom[7])
-            fl = 2.0 * m * N * T * spec.c_real
-            if fused_plain:
-                ops.gather_gemm(x, ld_of(x), spec.C, T, wp, Np, m, out, Np, mode=spec.mode, geom=geom,
-                                table=spec.table, bias=b, residual=res, ldr=0 if res is None else ld_of(res),
-                                act=spec.act, slope=spec.slope, flops=fl, lazy=lazy)
-            else:
-                st = None
-                if need_stats and not thin:
-                    st = stats[g0:g0 + gs[li]]
-                    g0 += gs[li]
-                ops.gather_gemm(x, ld_of(x), spec.C, T, wp, Np, m, out, Np, mode=spec.mode, geom=geom,
-                                table=spec.table, bias=b, act=ACT_NONE, stats=st, flops=fl, lazy=lazy)
-        ops.TLS.w2v_wanted = False
+        assert spec.custom_forward is None or (bn is not None and bias is None)
+        w2v = bool(ctx.needs_input_grad[1])
+        if bn is None:                      # bias (+residual) (+act) straight in the epilogue
+            run_launches(spec, x, ld_of(x), weight, out, Np, b, False, lazy=lazy, w2v=w2v, residual=res,
+                         ldr=0 if res is None else ld_of(res), act=spec.act, slope=spec.slope)
+        else:
+            stats = run_launches(spec, x, ld_of(x), weight, out, Np, b, need_stats, lazy=lazy, w2v=w2v)
         y = out
         if bn is not None:
             raw = out
-            if need_stats and thin:
-                stats, _ = ops.col_stats(out, M, Np, Np)
             if need_stats:
-                ops.bn_tick(bn)          # num_batches_tracked += 1, batched per forward / per step
-                momentum = bn.momentum if bn.momentum is not None else 0.1
-                g_, b_ = ops.pad_vec(gamma.detach(), Np), ops.pad_vec(beta.detach(), Np)
-                if Np == N:
-                    rm, rv = bn.running_mean, bn.running_var
-                else:
-                    rm, rv = ops.pad_vec(bn.running_mean, Np).clone(), ops.pad_vec(bn.running_var, Np, 1.0).clone()
-                scale, shift, mean, invstd = ops.bn_finalize(stats, stats.shape[0], Np, float(M), g_, b_, rm, rv,
-                                                             momentum, bn.eps, save=True)
-                if Np != N:
-                    bn.running_mean.copy_(rm[:N])
-                    bn.running_var.copy_(rv[:N])
+                scale, shift, mean, invstd = bn_batch_stats(bn, stats, Np, float(M), save=True)
             else:
                 with torch.no_grad():
                     invstd = ops.pad_vec(torch.rsqrt(bn.running_var + bn.eps), Np)
@@ -295,7 +322,7 @@ class GemmLayerFn(torch.autograd.Function):
         if TRACE is not None:
             g0, m0 = spec.launches[0] if spec.launches else (None, M)
             TRACE.append(dict(M=M, N=N, C=spec.C, T=spec.T, mode=spec.mode, bn=has_bn, res=has_res, pool=spec.pool, act=spec.act,
-                              nl=len(spec.launches), route=ops.gemm_route(spec.mode, spec.C, Np, spec.T if g0 is None else len(g0[7]), g0, m0),
+                              nl=len(spec.launches), route=ops.gemm_route(spec.mode, spec.C, Np, ops.taps_of(spec.T, g0), g0, m0),
                               x_from=getattr(x, '_efgh_src', None), dx=bool(ctx.needs_input_grad[0]),
                               in_elems=int(x.numel()), custom=spec.custom_forward is not None))
         if spec.pool and not fused_pool:    # pooled gradient -> full resolution (window recomputed from raw*scale+shift)
@@ -391,7 +418,7 @@ class GemmLayerFn(torch.autograd.Function):
             kw = {}
             if dskip is not None:
                 kw['add'] = as_rows(dskip)
-            if ctx.xsrc is not None and getattr(spec.dgrad, 'takes_bnsrc', False):
+            if ctx.xsrc is not None and spec.takes_bnsrc:
                 kw['bnsrc'] = ctx.xsrc
             if pre_v is not None:
                 kw['pre_v'] = pre_v
@@ -409,15 +436,15 @@ class GemmLayerFn(torch.autograd.Function):
 
             def run_wgrad():
                 x = xw
-                for li, (geom, m) in enumerate(spec.launches):
-                    T = spec.T if geom is None else len(geom[7])
+                for (geom, m), lay in zip(spec.launches, spec.layouts):
+                    T = ops.taps_of(spec.T, geom)
                     dWp = torch.empty((Np, T, spec.C), dtype=torch.float32, device=dev)
-                    ua = getattr(spec.wgrad_unpack, 'args', None)
+                    ua = lay.fold_args()            # (ops.gather_wgrad(unpack=...): fold + unpack in one launch)
                     done = ops.gather_wgrad(x, ld_of(x), spec.C, T, Np, m, draw, Np, dWp, mode=spec.mode, geom=geom,
-                                            table=spec.table, unpack=None if ua is None else (dW,) + tuple(ua(li)),
+                                            table=spec.table, unpack=None if ua is None else (dW,) + ua,
                                             lazy=lazy_w, pre_gy=pre_gy)
                     if not done:             # (a single row chunk, or a path with a transform behind its fold)
-                        spec.wgrad_unpack(dWp, li, dW)
+                        lay.unpack(dWp, dW)
             if side is None:
                 run_wgrad()
             else:

@@ -26,7 +26,7 @@ class Ctx:
 def _bn_eval_affine(bn, Np):
     """eval-mode BatchNorm as y = x*scale + shift, cached on the buffers' versions.  Train-mode forwards update
     running_mean / running_var through raw pointers (efgh_bn_finalize), which does not bump their version counters;
-    `num_batches_tracked += 1` (in _bn_train, the only writer) does, so it is part of the key."""
+    `num_batches_tracked += 1` (in FN.bn_batch_stats, the only writer) does, so it is part of the key."""
     key = ('bn_eval', Np)
     vers = ops._ver(bn.weight, bn.bias, bn.running_mean, bn.running_var) + \
         ((bn.num_batches_tracked._version,) if bn.num_batches_tracked is not None else ())
@@ -46,26 +46,6 @@ def _bias_vec(bias, Np):
     if bias.numel() == Np:
         return bias.detach()
     return ops._cached(bias, ('bias', Np), ops._ver(bias), lambda: ops.pad_vec(bias, Np))
-
-
-def _bn_train(ctx, bn, stats, G, Np, count):
-    """finalize batch statistics -> (scale, shift); updates running stats in place."""
-    N = bn.num_features
-    ops.bn_tick(bn)
-    momentum = bn.momentum if bn.momentum is not None else 0.1
-    if Np == N:
-        scale, shift, _, _ = ops.bn_finalize(stats, G, N, count, bn.weight.detach(), bn.bias.detach(),
-                                             bn.running_mean, bn.running_var, momentum, bn.eps)
-        return scale, shift
-    # padded channel count (tiny layers): run on padded temporaries, copy the real part back
-    g, b = ops.pad_vec(bn.weight, Np), ops.pad_vec(bn.bias, Np)
-    rm, rv = ops.pad_vec(bn.running_mean, Np), ops.pad_vec(bn.running_var, Np, 1.0)
-    if rm is bn.running_mean:
-        rm, rv = rm.clone(), rv.clone()
-    scale, shift, _, _ = ops.bn_finalize(stats, G, Np, count, g, b, rm, rv, momentum, bn.eps)
-    bn.running_mean.copy_(rm[:N])
-    bn.running_var.copy_(rv[:N])
-    return scale, shift
 
 
 def _epilogue_plan(ctx, bias, bn, Np):
@@ -91,43 +71,42 @@ def _alloc_out(x, shape_rows, N, out):
     return t, t.shape[-1], coff
 
 
-def _run(ctx, x, lda, C, T, Wp, N, M, mode, geoms, out_t, ldo, coff, bias, bn, act, slope, residual=None,
-         res_ld=0, res_off=0, table=None, a_off=0, count=None, c_real=None, pool=False):
-    """One logical layer = one or more GEMM launches (`geoms`: list of (geom, Wp, M_launch)), then the
-    BatchNorm finalize/apply pass when batch statistics are needed."""
-    Np = N if N % 4 == 0 else ceil4(N)
-    b, sc, sh, fused = _epilogue_plan(ctx, bias, bn, Np)
-    cr = c_real if c_real is not None else C
-
-    def fl(geom, m):       # algorithmic FLOPs of one launch: real (unpadded) channel counts
-        return 2.0 * m * N * (T if geom is None else len(geom[7])) * cr
+def _run(ctx, spec, x, lda, weight, bias, out_t, ldo, coff, residual=None, res_ld=0, res_off=0, a_off=0, count=None, pool=False):
+    """no-tape path of one layer (FN.LayerSpec): its GEMM launches with everything fused into their epilogues - or, when train-mode
+    BatchNorm needs batch statistics, raw output + statistics, then the normalise pass in place."""
+    Np = ceil4(spec.N)
+    b, sc, sh, fused = _epilogue_plan(ctx, bias, spec.bn, Np)
     if fused:
-        for geom, wp, m in geoms:
-            ops.gather_gemm(x, lda, C, T if geom is None else len(geom[7]), wp, Np, m, out_t, ldo, mode=mode,
-                            geom=geom, table=table, bias=b, scale=sc, shift=sh, residual=residual, ldr=res_ld,
-                            act=act, slope=slope, a_off=a_off, out_off=coff, res_off=res_off, flops=fl(geom, m), pool=pool)
+        FN.run_launches(spec, x, lda, weight, out_t, ldo, b, False, a_off, coff, pool=pool, scale=sc, shift=sh, residual=residual,
+                        ldr=res_ld, res_off=res_off, act=spec.act, slope=spec.slope)
         return
     assert not pool
-    # train-mode BatchNorm: raw conv output + per-block column statistics, then normalise in place
-    if ops.no_stats_epilogue(mode, C, Np, T, [(geom, m) for geom, _, m in geoms]):      # one extra streaming pass over the (small) output
-        for geom, wp, m in geoms:
-            ops.gather_gemm(x, lda, C, len(geom[7]), wp, Np, m, out_t, ldo, mode=mode, geom=geom, bias=b,
-                            act=ACT_NONE, a_off=a_off, out_off=coff, flops=fl(geom, m))
-        stats, _ = ops.col_stats(out_t, M, Np, ldo, x_off=coff)
-        gs = [stats.shape[0]]
-    else:
-        gs = [ops.stats_rows(mode, C, Np, geom, m) for geom, _, m in geoms]
-        stats = torch.empty((sum(gs), 2, Np), dtype=torch.float32, device=x.device)
-        g0 = 0
-        for (geom, wp, m), g in zip(geoms, gs):
-            ops.gather_gemm(x, lda, C, T if geom is None else len(geom[7]), wp, Np, m, out_t, ldo, mode=mode,
-                            geom=geom, table=table, bias=b, act=ACT_NONE, stats=stats[g0:g0 + g], a_off=a_off,
-                            out_off=coff, flops=fl(geom, m))
-            g0 += g
-    cnt = count if count is not None else M
-    scale, shift = _bn_train(ctx, bn, stats, sum(gs), Np, float(cnt))
-    ops.scale_shift_act(out_t, ldo, scale, shift, out_t, ldo, M, Np, act, slope, res=residual, ldr=res_ld,
+    stats = FN.run_launches(spec, x, lda, weight, out_t, ldo, b, True, a_off, coff)
+    scale, shift, _, _ = FN.bn_batch_stats(spec.bn, stats, Np, float(count if count is not None else spec.M))
+    ops.scale_shift_act(out_t, ldo, scale, shift, out_t, ldo, spec.M, Np, spec.act, spec.slope, res=residual, ldr=res_ld,
                         x_off=coff, y_off=coff, res_off=res_off)
+
+
+def _apply(spec, x, weight, bias, residual=None, passthrough=False, out=None):
+    """tape path of one layer: a GemmLayerFn node.  passthrough: the caller wants (y, alias of x); when the Function does not hand
+    one out (spec.passthrough is off) x itself serves"""
+    g_, b_ = (None, None) if spec.bn is None else (spec.bn.weight, spec.bn.bias)
+    y = FN.GemmLayerFn.apply(x, weight, bias, g_, b_, residual, spec, out)
+    return (y, x) if passthrough and not spec.passthrough else y
+
+
+def _parity_classes(kh, kw, ph, pw, Ho, Wo):
+    """a stride-2 layer seen from its fine side [Ho][Wo] (the output of a transposed convolution, the input of a convolution whose
+    data gradient is wanted): fine pixel (2i + cy, 2j + cx) meets the kernel taps (a, b) with cy + ph - a and cx + pw - b even, at
+    coarse offsets dh = (cy + ph - a) / 2, dw = (cx + pw - b) / 2.  Yields (cy, cx, tapidx, Hv, Wv, dh, dw) for each of the four
+    parity classes that has taps and pixels: one stride-1 launch over [Hv][Wv] each"""
+    for cy in range(2):
+        for cx in range(2):
+            taps = [(a, b) for a in range(kh) if (cy + ph - a) % 2 == 0 for b in range(kw) if (cx + pw - b) % 2 == 0]
+            Hv, Wv = (Ho - cy + 1) // 2, (Wo - cx + 1) // 2
+            if taps and Hv > 0 and Wv > 0:
+                yield (cy, cx, [a * kw + b for a, b in taps], Hv, Wv, [(cy + ph - a) // 2 for a, _ in taps],
+                       [(cx + pw - b) // 2 for _, b in taps])
 
 
 def _same3x3_geom(B, H, W):
@@ -158,29 +137,83 @@ def conv2d(ctx, x, conv, bn=None, act=ACT_NONE, slope=0.0, residual=None, out=No
     Ho, Wo = (H + 2 * ph - kh) // sh + 1, (W + 2 * pw - kw) // sw + 1
     T = kh * kw
     Np = ceil4(O)
-    Wp = ops.pack_weight(conv.weight, O, T, Cw, Cw * T, T, 1, list(range(T)), Np=Np, Cp=Cp, key=('conv', Np, Cp))
     dh = [i // kw - ph for i in range(T)]
     dw = [i % kw - pw for i in range(T)]
     geom = (B, H, W, Ho, Wo, sh, sw, dh, dw, Ho, Wo, 1, 1, 0, 0)
     M = B * Ho * Wo
+    lay = ops.WeightLayout(O, T, Cw, Cw * T, T, 1, list(range(T)), Np, Cp, ('conv', Np, Cp))
+    spec = FN.LayerSpec(O, Cp, T, 1, [(geom, M)], [lay], M, (B, Ho, Wo), bn=bn, train=ctx.train, act=act, slope=slope, c_real=Cw)
     if ctx.grad:
         assert in_ch is None or getattr(x, '_efgh_lazy', None) is None       # (a slice view would lose the pending activation)
         xs = x if in_ch is None else x[..., a_off:a_off + Cx]
-        return _conv2d_grad(ctx, xs, conv, bn, act, slope, residual, geom, (B, H, W, Ho, Wo), Cp, passthrough=skip_out, pool=pool,
-                            out=out, defer_act=defer_act)
+        # data AND weight gradient on the 2-D Winograd path: the BatchNorm backward's apply pass rides in their transforms
+        fus = bool((kh, kw, sh, sw, ph, pw) == (3, 3, 1, 1, 1, 1) and bn is not None and ctx.train
+                   and ops.lazy_capable(1, Np, Cp, _same3x3_geom(B, H, W)) and ops.wgrad_lazy_capable(1, Cp, Np, geom))
+        spec.for_tape(_conv2d_dgrad(conv, (B, H, W, Ho, Wo), Np, Cp), takes_bnsrc=True,
+                      passthrough=skip_out and xs.requires_grad and xs.shape[-1] == Cp, pool=pool, defer_act=defer_act, bwd_fusable=fus)
+        return _apply(spec, xs, conv.weight, conv.bias, residual, skip_out, out)
     assert not defer_act
     if pool:
         # inference: the following MaxPool2d(2,2) rides in the layer's output transform (run_vgg asks pool_fusable first)
         assert out is None and residual is None and not ctx.train
         out_t, ldo, coff = _alloc_out(x, (B, Ho if pool == 'h' else Ho // 2, Wo // 2), O, None)
-        _run(ctx, x, ldx, Cp, T, Wp, O, M, 1, [(geom, Wp, M)], out_t, ldo, coff, conv.bias, bn, act, slope, a_off=a_off, c_real=Cw,
-             pool=pool)
+        _run(ctx, spec, x, ldx, conv.weight, conv.bias, out_t, ldo, coff, a_off=a_off, pool=pool)
         return ops.maxpool_v2(out_t) if pool == 'h' else out_t
     out_t, ldo, coff = _alloc_out(x, (B, Ho, Wo), O, out)
     res_ld = residual.shape[-1] if residual is not None else 0
-    _run(ctx, x, ldx, Cp, T, Wp, O, M, 1, [(geom, Wp, M)], out_t, ldo, coff, conv.bias, bn, act, slope,
-         residual=residual, res_ld=res_ld, a_off=a_off, c_real=Cw)
+    _run(ctx, spec, x, ldx, conv.weight, conv.bias, out_t, ldo, coff, residual=residual, res_ld=res_ld, a_off=a_off)
     return out_t
+
+
+def _conv2d_dgrad(conv, dims, Np, Cp):
+    B, H, W, Ho, Wo = dims
+    Cw, O = conv.in_channels, conv.out_channels
+    kh, kw = conv.kernel_size
+    sh, sw = conv.stride
+    ph, pw = conv.padding
+    T = kh * kw
+
+    def dgrad(spec, w, draw, xin, add=None, bnsrc=None, pre_v=None):
+        """pre_v: B^T draw B, already made by ops.wino2d_bwd_transforms (draw itself is None then: it was never stored).
+        add: a gradient that reached x through ANOTHER consumer (handed over on this layer's passthrough alias); it is folded
+        into the result in the kernels' epilogues instead of by a separate elementwise pass of autograd.
+        bnsrc: the BatchNorm layer that produced x (fn.BnSrc): its backward column sums are taken in this launch's epilogue when
+        the kernel supports it, and the returned gradient is tagged with them"""
+        dev = (draw if draw is not None else pre_v).device
+        ldr = 0 if add is None else FN.ld_of(add)
+        assert pre_v is None or (sh == 1 and sw == 1)
+        if sh == 1 and sw == 1:
+            # taps in ascending (dh, dw) order = the canonical 3x3 order the Winograd kernel recognises
+            order = sorted(range(T), key=lambda i: (ph - i // kw, pw - i % kw))
+            dhs = [ph - i // kw for i in order]
+            dws = [pw - i % kw for i in order]
+            Wd = ops.WeightLayout(Cw, T, O, T, Cw * T, 1, order, Cp, Np, ('conv_d', Np, Cp)).pack(w)
+            dx = torch.empty((B, H, W, Cp), dtype=torch.float32, device=dev)
+            g = (B, Ho, Wo, H, W, 1, 1, dhs, dws, H, W, 1, 1, 0, 0)
+            st = ops.gather_gemm(draw, Np, Np, T, Wd, Cp, B * H * W, dx, Cp, mode=1, geom=g, residual=add, ldr=ldr,
+                                 flops=2.0 * B * H * W * Cw * T * O, bn_bwd=bnsrc, pre_v=pre_v)
+            if st is not None:
+                dx._efgh_bnsums = (st, bnsrc, dx._version)      # (an in-place accumulation by autograd moves the version on)
+            return dx
+        assert sh == 2 and sw == 2
+        classes = list(_parity_classes(kh, kw, ph, pw, H, W))
+        if add is not None and len(classes) < 4:
+            # e.g. the 1x1 / stride-2 downsample of a ResNet block: only one of the four input-parity classes receives anything.
+            # The other gradient IS the result there, so the launches accumulate into it in place (every element is read and
+            # written by one thread) - no zero fill, no addition pass
+            dx, ldx_ = add, ldr
+            assert add.shape[-1] == Cp
+        elif len(classes) == 4:
+            dx, ldx_ = torch.empty((B, H, W, Cp), dtype=torch.float32, device=dev), Cp
+        else:
+            dx, ldx_ = torch.zeros((B, H, W, Cp), dtype=torch.float32, device=dev), Cp
+        for cy, cx, tapidx, Hv, Wv, dhs, dws in classes:
+            Wd = ops.WeightLayout(Cw, len(tapidx), O, T, Cw * T, 1, tapidx, Cp, Np, ('conv_d2', cy, cx, Np, Cp)).pack(w)
+            g = (B, Ho, Wo, Hv, Wv, 1, 1, dhs, dws, H, W, 2, 2, cy, cx)
+            ops.gather_gemm(draw, Np, Np, len(tapidx), Wd, Cp, B * Hv * Wv, dx, ldx_, mode=1, geom=g, residual=add, ldr=ldr,
+                            flops=2.0 * B * Hv * Wv * Cw * len(tapidx) * O)
+        return dx
+    return dgrad
 
 
 def _convt_wcol(convt):
@@ -218,43 +251,74 @@ def conv_transpose2d(ctx, x, convt, bn=None, act=ACT_NONE, slope=0.0, out=None, 
     oph, opw = convt.output_padding
     Ho, Wo = (H - 1) * 2 - 2 * ph + 3 + oph, (W - 1) * 2 - 2 * pw + 3 + opw
     Np = ceil4(O)
-    if O <= 3 and ph == pw and convt.bias is None and bn is not None and out is None and not ctx.grad:
+    small = O <= 3 and ph == pw and convt.bias is None and bn is not None      # the GEMM + col2im form
+    if small and out is None and not ctx.grad:
         out_t = torch.empty((B, Ho, Wo, 4), dtype=torch.float32, device=x.device)
         if not ctx.train:
             sc, sh = _bn_eval_affine(bn, 4)
             _convt_small_forward(x, convt, out_t, sc, sh, act, slope)
         else:
             _convt_small_forward(x, convt, out_t)
-            stats, G = ops.col_stats(out_t, B * Ho * Wo, 4, 4)
-            scale, shift = _bn_train(ctx, bn, stats, G, 4, float(B * Ho * Wo))
+            stats, _ = ops.col_stats(out_t, B * Ho * Wo, 4, 4)
+            scale, shift, _, _ = FN.bn_batch_stats(bn, stats, 4, float(B * Ho * Wo))
             ops.scale_shift_act(out_t, 4, scale, shift, out_t, 4, B * Ho * Wo, 4, act, slope)
         return out_t
-    out_t, ldo, coff = (None, 0, 0) if ctx.grad else _alloc_out(x, (B, Ho, Wo), O, out)
-    geoms = []
-    for cy in range(2):
-        for cx in range(2):
-            khs = [k for k in range(3) if (cy + ph - k) % 2 == 0]
-            kws = [k for k in range(3) if (cx + pw - k) % 2 == 0]
-            taps = [(a, b) for a in khs for b in kws]
-            Hv, Wv = (Ho - cy + 1) // 2, (Wo - cx + 1) // 2
-            if Hv <= 0 or Wv <= 0:
-                continue
-            dh = [(cy + ph - a) // 2 for a, _ in taps]
-            dw = [(cx + pw - b) // 2 for _, b in taps]
-            tapidx = [a * 3 + b for a, b in taps]
-            # ConvTranspose2d weight is (in, out, kh, kw)
-            Wp = ops.pack_weight(convt.weight, O, len(taps), Cw, 9, O * 9, 1, tapidx, Np=Np,
-                                 key=('convt', cy, cx, ph, pw, Np))
-            geom = (B, H, W, Hv, Wv, 1, 1, dh, dw, Ho, Wo, 2, 2, cy, cx)
-            geoms.append((geom, Wp, B * Hv * Wv, tapidx, (cy, cx)))
+    launches, layouts = [], []
+    for cy, cx, tapidx, Hv, Wv, dh, dw in _parity_classes(3, 3, ph, pw, Ho, Wo):
+        launches.append(((B, H, W, Hv, Wv, 1, 1, dh, dw, Ho, Wo, 2, 2, cy, cx), B * Hv * Wv))
+        # ConvTranspose2d weight is (in, out, kh, kw)
+        layouts.append(ops.WeightLayout(O, len(tapidx), Cw, 9, O * 9, 1, tapidx, Np, key=('convt', cy, cx, ph, pw, Np)))
+    spec = FN.LayerSpec(O, Cw, 0, 1, launches, layouts, B * Ho * Wo, (B, Ho, Wo), bn=bn, train=ctx.train, act=act, slope=slope)
     if ctx.grad:
         assert out is None
+        cfwd, cwgrad = _convt_small_grad(convt, (B, H, W, Ho, Wo)) if small else (None, None)
         # defer_for: the Conv2d that is the ONLY consumer of this layer's activation (net_utils.py:66-98)
-        return _convt_grad(ctx, x, convt, bn, act, slope, geoms, (B, H, W, Ho, Wo), passthrough=skip_out,
-                           defer_act=defer_for is not None and lazy_consumer_ok(ctx, defer_for, B, Ho, Wo))
-    _run(ctx, x, ldx, Cw, 0, None, O, B * Ho * Wo, 1, [g[:3] for g in geoms], out_t, ldo, coff, convt.bias, bn,
-         act, slope)
+        spec.for_tape(_convt_dgrad(convt, (B, H, W, Ho, Wo)), custom_forward=cfwd, custom_wgrad=cwgrad,
+                      passthrough=skip_out and x.requires_grad,
+                      defer_act=not small and defer_for is not None and lazy_consumer_ok(ctx, defer_for, B, Ho, Wo))
+        return _apply(spec, x, convt.weight, convt.bias, None, skip_out)
+    out_t, ldo, coff = _alloc_out(x, (B, Ho, Wo), O, out)
+    _run(ctx, spec, x, ldx, convt.weight, convt.bias, out_t, ldo, coff)
     return out_t
+
+
+def _convt_dgrad(convt, dims):
+    B, H, W, Ho, Wo = dims
+    Cw, O = convt.in_channels, convt.out_channels
+    ph, pw = convt.padding
+    Np = ceil4(O)
+
+    def dgrad(spec, w, draw, xin, add=None):
+        # dX[ci][ih][iw] = sum_{co,kh,kw} dY[co][2ih-ph+kh][2iw-pw+kw] * W[ci][co][kh][kw]  (stride-2 conv)
+        dhs = [k // 3 - ph for k in range(9)]
+        dws = [k % 3 - pw for k in range(9)]
+        Wd = ops.WeightLayout(Cw, 9, O, O * 9, 9, 1, list(range(9)), Cp=Np, key=('convt_d', Np)).pack(w)
+        dx = torch.empty((B, H, W, Cw), dtype=torch.float32, device=draw.device)
+        g = (B, Ho, Wo, H, W, 2, 2, dhs, dws, H, W, 1, 1, 0, 0)
+        ops.gather_gemm(draw, Np, Np, 9, Wd, Cw, B * H * W, dx, Cw, mode=1, geom=g,
+                        residual=add, ldr=0 if add is None else FN.ld_of(add),
+                        flops=2.0 * B * H * W * Cw * 9 * O / 4 * 4)
+        return dx
+    return dgrad
+
+
+def _convt_small_grad(convt, dims):
+    """(custom_forward, custom_wgrad) of the GEMM + col2im form on the tape path"""
+    B, H, W, Ho, Wo = dims
+    Cw, O = convt.in_channels, convt.out_channels
+
+    def custom_fwd(xin, w, out_raw):
+        _convt_small_forward(xin, convt, out_raw)
+
+    def custom_wgrad(xin, w, draw):
+        # dWcol[(tap,o)][c] = sum_pix im2col(draw)[pix][(tap,o)] * x[pix][c]
+        n9 = ceil4(9 * O)
+        ycol = torch.empty((B * H * W, n9), dtype=torch.float32, device=draw.device)
+        ops.convt_im2col(draw, B, H, W, Ho, Wo, O, convt.padding[0], ycol)
+        dwcol = torch.empty((n9, 1, Cw), dtype=torch.float32, device=draw.device)
+        ops.gather_wgrad(xin, FN.ld_of(xin), Cw, 1, n9, B * H * W, ycol, n9, dwcol, mode=0)
+        return dwcol[:9 * O, 0].reshape(9, O, Cw).permute(2, 1, 0).reshape(Cw, O, 3, 3).contiguous()
+    return custom_fwd, custom_wgrad
 
 
 def linear_rows(ctx, x, M, C, weight, bias, bn=None, act=ACT_NONE, slope=0.0, out=None, lda=None, a_off=0,
@@ -264,19 +328,25 @@ def linear_rows(ctx, x, M, C, weight, bias, bn=None, act=ACT_NONE, slope=0.0, ou
     Cp = ceil4(C)
     lda = lda if lda is not None else x.shape[-1]
     Np = ceil4(O)
+    lay = ops.WeightLayout(O, 1, C, C, 1, 1, [0], Np, Cp, ('lin', Np, Cp))
+    spec = FN.LayerSpec(O, Cp, 1, 0, [(None, M)], [lay], M, (M,), bn=bn, train=ctx.train, act=act, slope=slope, c_real=C)
     if ctx.grad:
         assert out is None
         xs = x if (a_off == 0 and x.shape[-1] == Cp) else x.view(-1, x.shape[-1])[:, a_off:a_off + Cp]
-        return _linear_grad(ctx, xs.reshape(M, -1) if xs.dim() != 2 else xs, M, C, weight, bias, bn, act, slope)
-    Wp = ops.pack_weight(weight, O, 1, C, C, 1, 1, [0], Np=Np, Cp=Cp, key=('lin', Np, Cp))
+
+        def dgrad(spec, w, draw, xin):
+            Wd = ops.WeightLayout(C, 1, O, 1, C, 1, [0], Cp, Np, ('lin_d', Np, Cp)).pack(w)
+            dx = torch.empty((M, Cp), dtype=torch.float32, device=draw.device)
+            ops.gather_gemm(draw, Np, Np, 1, Wd, Cp, M, dx, Cp, mode=0, flops=2.0 * M * C * O)
+            return dx
+        return _apply(spec.for_tape(dgrad), xs.reshape(M, -1) if xs.dim() != 2 else xs, weight, bias)
     if out is None:
         out_t = torch.empty((M, Np), dtype=torch.float32, device=x.device)
         ldo, coff = Np, 0
     else:
         out_t, coff = out
         ldo = out_t.shape[-1]
-    _run(ctx, x, lda, Cp, 1, Wp, O, M, 0, [(None, Wp, M)], out_t, ldo, coff, bias, bn, act, slope, a_off=a_off,
-         count=count, c_real=C)
+    _run(ctx, spec, x, lda, weight, bias, out_t, ldo, coff, a_off=a_off, count=count)
     return out_t
 
 
@@ -284,32 +354,46 @@ def blur_conv(ctx, splat, H, C, table, conv0, conv1, out=None, last_act=ACT_NONE
     """BCL blur: gather 15 neighbour rows + Conv2d(C,C0,(15,1)) + ReLU + Conv2d(C0,C1,1)
     (nets/bilateralNN.py:240-246).  splat [H][C]; `table` = the lattice level (efgh_amd.lattice.LatticeLevel: its neighbour
     table also serves the adjoint of the gather) or a bare [H][16] neighbour table -> [H][ld]."""
-    C0, C1 = conv0.out_channels, conv1.out_channels
+    C0 = conv0.out_channels
     lv = table if hasattr(table, 'nbr') else None
     if lv is not None:
         table = lv.nbr
     if lv is not None and lv.radius != 1:
-        # radius 2 / 3 (scale_map's second column): F = 65 / 175 taps through the level's [H][ld] table
+        # radius 2 / 3 (scale_map's second column): F = 65 / 175 taps through the level's [H][ld] table, on the mode-MODE_BLUR_R
+        # launches (forward, data gradient through the same table with mirrored taps, weight gradient [C0][F][C] -> (C0, C, F, 1))
         if conv0.kernel_size != (lv.F, 1):
             raise ops._C.EfghError('BCL blur weight %s does not match the radius-%d lattice level (F = %d taps)'
                                    % (tuple(conv0.weight.shape), lv.radius, lv.F))
-        if ctx.grad:
-            assert out is None
-            mid = _blur_grad_r(ctx, splat, H, C, lv, conv0)
-            return linear_rows(ctx, mid, H, C0, conv1.weight, conv1.bias, act=last_act, slope=last_slope)
-        mid = torch.empty((H, C0), dtype=torch.float32, device=splat.device)
-        ops.blur_r_gemm(splat, C, C, lv.F, ops.blur_r_pack(conv0.weight), C0, H, mid, C0, lv.nbr, bias=conv0.bias.detach(),
-                        act=ACT_RELU, flops=2.0 * H * lv.F * C * C0)
-        return linear_rows(ctx, mid, H, C0, conv1.weight, conv1.bias, out=out, act=last_act, slope=last_slope)
+        spec = FN.LayerSpec(C0, C, lv.F, ops.MODE_BLUR_R, [(None, H)], [ops.BlurRLayout()], H, (H,), act=ACT_RELU, table=table)
+    else:
+        lay = ops.WeightLayout(C0, 15, C, C * 15, 15, 1, list(range(15)), key=('blur0',))
+        spec = FN.LayerSpec(C0, C, 15, 2, [(None, H)], [lay], H, (H,), act=ACT_RELU, table=table)
     if ctx.grad:
         assert out is None
-        mid = _blur_grad(ctx, splat, H, C, table, conv0, lv)
-        return linear_rows(ctx, mid, H, C0, conv1.weight, conv1.bias, act=last_act, slope=last_slope)
-    Wp0 = ops.pack_weight(conv0.weight, C0, 15, C, C * 15, 15, 1, list(range(15)), key=('blur0',))
-    mid = torch.empty((H, C0), dtype=torch.float32, device=splat.device)
-    ops.gather_gemm(splat, C, C, 15, Wp0, C0, H, mid, C0, mode=2, table=table, bias=conv0.bias.detach(),
-                    act=ACT_RELU)
+        mid = _apply(spec.for_tape(_blur_dgrad(lv, table, H, C, C0)), splat, conv0.weight, conv0.bias)
+    else:
+        assert C0 % 4 == 0
+        mid = torch.empty((H, C0), dtype=torch.float32, device=splat.device)
+        _run(ctx, spec, splat, C, conv0.weight, conv0.bias, mid, C0, 0)
     return linear_rows(ctx, mid, H, C0, conv1.weight, conv1.bias, out=out, act=last_act, slope=last_slope)   # (last_relu, bilateralNN.py:121-135)
+
+
+def _blur_dgrad(lv, table, H, C, C0):
+    def dgrad(spec, w, draw, xin):
+        if lv is not None and lv.radius != 1:
+            return ops.blur_r_dgrad(lv, draw, C0, w, C)
+        if lv is not None and ops.BLUR_DGRAD_FUSED and C % 4 == 0 and C0 % 4 == 0:
+            return ops.blur_dgrad(lv, draw, C0, w, C)        # one gather-GEMM through the lattice's symmetric table
+        # tmp[m][t*C+c] = sum_n draw[m][n] * W0[n][c][t], then scattered through the neighbour table
+        Wd = w.detach().squeeze(-1).permute(2, 1, 0).contiguous().view(15 * C, C0)
+        tmp = torch.empty((H, 15 * C), dtype=torch.float32, device=draw.device)
+        ops.gather_gemm(draw, C0, C0, 1, Wd, 15 * C, H, tmp, 15 * C, mode=0, flops=2.0 * H * 15 * C * C0)
+        if lv is not None:              # through the lattice's own (symmetric) table: a gather, no atomics
+            return ops.neighbor_gather_adjoint(lv, tmp, C)
+        dsplat = torch.zeros((H, C), dtype=torch.float32, device=draw.device)
+        ops.table_scatter_add(tmp, table, H, 15, C, dsplat)
+        return dsplat
+    return dgrad
 
 
 def maxpool2(ctx, x):
@@ -364,7 +448,7 @@ def run_conv_bn_relu(ctx, seq, x, out=None, in_ch=None, skip_out=False):
 def run_convt_bn_relu(ctx, seq, x, out=None, skip_out=False):
     """nets/net_utils.py:66-98: ConvT+BN+LeakyReLU(0.2) then Conv3x3+BN+LeakyReLU(0.2).
     skip_out (training path): also returns an alias of x for x's NEXT consumer; the gradient that consumer sends back is added
-    in this layer's dgrad epilogue (see _conv2d_grad.dgrad)."""
+    in this layer's dgrad epilogue (see _conv2d_dgrad)."""
     if skip_out and ctx.grad:
         y, alias = conv_transpose2d(ctx, x, seq[0], seq[1], ACT_LEAKY, 0.2, skip_out=True, defer_for=seq[3])
         return conv2d(ctx, y, seq[3], seq[4], ACT_LEAKY, 0.2, out=out), alias
@@ -585,217 +669,3 @@ def run_resnet_layer(ctx, layer, x, out=None, alias_in=False):
         else:
             x = run_basic_block(ctx, blk, x, out=out if last else None)
     return (x, alias) if alias_in else x
-
-
-# ==============================================================================================
-# training path: the same layers as autograd Functions with hand-written HIP backward (fn.py)
-# ==============================================================================================
-def _bn_args(bn):
-    return (None, None) if bn is None else (bn.weight, bn.bias)
-
-
-def _conv2d_grad(ctx, x, conv, bn, act, slope, residual, geom, dims, Cp, passthrough=False, pool=False, out=None, defer_act=False):
-    B, H, W, Ho, Wo = dims
-    Cw, O = conv.in_channels, conv.out_channels
-    kh, kw = conv.kernel_size
-    sh, sw = conv.stride
-    ph, pw = conv.padding
-    T, Np = kh * kw, ceil4(O)
-
-    def pack_fwd(w, i):
-        return ops.pack_weight(w, O, T, Cw, Cw * T, T, 1, list(range(T)), Np=Np, Cp=Cp, key=('conv', Np, Cp))
-
-    def unpack(dWp, i, dW):
-        ops.unpack_weight(dWp, dW, O, T, Cw, Cp, Cw * T, T, 1, list(range(T)))
-    unpack.args = lambda i: (O, T, Cw, Cp, Cw * T, T, 1, list(range(T)), False)       # (ops.gather_wgrad(unpack=...): fold + unpack in one launch)
-
-    def dgrad(spec, w, draw, xin, add=None, bnsrc=None, pre_v=None):
-        """pre_v: B^T draw B, already made by ops.wino2d_bwd_transforms (draw itself is None then: it was never stored).
-        add: a gradient that reached x through ANOTHER consumer (handed over on this layer's passthrough alias); it is folded
-        into the result in the kernels' epilogues instead of by a separate elementwise pass of autograd.
-        bnsrc: the BatchNorm layer that produced x (fn.BnSrc): its backward column sums are taken in this launch's epilogue when
-        the kernel supports it, and the returned gradient is tagged with them"""
-        dev = (draw if draw is not None else pre_v).device
-        assert pre_v is None or (sh == 1 and sw == 1)
-        if sh == 1 and sw == 1:
-            # taps in ascending (dh, dw) order = the canonical 3x3 order the Winograd kernel recognises
-            order = sorted(range(T), key=lambda i: (ph - i // kw, pw - i % kw))
-            dhs = [ph - i // kw for i in order]
-            dws = [pw - i % kw for i in order]
-            Wd = ops.pack_weight(w, Cw, T, O, T, Cw * T, 1, order, Np=Cp, Cp=Np, key=('conv_d', Np, Cp))
-            dx = torch.empty((B, H, W, Cp), dtype=torch.float32, device=dev)
-            g = (B, Ho, Wo, H, W, 1, 1, dhs, dws, H, W, 1, 1, 0, 0)
-            st = ops.gather_gemm(draw, Np, Np, T, Wd, Cp, B * H * W, dx, Cp, mode=1, geom=g,
-                                 residual=add, ldr=0 if add is None else FN.ld_of(add), flops=2.0 * B * H * W * Cw * T * O,
-                                 bn_bwd=bnsrc, pre_v=pre_v)
-            if st is not None:
-                dx._efgh_bnsums = (st, bnsrc, dx._version)      # (an in-place accumulation by autograd moves the version on)
-            return dx
-        assert sh == 2 and sw == 2
-        classes = []
-        for cy in range(2):
-            for cx in range(2):
-                khs = [k for k in range(kh) if (cy + ph - k) % 2 == 0]
-                kws = [k for k in range(kw) if (cx + pw - k) % 2 == 0]
-                taps = [(a, b) for a in khs for b in kws]
-                Hv, Wv = (H - cy + 1) // 2, (W - cx + 1) // 2
-                classes.append((cy, cx, taps, Hv, Wv))
-        full = all(len(c[2]) > 0 and c[3] > 0 and c[4] > 0 for c in classes)
-        if add is not None and not full:
-            # e.g. the 1x1 / stride-2 downsample of a ResNet block: only one of the four input-parity classes receives anything.
-            # The other gradient IS the result there, so the launches accumulate into it in place (every element is read and
-            # written by one thread) - no zero fill, no addition pass
-            dx, ldx_ = add, FN.ld_of(add)
-            assert add.shape[-1] == Cp
-        elif full:
-            dx, ldx_ = torch.empty((B, H, W, Cp), dtype=torch.float32, device=dev), Cp
-        else:
-            dx, ldx_ = torch.zeros((B, H, W, Cp), dtype=torch.float32, device=dev), Cp
-        for cy, cx, taps, Hv, Wv in classes:
-            if not taps or Hv <= 0 or Wv <= 0:
-                continue
-            dhs = [(cy + ph - a) // 2 for a, _ in taps]
-            dws = [(cx + pw - b) // 2 for _, b in taps]
-            tapidx = [a * kw + b for a, b in taps]
-            Wd = ops.pack_weight(w, Cw, len(taps), O, T, Cw * T, 1, tapidx, Np=Cp, Cp=Np,
-                                 key=('conv_d2', cy, cx, Np, Cp))
-            g = (B, Ho, Wo, Hv, Wv, 1, 1, dhs, dws, H, W, 2, 2, cy, cx)
-            ops.gather_gemm(draw, Np, Np, len(taps), Wd, Cp, B * Hv * Wv, dx, ldx_, mode=1, geom=g,
-                            residual=add, ldr=0 if add is None else FN.ld_of(add),
-                            flops=2.0 * B * Hv * Wv * Cw * len(taps) * O)
-        return dx
-
-    dgrad.takes_bnsrc = True
-    # data AND weight gradient on the 2-D Winograd path: the BatchNorm backward's apply pass rides in their transforms
-    fus = bool((kh, kw, sh, sw, ph, pw) == (3, 3, 1, 1, 1, 1) and bn is not None and ctx.train
-               and ops.lazy_capable(1, Np, Cp, _same3x3_geom(B, H, W)) and ops.wgrad_lazy_capable(1, Cp, Np, geom))
-    spec = FN.LayerSpec(O, Cp, T, 1, [(geom, B * Ho * Wo)], B * Ho * Wo, (B, Ho, Wo), pack_fwd, dgrad, unpack,
-                        bn=bn, train=ctx.train, act=act, slope=slope, c_real=Cw,
-                        passthrough=passthrough and x.requires_grad and x.shape[-1] == Cp, pool=pool,
-                        defer_act=defer_act, bwd_fusable=fus)
-    g_, b_ = _bn_args(bn)
-    out = FN.GemmLayerFn.apply(x, conv.weight, conv.bias, g_, b_, residual, spec, out)
-    if passthrough and not spec.passthrough:
-        return out, x
-    return out
-
-
-def _convt_grad(ctx, x, convt, bn, act, slope, geoms, dims, passthrough=False, defer_act=False):
-    B, H, W, Ho, Wo = dims
-    Cw, O = convt.in_channels, convt.out_channels
-    ph, pw = convt.padding
-    Np = ceil4(O)
-
-    def pack_fwd(w, i):
-        return geoms[i][1]
-
-    def unpack(dWp, i, dW):
-        tapidx = geoms[i][3]
-        ops.unpack_weight(dWp, dW, O, len(tapidx), Cw, Cw, 9, O * 9, 1, tapidx)
-    unpack.args = lambda i: (O, len(geoms[i][3]), Cw, Cw, 9, O * 9, 1, geoms[i][3], False)
-
-    def dgrad(spec, w, draw, xin, add=None):
-        # dX[ci][ih][iw] = sum_{co,kh,kw} dY[co][2ih-ph+kh][2iw-pw+kw] * W[ci][co][kh][kw]  (stride-2 conv)
-        dhs = [k // 3 - ph for k in range(9)]
-        dws = [k % 3 - pw for k in range(9)]
-        Wd = ops.pack_weight(w, Cw, 9, O, O * 9, 9, 1, list(range(9)), Cp=Np, key=('convt_d', Np))
-        dx = torch.empty((B, H, W, Cw), dtype=torch.float32, device=draw.device)
-        g = (B, Ho, Wo, H, W, 2, 2, dhs, dws, H, W, 1, 1, 0, 0)
-        ops.gather_gemm(draw, Np, Np, 9, Wd, Cw, B * H * W, dx, Cw, mode=1, geom=g,
-                        residual=add, ldr=0 if add is None else FN.ld_of(add),
-                        flops=2.0 * B * H * W * Cw * 9 * O / 4 * 4)
-        return dx
-
-    custom_fwd = custom_wgrad = None
-    if O <= 3 and ph == pw and convt.bias is None and bn is not None:
-        def custom_fwd(xin, w, out_raw):
-            _convt_small_forward(xin, convt, out_raw)
-
-        def custom_wgrad(xin, w, draw):
-            # dWcol[(tap,o)][c] = sum_pix im2col(draw)[pix][(tap,o)] * x[pix][c]
-            n9 = ceil4(9 * O)
-            ycol = torch.empty((B * H * W, n9), dtype=torch.float32, device=draw.device)
-            ops.convt_im2col(draw, B, H, W, Ho, Wo, O, ph, ycol)
-            dwcol = torch.empty((n9, 1, Cw), dtype=torch.float32, device=draw.device)
-            ops.gather_wgrad(xin, FN.ld_of(xin), Cw, 1, n9, B * H * W, ycol, n9, dwcol, mode=0)
-            return dwcol[:9 * O, 0].reshape(9, O, Cw).permute(2, 1, 0).reshape(Cw, O, 3, 3).contiguous()
-
-    spec = FN.LayerSpec(O, Cw, 0, 1, [(g[0], g[2]) for g in geoms], B * Ho * Wo, (B, Ho, Wo), pack_fwd, dgrad,
-                        unpack, bn=bn, train=ctx.train, act=act, slope=slope, c_real=Cw,
-                        custom_forward=custom_fwd, custom_wgrad=custom_wgrad,
-                        passthrough=passthrough and x.requires_grad, defer_act=defer_act and custom_fwd is None)
-    g_, b_ = _bn_args(bn)
-    out = FN.GemmLayerFn.apply(x, convt.weight, convt.bias, g_, b_, None, spec)
-    if passthrough and not spec.passthrough:
-        return out, x
-    return out
-
-
-def _linear_grad(ctx, x, M, C, weight, bias, bn, act, slope):
-    O = weight.shape[0]
-    Cp, Np = ceil4(C), ceil4(O)
-
-    def pack_fwd(w, i):
-        return ops.pack_weight(w, O, 1, C, C, 1, 1, [0], Np=Np, Cp=Cp, key=('lin', Np, Cp))
-
-    def unpack(dWp, i, dW):
-        ops.unpack_weight(dWp, dW, O, 1, C, Cp, C, 1, 1, [0])
-    unpack.args = lambda i: (O, 1, C, Cp, C, 1, 1, [0], False)
-
-    def dgrad(spec, w, draw, xin):
-        Wd = ops.pack_weight(w, C, 1, O, 1, C, 1, [0], Np=Cp, Cp=Np, key=('lin_d', Np, Cp))
-        dx = torch.empty((M, Cp), dtype=torch.float32, device=draw.device)
-        ops.gather_gemm(draw, Np, Np, 1, Wd, Cp, M, dx, Cp, mode=0, flops=2.0 * M * C * O)
-        return dx
-
-    spec = FN.LayerSpec(O, Cp, 1, 0, [(None, M)], M, (M,), pack_fwd, dgrad, unpack, bn=bn, train=ctx.train, act=act,
-                        slope=slope, c_real=C)
-    g_, b_ = _bn_args(bn)
-    return FN.GemmLayerFn.apply(x, weight, bias, g_, b_, None, spec)
-
-
-def _blur_grad(ctx, splat, H, C, table, conv0, lv=None):
-    C0 = conv0.out_channels
-
-    def pack_fwd(w, i):
-        return ops.pack_weight(w, C0, 15, C, C * 15, 15, 1, list(range(15)), key=('blur0',))
-
-    def unpack(dWp, i, dW):
-        ops.unpack_weight(dWp, dW, C0, 15, C, C, C * 15, 15, 1, list(range(15)))
-    unpack.args = lambda i: (C0, 15, C, C, C * 15, 15, 1, list(range(15)), False)
-
-    def dgrad(spec, w, draw, xin):
-        if lv is not None and ops.BLUR_DGRAD_FUSED and C % 4 == 0 and C0 % 4 == 0:
-            return ops.blur_dgrad(lv, draw, C0, w, C)        # one gather-GEMM through the lattice's symmetric table
-        # tmp[m][t*C+c] = sum_n draw[m][n] * W0[n][c][t], then scattered through the neighbour table
-        Wd = w.detach().squeeze(-1).permute(2, 1, 0).contiguous().view(15 * C, C0)
-        tmp = torch.empty((H, 15 * C), dtype=torch.float32, device=draw.device)
-        ops.gather_gemm(draw, C0, C0, 1, Wd, 15 * C, H, tmp, 15 * C, mode=0, flops=2.0 * H * 15 * C * C0)
-        if lv is not None:              # through the lattice's own (symmetric) table: a gather, no atomics
-            return ops.neighbor_gather_adjoint(lv, tmp, C)
-        dsplat = torch.zeros((H, C), dtype=torch.float32, device=draw.device)
-        ops.table_scatter_add(tmp, table, H, 15, C, dsplat)
-        return dsplat
-
-    spec = FN.LayerSpec(C0, C, 15, 2, [(None, H)], H, (H,), pack_fwd, dgrad, unpack, act=ACT_RELU, table=table,
-                        c_real=C)
-    return FN.GemmLayerFn.apply(splat, conv0.weight, conv0.bias, None, None, None, spec)
-
-
-def _blur_grad_r(ctx, splat, H, C, lv, conv0):
-    """training form of the radius-r blur: GemmLayerFn on the mode-MODE_BLUR_R launches (forward, data gradient through the same
-    table with mirrored taps, weight gradient [C0][F][C] -> (C0, C, F, 1))"""
-    C0, F = conv0.out_channels, lv.F
-
-    def pack_fwd(w, i):
-        return ops.blur_r_pack(w)
-
-    def unpack(dWp, i, dW):
-        dW.copy_(dWp[:C0].permute(0, 2, 1).unsqueeze(-1))
-
-    def dgrad(spec, w, draw, xin):
-        return ops.blur_r_dgrad(lv, draw, C0, w, C)
-
-    spec = FN.LayerSpec(C0, C, F, ops.MODE_BLUR_R, [(None, H)], H, (H,), pack_fwd, dgrad, unpack, act=ACT_RELU, table=lv.nbr,
-                        c_real=C)
-    return FN.GemmLayerFn.apply(splat, conv0.weight, conv0.bias, None, None, None, spec)

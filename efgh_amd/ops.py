@@ -333,6 +333,26 @@ def pack_weight(w, N, T, C, sn, sc, st, taps=None, Np=None, Cp=None, key=None):
     return ent[1]
 
 
+class WeightLayout:
+    """one packed layout of a weight, stated once: Wp[n][t][c] = w.flat[n*sn + c*sc + taps[t]*st], zero-padded to (Np, T, Cp), cached on
+    the weight under `key` (pack_weight).  pack() makes it, unpack() scatters a packed gradient back into the weight's own layout,
+    fold_args() is what gather_wgrad(unpack=) wants behind dW to leave the gradient there itself."""
+    __slots__ = ('N', 'T', 'C', 'sn', 'sc', 'st', 'taps', 'Np', 'Cp', 'key')
+
+    def __init__(self, N, T, C, sn, sc, st, taps, Np=None, Cp=None, key=None):
+        self.N, self.T, self.C, self.sn, self.sc, self.st, self.taps = N, T, C, sn, sc, st, taps
+        self.Np, self.Cp, self.key = Np or N, Cp or C, key
+
+    def pack(self, w):
+        return pack_weight(w, self.N, self.T, self.C, self.sn, self.sc, self.st, self.taps, Np=self.Np, Cp=self.Cp, key=self.key)
+
+    def unpack(self, dWp, dW):
+        unpack_weight(dWp, dW, self.N, self.T, self.C, self.Cp, self.sn, self.sc, self.st, self.taps)
+
+    def fold_args(self):
+        return (self.N, self.T, self.C, self.Cp, self.sn, self.sc, self.st, self.taps, False)
+
+
 def pad_vec(v, Np, fill=0.0):
     if v is None or v.numel() == Np:
         return v
@@ -558,10 +578,15 @@ def stats_rows(mode, C, N, geom, M):
     return gemm_grid_m(M, N)
 
 
+def taps_of(T, geom):
+    """the tap count of one launch of a layer: its geometry's, or the layer's T when it has none"""
+    return T if geom is None else len(geom[7])
+
+
 def no_stats_epilogue(mode, C, N, T, launches):
     """`launches`: the [(geom, M)] of one layer.  True when every one of them lands on the thin kernels, which carry no statistics
     epilogue: the layer passes no `stats` (with `stats` the launch goes to another family) and calls col_stats on its output"""
-    return all(gemm_route(mode, C, N, T if g is None else len(g[7]), g, m) == 'thin' for g, m in launches)
+    return all(gemm_route(mode, C, N, taps_of(T, g), g, m) == 'thin' for g, m in launches)
 
 
 def _desc(A, lda, C, T, mode, N, M, geom=None, table=None, a_off=0, Wp=None, out=None, ldo=0, out_off=0, bias=None, scale=None,
@@ -1177,6 +1202,19 @@ def blur_r_pack(w, inv=None):
     if inv is None:
         return w[..., 0].permute(0, 2, 1).contiguous().view(w.shape[0], -1)
     return w[:, :, torch.as_tensor(inv, device=w.device), 0].permute(1, 2, 0).contiguous().view(w.shape[1], -1)
+
+
+class BlurRLayout:
+    """the WeightLayout members for the radius-r blur weight (C0, C, F, 1) <-> [C0][F*C]: its own packing, no fold in the launch"""
+
+    def pack(self, w):
+        return blur_r_pack(w)
+
+    def unpack(self, dWp, dW):
+        dW.copy_(dWp[:dW.shape[0]].permute(0, 2, 1).unsqueeze(-1))
+
+    def fold_args(self):
+        return None
 
 
 def blur_r_dgrad(lv, draw, C0, w, C):

@@ -142,7 +142,7 @@ def test_forward_conv_transpose_classes_vs_torch(ph, oph):
 
 @pytest.mark.parametrize('k', [1, 3])
 def test_data_gradient_geometry_vs_autograd(k):
-    """the stride-2 data gradient of layers._conv2d_grad: one launch per input-parity class on the gradient (Ho x Wo) with the placement
+    """the stride-2 data gradient of layers._conv2d_dgrad: one launch per input-parity class on the gradient (Ho x Wo) with the placement
     (2i + cy, 2j + cx) in the input image; for the 1x1 downsample only one class exists and it accumulates into the other branch's
     gradient in place (residual = out)"""
     B, H, W, C, O = 2, 9, 10, 8, 12
