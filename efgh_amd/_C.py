@@ -7,7 +7,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 SO_PATH = os.environ.get('EFGH_LIB') or os.path.join(_HERE, 'lib', 'libefgh_hip.so')      # EFGH_LIB: A/B runs of two builds
 _lib = None
-ABI_VERSION = 3          # EFGH_ABI_VERSION of include/efgh_hip.h this binding was written against
+ABI_VERSION = 4          # EFGH_ABI_VERSION of include/efgh_hip.h this binding was written against
 
 c_void_p, c_int, c_int32, c_int64, c_float = (ctypes.c_void_p, ctypes.c_int, ctypes.c_int32,
                                               ctypes.c_int64, ctypes.c_float)

@@ -7,12 +7,9 @@ the next one - lives in device memory, so when the sizes of a previous call with
 are known the whole pyramid is enqueued without a host read-back between levels (capacities = previous sizes + 25 %) and
 the five counts come back in ONE read; a count that does not fit its capacity (flagged by the device) falls back to the
 level-by-level path, which reads each count before sizing the next level."""
+import collections
 import logging
 import math
-
-import os
-
-import ctypes
 
 import numpy as np
 import torch
@@ -25,15 +22,6 @@ INFO_H, INFO_ERR, INFO_ALIAS, INFO_SEG = 0, 1, 2, 4          # include/efgh_hip.
 
 PROFILE = None          # bench.py: list of (start_event, end_event, algorithmic_bytes, 'lattice build') per pyramid
 _SIZES = {}             # (device, B, N, scales) -> vertex counts of the last build with that signature
-_PER_SAMPLE = {}        # the same key -> (largest per-sample point count, largest per-sample vertex count) per level of that build
-_NO_TAIL = {}           # the same key -> levels the one-launch tail build overflowed on: they keep the per-level kernels
-# the tail of the pyramid in ONE launch (lattice.hip k_lat_tail: one workgroup per sample builds every level that fits its LDS).
-# Built and verified bit for bit in round 5 as the round-4 verdict asked - and SLOWER than the per-level kernels at every batch
-# size (tools/bench_tail.py, MI355X: levels 3-4 of the bench scene cost ~0.33 ms as one launch of B workgroups against ~0.10 ms
-# as 14 launches over the whole chip; pyramid 0.84 vs 0.62 ms at batch 8, 2.15 vs 1.98 at 32, a tie at 64): a level is a chain of
-# ~10 dependent phases, and one workgroup on one CU walks it at its own memory latency while the per-level kernels spread every
-# phase over 256 CUs.  Off by default; tests/test_gpu_lattice.py keeps it correct.
-TAIL = False
 _BIG_LEVELS = {}        # the same key -> levels where a bucket of the partitioned build overflowed: built with the big-bucket kernel from then on
 _HASH_LEVELS = {}       # the same key -> levels where that overflowed as well: they take the hash build
 _CLEAN = {}             # the same key -> consecutive clean speculative builds since the last change of the escalation sets
@@ -158,63 +146,73 @@ class _SampleView:
 
 
 
-
 def _pow2ceil(v):
     return 1 << max(0, int(v) - 1).bit_length()
 
 
-def _plan(L, n_cap, h_est):
-    """how to build a level of n_cap points expecting ~h_est vertices (None: unknown):
-    ('part', buckets, slots per bucket) - entries dealt into buckets, every bucket grouped in LDS - or, for more points than the
-    partitioned build's bucket limit (~2.8 M), ('hash', slots) - the global hash insert (0 = its default table)"""
-    nb = L.efgh_lattice_part_buckets(_C.c_int32(n_cap))
+# how a level is built.  kind 'part': the entries are dealt into `buckets` buckets and every bucket is grouped in LDS in a table of
+# `slots` slots, big: with the big-bucket kernel behind it (one more launch; spatially dense sweeps need it).  kind 'hash': the
+# global hash insert into a table of `slots` entries (0 = its default table); buckets = 0, big = False
+Plan = collections.namedtuple('Plan', 'kind buckets slots big')
+
+
+def _as_plan(mode):
+    """a Plan from what a caller hands in: a Plan, ('hash', slots), ('part', buckets, slots) or ('part', buckets, slots, big)"""
+    if isinstance(mode, Plan):
+        return mode
+    if mode[0] == 'hash':
+        return Plan('hash', 0, mode[1], False)
+    return Plan('part', mode[1], mode[2], len(mode) > 3 and bool(mode[3]))
+
+
+def _plan(L, n_cap, h_est, hashed=False, big=False):
+    """the Plan of a level of n_cap points expecting ~h_est vertices (None: unknown).  hashed / big: the level's escalation state
+    (_HASH_LEVELS / _BIG_LEVELS).  More points than the partitioned build's bucket limit (~2.8 M) take the hash build as well"""
+    nb = 0 if hashed else L.efgh_lattice_part_buckets(_C.c_int32(n_cap))
     if nb:
-        if h_est is None:
-            return ('part', nb, 2048)
-        return ('part', nb, min(2048, max(64, _pow2ceil(2.5 * h_est / nb + 64))))
-    if h_est is None:
-        return ('hash', 0)
+        return Plan('part', nb, 2048 if h_est is None else min(2048, max(64, _pow2ceil(2.5 * h_est / nb + 64))), big)
     # hash table sized for the expected vertex count (load <= 1/2) instead of the worst case 4 * n_cap keys
-    return ('hash', max(4096, 1 << (2 * h_est - 1).bit_length()))
+    return Plan('hash', 0, 0 if h_est is None else max(4096, 1 << (2 * h_est - 1).bit_length()), False)
 
 
-class _TailLevel(ctypes.Structure):
-    """mirror of efgh_lattice_tail_level (include/efgh_hip.h)"""
-    _fields_ = [('scale32', ctypes.c_float), ('div32', ctypes.c_float), ('h_cap', ctypes.c_int32), ('alias_cap', ctypes.c_int32),
-                ('bary', ctypes.c_void_p), ('emg', ctypes.c_void_p), ('off', ctypes.c_void_p), ('list', ctypes.c_void_p),
-                ('vseg', ctypes.c_void_p), ('nbr', ctypes.c_void_p), ('pts_next', ctypes.c_void_p), ('vsid', ctypes.c_void_p),
-                ('info', ctypes.c_void_p), ('alist', ctypes.c_void_p)]
+def _state(key, l):
+    """(hashed, big) of level l of a signature, as _plan takes them"""
+    return l in _HASH_LEVELS[key], l in _BIG_LEVELS[key]
 
 
-class _TailDesc(ctypes.Structure):
-    """mirror of efgh_lattice_tail_desc"""
-    _fields_ = [('nlevels', ctypes.c_int32), ('nsamples', ctypes.c_int32), ('slots', ctypes.c_int32), ('pts_per_sample', ctypes.c_int32),
-                ('pts', ctypes.c_void_p), ('pts_cstride', ctypes.c_int64), ('info_prev', ctypes.c_void_p), ('prev_h_cap', ctypes.c_int32),
-                ('pad', ctypes.c_int32), ('levels', _TailLevel * 5)]
+def _escalate(key, l, err, plan):
+    """level l, built by the partitioned `plan`, overflowed (ERR bit 2: a bucket with more entries than its window, a table too
+    small): it is escalated for this signature - first to the build with the big-bucket kernel, then to the hash build.  A key range
+    too wide for the partitioned build's entry word (bit 3) is not a bucket problem: the big-bucket kernel cannot fix it, the level
+    goes straight to the hash build.  Returns the name of the build the level takes from now on"""
+    to_hash = bool(err & 8) or plan.big
+    (_HASH_LEVELS if to_hash else _BIG_LEVELS)[key].add(l)
+    _CLEAN[key] = 0
+    return 'hash' if to_hash else 'big-bucket'
 
 
-def _tail_plan(L, key, B, N, nlev):
-    """(first tail level, table slots) or None: the levels [l0, nlev) of this signature whose largest sample had, in the previous
-    build, few enough points and vertices (with 25 % headroom) for one workgroup's LDS"""
-    ps = _PER_SAMPLE.get(key)
-    if not TAIL or ps is None or B > 64:
-        return None
-    nmax = L.efgh_lattice_tail_max_points()
-    bad = _NO_TAIL.get(key, set())
-    l0, slots = nlev, 1024
-    for l in range(nlev - 1, -1, -1):
-        mn, mh = ps[l]
-        need = _pow2ceil(max(1024, int((mh + mh // 8 + 32) / 0.8)))          # (the kernel flags a table more than 0.8 full)
-        if l in bad or mn + mn // 4 + 64 > nmax or need > 2048:
-            break
-        l0, slots = l, max(slots, need)
-    return (l0, slots) if l0 < nlev else None
+def _relax(key):
+    """the counterpart of _escalate, after a clean speculative build: once ESCALATION_DECAY of them have passed in a row the most
+    expensive escalation of the signature is taken back one step"""
+    forced, bigl = _HASH_LEVELS[key], _BIG_LEVELS[key]
+    _CLEAN[key] = _CLEAN.get(key, 0) + 1
+    if not (forced or bigl) or ESCALATION_DECAY <= 0 or _CLEAN[key] < ESCALATION_DECAY:
+        return
+    _CLEAN[key] = 0
+    if forced:
+        l = max(forced)
+        forced.discard(l)
+        bigl.add(l)
+        _log.info('lattice %s: level %d back from the hash build to the big-bucket build after %d clean builds', key, l, ESCALATION_DECAY)
+    else:
+        l = max(bigl)
+        bigl.discard(l)
+        _log.info('lattice %s: level %d back to the regular partitioned build after %d clean builds', key, l, ESCALATION_DECAY)
 
 
 def _ctrl_bytes(L, n_cap, B, mode):
-    """bytes of the zero-initialised control block of a level: info (+ the tail build's ticket and per-sample counts behind the
-    sample bases), and for the partitioned build its `zeroed` area"""
-    info_b = (4 * (INFO_SEG + 2 * B + 2) + 255) // 256 * 256
+    """bytes of the zero-initialised control block of a level: info, and for the partitioned build its `zeroed` area"""
+    info_b = (4 * (INFO_SEG + B) + 255) // 256 * 256
     return info_b, (L.efgh_lattice_part_zeroed_bytes(_C.c_int32(n_cap)) if mode[0] == 'part' else 0)
 
 
@@ -222,17 +220,14 @@ def _level_arrays(L, dev, n_cap, h_cap, B, mode=('hash', 0), ctrl=None, need_off
     """arrays of one level.  ctrl: a ZEROED uint8 tensor of sum(_ctrl_bytes) bytes (one fill serves all levels of a pyramid);
     None = allocate and zero one here.  need_off=False (partitioned build only): lattice_offset is not produced"""
     lv = LatticeLevel()
-    lv._mode = mode
+    lv._mode = mode = _as_plan(mode)
     lv.radius, lv.F, lv.ld = 1, 15, 16
     lv.bary_pm = torch.empty((n_cap, 4), dtype=torch.float32, device=dev)
     lv.emg_pm = torch.empty((n_cap, 4), dtype=torch.float32, device=dev)
-    lv.off_pm = torch.empty((n_cap, 4), dtype=torch.int32, device=dev) if (need_off or mode[0] == 'hash') else None
-    if mode[0] == 'part':       # every bucket owns a fixed window of the list array
-        lv.list = torch.empty(L.efgh_lattice_part_list_len(n_cap, mode[1]), dtype=torch.int32, device=dev)
-        ws_bytes = L.efgh_lattice_part_workspace_bytes(n_cap, h_cap, B, mode[1], mode[2])
-    elif mode[0] == 'tail':     # everything else lives in the workgroups' LDS
-        lv.list = torch.empty(4 * n_cap, dtype=torch.int32, device=dev)
-        ws_bytes = 0
+    lv.off_pm = torch.empty((n_cap, 4), dtype=torch.int32, device=dev) if (need_off or mode.kind == 'hash') else None
+    if mode.kind == 'part':       # every bucket owns a fixed window of the list array
+        lv.list = torch.empty(L.efgh_lattice_part_list_len(n_cap, mode.buckets), dtype=torch.int32, device=dev)
+        ws_bytes = L.efgh_lattice_part_workspace_bytes(n_cap, h_cap, B, mode.buckets, mode.slots)
     else:
         lv.list = torch.empty(4 * n_cap, dtype=torch.int32, device=dev)
         ws_bytes = L.efgh_lattice_workspace_bytes(n_cap, h_cap, B)
@@ -255,38 +250,40 @@ def _launch_build(L, lv, pts, cstride, n_dev, sid, pps, B, s, st):
     head = (_C.ptr(pts), _C.c_int64(cstride), _C.ptr(n_dev), _C.c_int32(n_cap), _C.ptr(sid), _C.c_int32(pps), _C.c_int32(B),
             _C.c_float(np.float32(s)))
     lv._geom = (pts, cstride, n_dev, sid, pps, s)          # (kept alive for the neighbours call)
-    if lv._mode[0] == 'part':
+    plan = lv._mode
+    if plan.kind == 'part':
         _C.check(L.efgh_lattice_part_build(*head, _C.ptr(lv.bary_pm), _C.ptr(lv.emg_pm), _C.ptr(lv.list), _C.c_int32(h_cap),
-                                           _C.ptr(lv.info), _C.ptr(lv._ws), _C.ptr(lv._zeroed), _C.c_int32(lv._mode[1]),
-                                           _C.c_int32(lv._mode[2]), _C.c_int32(0 if lv.off_pm is None else 1),
-                                           _C.c_int32(1 if len(lv._mode) > 3 and lv._mode[3] else 0), st))
+                                           _C.ptr(lv.info), _C.ptr(lv._ws), _C.ptr(lv._zeroed), _C.c_int32(plan.buckets),
+                                           _C.c_int32(plan.slots), _C.c_int32(0 if lv.off_pm is None else 1),
+                                           _C.c_int32(1 if plan.big else 0), st))
     else:
         _C.check(L.efgh_lattice_level_build(*head, _C.c_float(np.float32(EXPECTED_STD * s)), _C.ptr(lv.bary_pm), _C.ptr(lv.emg_pm),
                                             _C.ptr(lv.off_pm), _C.ptr(lv.list), _C.c_int32(h_cap), _C.ptr(lv.vseg),
                                             _C.ptr(lv.pts_next_buf), _C.ptr(lv.vsid), _C.ptr(lv.info), _C.ptr(lv._ws),
-                                            _C.c_int64(lv._mode[1]), st))
+                                            _C.c_int64(plan.slots), st))
 
 
 def _launch_neighbors(L, lv, B, h_rows, st):
     n_cap, h_cap = lv._caps
+    plan = lv._mode
     lv.nbr = torch.empty((h_rows, 16), dtype=torch.int32, device=lv.info.device)
-    if lv.radius != 1 and lv._mode[0] != 'part':
+    if lv.radius != 1 and plan.kind != 'part':
         _launch_neighbors_r(L, lv, B, h_rows, st)          # (the hash build left its vertex records: its radius-1 probes are not needed)
         return
-    if lv._mode[0] == 'part':
+    if plan.kind == 'part':
         pts, cstride, n_dev, sid, pps, s = lv._geom
         _C.check(L.efgh_lattice_part_neighbors(
             _C.ptr(lv._ws), _C.ptr(pts), _C.c_int64(cstride), _C.ptr(n_dev), _C.c_int32(n_cap), _C.ptr(sid), _C.c_int32(pps),
             _C.c_int32(B), _C.c_float(np.float32(s)), _C.c_float(np.float32(EXPECTED_STD * s)), _C.c_int32(h_cap), _C.ptr(lv.info),
             _C.c_int32(h_rows), _C.ptr(lv.nbr), _C.ptr(lv.alist), _C.c_int32(ALIAS_CAP), _C.ptr(lv.off_pm), _C.ptr(lv.vseg),
-            _C.ptr(lv.pts_next_buf), _C.ptr(lv.vsid), _C.c_int32(lv._mode[1]), _C.c_int32(lv._mode[2]), st))
+            _C.ptr(lv.pts_next_buf), _C.ptr(lv.vsid), _C.c_int32(plan.buckets), _C.c_int32(plan.slots), st))
         if lv.radius != 1:              # (that launch also emitted the vertex records the radius-r probes start from)
             _launch_neighbors_r(L, lv, B, h_rows, st)
             return
     else:
         _C.check(L.efgh_lattice_level_neighbors(_C.ptr(lv._ws), _C.c_int32(n_cap), _C.c_int32(h_cap), _C.c_int32(B), _C.ptr(lv.info),
                                                 _C.ptr(lv.vsid), _C.c_int32(h_rows), _C.ptr(lv.nbr), _C.ptr(lv.alist),
-                                                _C.c_int32(ALIAS_CAP), _C.c_int64(lv._mode[1]), st))
+                                                _C.c_int32(ALIAS_CAP), _C.c_int64(plan.slots), st))
     lv._geom = lv._zeroed = None
 
 
@@ -303,6 +300,23 @@ def _launch_neighbors_r(L, lv, B, h_rows, st):
     lv._geom = lv._zeroed = None
 
 
+def _enqueue(L, lv, src, N, B, s, st, exact=False):
+    """build and neighbours of one level from its source (pts, cstride, n_dev, sid, n_cap) -> (the next level's source, ERR).
+    exact: the vertex count H is read back between the two (a host sync) - the neighbour table gets H rows and the next level
+    exactly H points; a partitioned build that overflowed (ERR bit 2) gets no neighbours and no next source (None)"""
+    pts, cstride, n_dev, sid, _ = src
+    h_cap = lv._caps[1]
+    _launch_build(L, lv, pts, cstride, n_dev, sid, N, B, s, st)
+    if not exact:           # the count stays on the device: capacities stand in for it
+        _launch_neighbors(L, lv, B, h_cap, st)
+        return (lv.pts_next_buf, h_cap, lv.info[INFO_H:], lv.vsid, h_cap), 0
+    H, err = lv.info[:2].tolist()
+    if err & 4 and lv._mode.kind == 'part':
+        return None, err
+    _launch_neighbors(L, lv, B, H, st)
+    return (lv.pts_next_buf, h_cap, None, lv.vsid, H), err
+
+
 def _finish(lv, host, n_in, seg_in, B):
     if host[INFO_ERR] & 2:
         raise _C.EfghError('lattice: more than %d aliased neighbour hits on one level' % ALIAS_CAP)
@@ -313,6 +327,66 @@ def _finish(lv, host, n_in, seg_in, B):
     lv._ws = None                      # scratch no longer needed (the stream orders its reuse)
     if lv.nbr.shape[0] != H:
         lv.nbr = lv.nbr[:H]
+
+
+def _speculative(L, dev, key, prev, src, scales, radii, B, N, need_off, st, e1):
+    """the whole pyramid enqueued with capacities from `prev`, the vertex counts of the previous build of this signature (+ 25 %),
+    no read-back between levels, the counts back in ONE read.  Returns (levels, False); (None, False) when the batch has to take
+    the level-by-level path - a vertex count beyond its capacity (ERR bit 0); or (None, True) when a partitioned level overflowed
+    and was escalated: the pyramid is to be enqueued once more (levels behind the first overflow were built on its garbage)"""
+    # capacities and plans of all levels first: their control blocks (device counters, first-seen bitmaps) are zeroed by ONE fill.
+    # Tables are sized for the expected vertex count
+    caps, nc = [], src[4]
+    for l, hp in enumerate(prev):
+        hc = min(4 * nc, hp + hp // 4 + 1024)
+        caps.append((nc, hc, _plan(L, nc, hc, *_state(key, l))))
+        nc = hc
+    sizes = [_ctrl_bytes(L, nc_, B, plan) for nc_, _, plan in caps]
+    ctrl = torch.zeros(sum(a + b for a, b in sizes), dtype=torch.uint8, device=dev)
+    lvs, coff = [], 0
+    for s, r, (n_cap, h_cap, plan), (ib, zb) in zip(scales, radii, caps, sizes):
+        lv = _level_arrays(L, dev, n_cap, h_cap, B, plan, ctrl[coff:coff + ib + zb], need_off)
+        _set_radius(lv, r)
+        coff += ib + zb
+        src, _ = _enqueue(L, lv, src, N, B, s, st)
+        lvs.append(lv)
+    if e1 is not None:
+        e1.record()              # (before the read-back: the events bracket the launches only)
+    host = torch.stack([lv.info for lv in lvs]).cpu().tolist()           # the one host sync of the pyramid
+    if not any(h[INFO_ERR] & 5 for h in host):
+        n_in, seg_in = B * N, [b * N for b in range(B + 1)]
+        for lv, h in zip(lvs, host):
+            _finish(lv, h, n_in, seg_in, B)
+            n_in, seg_in = lv.H, lv.seg
+        _relax(key)
+        return lvs, False
+    over = [l for l, (h, lv) in enumerate(zip(host, lvs)) if h[INFO_ERR] & 4 and lv._mode.kind == 'part']
+    if not over or any(h[INFO_ERR] & 1 for h in host):
+        return None, False
+    l, err = over[0], host[over[0]][INFO_ERR]
+    _log.warning('lattice %s: level %d %s; escalated to the %s build, pyramid re-enqueued', key, l,
+                 'has a key range too wide for the partitioned build' if err & 8 else 'overflowed a bucket',
+                 _escalate(key, l, err, lvs[l]._mode))
+    return None, True
+
+
+def _level_by_level(L, dev, key, src, scales, radii, B, N, need_off, st):
+    """each level's count is read before the next level is sized (exact capacities); a partitioned level that overflows is
+    escalated and built again on the spot"""
+    out, seg_in = [], [b * N for b in range(B + 1)]
+    for l, (s, r) in enumerate(zip(scales, radii)):
+        n, nxt = src[4], None
+        while nxt is None:
+            plan = _plan(L, n, None, *_state(key, l))
+            lv = _level_arrays(L, dev, n, 4 * n, B, plan, None, need_off)
+            _set_radius(lv, r)
+            nxt, err = _enqueue(L, lv, src, N, B, s, st, exact=True)
+            if nxt is None:
+                _escalate(key, l, err, plan)
+        _finish(lv, lv.info.cpu().tolist(), n, seg_in, B)
+        out.append(lv)
+        src, seg_in = nxt, lv.seg
+    return out
 
 
 def build_pyramid_batched(pc, scales, radii=None, need_off=True):
@@ -326,158 +400,32 @@ def build_pyramid_batched(pc, scales, radii=None, need_off=True):
     dev = pc.device
     B, _, N = pc.shape
     assert pc.dtype == torch.float32 and pc.size(1) == 3 and B >= 1 and N >= 1
-    pts0 = pc.permute(1, 0, 2).reshape(3, B * N).contiguous()
+    src = (pc.permute(1, 0, 2).reshape(3, B * N).contiguous(), B * N, None, None, B * N)
     st = _C.stream_ptr()
     scales = [float(s) for s in scales]
     key = (dev.index, B, N, tuple(scales))
+    e0 = e1 = None
     if PROFILE is not None:
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
-    out = lvs = None
+    out = None
     prev = _SIZES.get(key)
-    forced, bigl = _HASH_LEVELS.setdefault(key, set()), _BIG_LEVELS.setdefault(key, set())
-    for attempt in range(3 if prev is not None else 0):
-        # speculative path: capacities from the previous build of this signature, no read-back between levels
-        lvs, pts, cstride, n_dev, sid, n_cap = [], pts0, B * N, None, None, B * N
-        # capacities and plans of all levels first: their control blocks (device counters, first-seen bitmaps) are zeroed by ONE fill.
-        # Tables are sized for the expected vertex count.  A partitioned level that overflows (ERR bit 2: a bucket with more entries
-        # than its window, a table too small) is escalated for this signature - first to the build with the big-bucket kernel
-        # (one more launch; spatially dense sweeps need it, the random-range bench scene never does), then to the hash build -
-        # and the pyramid is enqueued once more; a vertex count beyond its capacity (bit 0) sends the batch to the
-        # level-by-level path below
-        caps, nc = [], n_cap
-        tail = _tail_plan(L, key, B, N, len(prev))
-        if tail is not None and any(l in forced or l in bigl or radii[l] != 1 for l in range(tail[0], len(prev))):
-            tail = None                 # (the one-launch tail probes the 15 radius-1 taps only: such levels keep the per-level kernels)
-        for l, hp in enumerate(prev):
-            hc = min(4 * nc, hp + hp // 4 + 1024)
-            md = _plan(L, nc, hc)
-            if tail is not None and l >= tail[0]:
-                md = ('tail', tail[1])
-            elif l in forced and md[0] == 'part':
-                md = ('hash', max(4096, 1 << (2 * hc - 1).bit_length()))
-            elif l in bigl and md[0] == 'part':
-                md = md + (True,)
-            caps.append((nc, hc, md))
-            nc = hc
-        sizes = [_ctrl_bytes(L, nc_, B, md) for nc_, _, md in caps]
-        ctrl = torch.zeros(sum(a + b for a, b in sizes), dtype=torch.uint8, device=dev)
-        coff = 0
-        tail_lvs = []
-        for s, r, (n_cap, h_cap, mode), (ib, zb) in zip(scales, radii, caps, sizes):
-            lv = _level_arrays(L, dev, n_cap, h_cap, B, mode, ctrl[coff:coff + ib + zb], need_off)
-            _set_radius(lv, r)
-            coff += ib + zb
-            if mode[0] == 'tail':
-                lv.nbr = torch.empty((h_cap, 16), dtype=torch.int32, device=dev)
-                tail_lvs.append((lv, s))
-                lvs.append(lv)
-                continue
-            _launch_build(L, lv, pts, cstride, n_dev, sid, N, B, s, st)
-            _launch_neighbors(L, lv, B, h_cap, st)
-            lvs.append(lv)
-            pts, cstride, n_dev, sid, n_cap = lv.pts_next_buf, h_cap, lv.info[INFO_H:], lv.vsid, h_cap
-        if tail_lvs:
-            # the remaining levels in ONE launch: one workgroup per sample walks down them in LDS
-            d = _TailDesc()
-            d.nlevels, d.nsamples, d.slots = len(tail_lvs), B, tail_lvs[0][0]._mode[1]
-            first = len(lvs) - len(tail_lvs)
-            d.pts, d.pts_cstride = pts.data_ptr(), cstride
-            if first == 0:
-                d.pts_per_sample, d.info_prev, d.prev_h_cap = N, 0, 0
-            else:
-                d.pts_per_sample, d.info_prev, d.prev_h_cap = 0, lvs[first - 1].info.data_ptr(), lvs[first - 1]._caps[1]
-            for i, (lv, s) in enumerate(tail_lvs):
-                t = d.levels[i]
-                t.scale32, t.div32 = float(np.float32(s)), float(np.float32(EXPECTED_STD * s))
-                t.h_cap, t.alias_cap = lv._caps[1], ALIAS_CAP
-                t.bary, t.emg, t.off = lv.bary_pm.data_ptr(), lv.emg_pm.data_ptr(), (0 if lv.off_pm is None else lv.off_pm.data_ptr())
-                t.list, t.vseg, t.nbr = lv.list.data_ptr(), lv.vseg.data_ptr(), lv.nbr.data_ptr()
-                t.pts_next, t.vsid, t.info, t.alist = lv.pts_next_buf.data_ptr(), lv.vsid.data_ptr(), lv.info.data_ptr(), lv.alist.data_ptr()
-            _C.check(L.efgh_lattice_tail_build(ctypes.byref(d), st))
-        if PROFILE is not None:
-            e1.record()              # (before the read-back: the events bracket the launches only)
-        host = torch.stack([lv.info for lv in lvs]).cpu().tolist()           # the one host sync of the pyramid
-        if not any(h[INFO_ERR] & 5 for h in host):
-            n_in, seg_in = B * N, [b * N for b in range(B + 1)]
-            for lv, h in zip(lvs, host):
-                _finish(lv, h, n_in, seg_in, B)
-                n_in, seg_in = lv.H, lv.seg
-            out = lvs
-            STATS['speculative'] += 1
-            _CLEAN[key] = _CLEAN.get(key, 0) + 1
-            if (forced or bigl) and ESCALATION_DECAY > 0 and _CLEAN[key] >= ESCALATION_DECAY:
-                _CLEAN[key] = 0
-                if forced:
-                    l = max(forced)
-                    forced.discard(l)
-                    bigl.add(l)
-                    _log.info('lattice %s: level %d back from the hash build to the big-bucket build after %d clean builds', key, l, ESCALATION_DECAY)
-                else:
-                    l = max(bigl)
-                    bigl.discard(l)
-                    _log.info('lattice %s: level %d back to the regular partitioned build after %d clean builds', key, l, ESCALATION_DECAY)
+    _HASH_LEVELS.setdefault(key, set())
+    _BIG_LEVELS.setdefault(key, set())
+    for _ in range(3 if prev is not None else 0):
+        out, again = _speculative(L, dev, key, prev, src, scales, radii, B, N, need_off, st, e1)
+        if not again:
             break
-        tail_over = [l for l, (h, lv) in enumerate(zip(host, lvs)) if h[INFO_ERR] & 4 and lv._mode[0] == 'tail']
-        if tail_over and not any(h[INFO_ERR] & 4 and lv._mode[0] == 'part' for h, lv in zip(host, lvs)) \
-                and not any(h[INFO_ERR] & 1 for h, lv in zip(host, lvs) if lv._mode[0] != 'tail'):
-            # a sample did not fit a workgroup's LDS on that level (points, vertices, a very long list): the level keeps the
-            # per-level kernels for this signature from now on; the pyramid is enqueued once more
-            _NO_TAIL.setdefault(key, set()).add(tail_over[0])
-            STATS['reenqueued'] += 1
-            _log.warning('lattice %s: level %d does not fit the one-launch tail build; per-level kernels from now on, pyramid re-enqueued',
-                         key, tail_over[0])
-            continue
-        over = [l for l, (h, lv) in enumerate(zip(host, lvs)) if h[INFO_ERR] & 4 and lv._mode[0] == 'part']
-        if not over or any(h[INFO_ERR] & 1 for h in host):
-            break
-        # (levels behind the first overflow were built on its garbage.)  A key range too wide for the partitioned build's entry
-        # word (bit 3) is not a bucket problem: the big-bucket kernel cannot fix it, the level goes straight to the hash build
-        wide = bool(host[over[0]][INFO_ERR] & 8)
-        (forced if (wide or over[0] in bigl) else bigl).add(over[0])
-        _CLEAN[key] = 0
         STATS['reenqueued'] += 1
-        _log.warning('lattice %s: level %d %s; escalated to the %s build, pyramid re-enqueued', key, over[0],
-                     'has a key range too wide for the partitioned build' if wide else 'overflowed a bucket',
-                     'hash' if over[0] in forced else 'big-bucket')
-    if out is None:
-        # level-by-level path: each level's count is read before the next level is sized (exact capacities)
+    if out is not None:
+        STATS['speculative'] += 1
+    else:
         STATS['level_by_level'] += 1
-        out, pts, cstride, sid, n = [], pts0, B * N, None, B * N
-        seg_in = [b * N for b in range(B + 1)]
-        for l, s in enumerate(scales):
-            plan = _plan(L, n, None)
-            modes = [('hash', 0)] if (l in forced or plan[0] != 'part') else [plan + (l in bigl,), plan + (True,), ('hash', 0)]
-            i = 0
-            while True:
-                mode = modes[i]
-                lv = _level_arrays(L, dev, n, 4 * n, B, mode, None, need_off)
-                _set_radius(lv, radii[l])
-                _launch_build(L, lv, pts, cstride, None, sid, N, B, s, st)
-                head = lv.info[:2].tolist()           # host sync (sizes the next level)
-                if not head[INFO_ERR] & 4 or mode == ('hash', 0):
-                    break
-                # a bucket of the partitioned build overflowed - escalate; a key range too wide for its entry word (bit 3) goes
-                # straight to the hash build
-                _CLEAN[key] = 0
-                if head[INFO_ERR] & 8:
-                    forced.add(l)
-                    i = len(modes) - 1
-                else:
-                    (forced if (l in bigl or mode[-1] is True) else bigl).add(l)
-                    i += 1
-            H = head[INFO_H]
-            _launch_neighbors(L, lv, B, H, st)
-            host = lv.info.cpu().tolist()
-            _finish(lv, host, n, seg_in, B)
-            out.append(lv)
-            pts, cstride, sid, n, seg_in = lv.pts_next_buf, 4 * n, lv.vsid, H, lv.seg
-    _SIZES[key] = [lv.H for lv in out]
-    _PER_SAMPLE[key] = [(max(b - a for a, b in zip(lv.seg_in[:-1], lv.seg_in[1:])), max(b - a for a, b in zip(lv.seg[:-1], lv.seg[1:])))
-                        for lv in out]
-    if PROFILE is not None:
-        if prev is None or out is not lvs:
+        out = _level_by_level(L, dev, key, src, scales, radii, B, N, need_off, st)
+        if e1 is not None:
             e1.record()
+    _SIZES[key] = [lv.H for lv in out]
+    if PROFILE is not None:
         by = 0.0
         for lv in out:          # reads N*3*4, writes N*(4*4 + 4*4 + 4*8) + 15*H*8 + 4*H*4
             by += lv.n_in * 12.0 + lv.n_in * 64.0 + lv.H * (lv.F * 8 + 16.0)

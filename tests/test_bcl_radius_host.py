@@ -114,7 +114,7 @@ def test_radius_entry_points_exported():
         assert re.search(r'\b' + n + r'\s*\(', hdr), n
         assert hasattr(lib, n), n
     lib.efgh_version.restype = ctypes.c_int
-    assert lib.efgh_version() == 3
+    assert lib.efgh_version() == 4
     lib.efgh_lattice_neighbors_r_workspace.restype = ctypes.c_int64
     assert lib.efgh_lattice_neighbors_r_workspace(ctypes.c_int32(1000), ctypes.c_int32(2)) > 1000 * 16
     # argument validation before any device work

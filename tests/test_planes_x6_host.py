@@ -31,7 +31,7 @@ def test_header_declares_and_library_exports_the_x6_entry_points(so_path):
     hdr = re.sub(r'/\*.*?\*/', '', open(os.path.join(ROOT, 'include', 'efgh_hip.h')).read(), flags=re.S)
     assert _decl(hdr, 'efgh_plane_gemm_x6') == _decl(hdr, 'efgh_plane_gemm')
     assert _decl(hdr, 'efgh_plane_wgrad_x6_batched') == _decl(hdr, 'efgh_plane_wgrad_batched')
-    assert int(re.search(r'#define\s+EFGH_ABI_VERSION\s+(\d+)', hdr).group(1)) == 3
+    assert int(re.search(r'#define\s+EFGH_ABI_VERSION\s+(\d+)', hdr).group(1)) == 4
     lib = ctypes.CDLL(so_path)
     for n in X6:
         assert hasattr(lib, n), n
