@@ -13,6 +13,16 @@ __device__ __forceinline__ float act_f(float v, int act, float slope) {
     return v;
 }
 
+// the same for the kernels that WRITE an activation map (k_scale_shift_act*): a NaN stays a NaN under ReLU too (`v > 0` is false for a
+// NaN, so act_f turns NaN statistics into a channel of clean zeros - a diverged network must not look healthy; the GEMM epilogues
+// behave the same way).  Every non-NaN value keeps its bits.  (k_maxpool2_affine keeps act_f: its fmaxf drops a NaN anyway, and the
+// fused inference pools are pinned bit-identical to it.)
+__device__ __forceinline__ float act_keep_nan(float v, int act, float slope) {
+    if (act == 1) return (v > 0.f || v != v) ? v : 0.f;
+    if (act == 2) return v > 0.f ? v : v * slope;
+    return v;
+}
+
 // stats: [G][2][C] per-block partial (sum, sumsq) from the GEMM epilogue.
 // -> scale/shift for y = x*scale + shift, running stats update (nn.BatchNorm, momentum form).
 // stage 1 for many partial rows: slice s sums rows g = s, s+S, s+2S, ... into row s (in place: row s is
@@ -113,8 +123,8 @@ k_scale_shift_act(const float *__restrict__ x, long long ldx, const float *__res
             float4 q = *reinterpret_cast<const float4 *>(res + r * ldr + c);
             v.x += q.x; v.y += q.y; v.z += q.z; v.w += q.w;
         }
-        v.x = act_f(v.x, act, slope); v.y = act_f(v.y, act, slope);
-        v.z = act_f(v.z, act, slope); v.w = act_f(v.w, act, slope);
+        v.x = act_keep_nan(v.x, act, slope); v.y = act_keep_nan(v.y, act, slope);
+        v.z = act_keep_nan(v.z, act, slope); v.w = act_keep_nan(v.w, act, slope);
         st_stream<NT>(y + r * ldy + c, v);
         if (BITS) {
             // (total % 8 == 0 and the loop advances all lanes together: the eight lanes of a word are active together)
@@ -136,7 +146,7 @@ k_scale_shift_act1(const float *__restrict__ x, long long ldx, const float *__re
         long long r = i / C; int c = (int)(i - r * C);
         float v = x[r * ldx + c] * (scale ? scale[c] : 1.f) + (shift ? shift[c] : 0.f);
         if (res) v += res[r * ldr + c];
-        y[r * ldy + c] = act_f(v, act, slope);
+        y[r * ldy + c] = act_keep_nan(v, act, slope);
     }
 }
 

@@ -292,6 +292,7 @@ int efgh_col_stats(const float *x, int64_t M, int32_t C, int64_t ld, float *stat
 int efgh_scale_shift_act(const float *x, int64_t ldx, const float *scale, const float *shift,
                          const float *res, int64_t ldr, float *y, int64_t ldy, int64_t M, int32_t C,
                          int32_t act, float slope, void *stream);
+/* (both forms: a NaN stays a NaN under every activation, ReLU included; its mask bit is 0) */
 /* the same pass, also leaving the sign bits of y (C % 32 == 0): bit (r*C + c) % 32 of word (r*C + c) / 32 = (y[r][c] > 0), M*C/32
  * words - the activation mask of a residual layer for efgh_act_bn_bwd_reduce / _apply (pass it as `y` with ldy = 0)       */
 int efgh_scale_shift_act_bits(const float *x, int64_t ldx, const float *scale, const float *shift,
@@ -516,7 +517,9 @@ int efgh_pool_bn_bwd_reduce(const float *dy_pool, const float *raw, const float 
                             void *stream);
 /* round 6: the same sums for a ReLU layer from POOLED tensors only - the pooled gradient and the pooled activation y_pool
  * [B][H/2][W/2][C] (dpre is non-zero only where y_pool > 0, and there xhat = (y_pool - beta) / gamma of the winning element): half a
- * unit of traffic instead of 1.25.  raw is read only for channels with pscale == 0.  part: [efgh_bwd_groups(B*(H/2)*(W/2))][2][C] */
+ * unit of traffic instead of 1.25.  raw is read only for channels with pscale == 0 or |beta| > 2 |gamma| (beta = mean*pscale + pshift,
+ * gamma = pscale/invstd: there the rounding of y_pool would cost |beta|/|gamma| roundings of xhat), whose xhat comes from raw at the
+ * window's first maximum.  part: [efgh_bwd_groups(B*(H/2)*(W/2))][2][C] */
 int efgh_pool_bn_bwd_reduce_pooled(const float *dy_pool, const float *y_pool, const float *raw, const float *mean,
                                    const float *invstd, const float *pscale, const float *pshift, int32_t B, int32_t H, int32_t W,
                                    int32_t C, double *part, float *sum_dpre, float *sum_dpre_xhat, double *mean_dpre,
