@@ -9,6 +9,7 @@
 // weights fetched by one load each, then lanes = (entry, 16-byte chunk) pairs so that every row of the list is in flight at
 // once; partial sums are folded across the entry slots with shuffles and the normalised row is written once.
 #include "common.h"
+#include <algorithm>
 
 namespace {
 constexpr int TPB = 256;
@@ -34,7 +35,7 @@ template <int LPV>
 __global__ void __launch_bounds__(TPB)
 k_splat_gather(const float4 *__restrict__ emg, const float4 *__restrict__ feat, int64_t ldf4, int cf4,
                const float *__restrict__ bary, const int *__restrict__ list, const int2 *__restrict__ vseg, int H,
-               float4 *__restrict__ splat, float *__restrict__ wsum, int normalize) {
+               float4 *__restrict__ splat, int64_t lds4, float *__restrict__ wsum, int normalize) {
     constexpr int VPB = TPB / LPV;                             // vertices per block
     const int64_t nblocks = ((int64_t)H + VPB - 1) / VPB;
     const int64_t blk = xcd_band_block(blockIdx.x, nblocks);
@@ -94,10 +95,10 @@ k_splat_gather(const float4 *__restrict__ emg, const float4 *__restrict__ feat, 
     if (e != 0 || !have) return;
     // w of slot 0 was accumulated by every lane of the slot identically
     const float nrm = normalize ? 1.0f / (w + 1e-5f) : 1.0f;          // (use_norm = False, bilateralNN.py:196: the plain sparse sum)
-    float4 *dst = splat + (int64_t)h * CH;
+    float4 *dst = splat + (int64_t)h * lds4;                           // (lds4 = CH for the splat; the slice's backward has its own row stride)
     dst[c] = make_float4(a0.x * nrm, a0.y * nrm, a0.z * nrm, a0.w * nrm);
     if (LPV == 64 && c + 64 < CH) dst[c + 64] = make_float4(a1.x * nrm, a1.y * nrm, a1.z * nrm, a1.w * nrm);
-    if (c == 0) wsum[h] = w;
+    if (wsum && c == 0) wsum[h] = w;
 }
 
 // backward of the splat w.r.t. the feature part of the rows (el_minus_gr carries no gradient, generate_data.py:119):
@@ -223,6 +224,177 @@ k_blur_dgrad_alias(const float *__restrict__ dy, int64_t ldy, int N, const float
     }
 }
 
+
+// ---- BCL slice (bilateralNN.py:251-263): lattice rows back onto points.  One thread per (point, 16-byte chunk): four C-wide rows
+// gathered, weighted in the order r = 0..3, then the bias.  An offset outside [0, H) contributes nothing (the reference would wrap
+// a -1 to the last vertex; efgh_offsets_invert counts such entries - here they are only kept from reading out of bounds).
+__global__ void __launch_bounds__(TPB)
+k_slice(const float4 *__restrict__ feat, int64_t ldf4, int H, const float4 *__restrict__ bary, const int4 *__restrict__ off, int n,
+        int c4, const float4 *__restrict__ bias, float4 *__restrict__ out, int64_t ldo4, int ooff4) {
+    const int64_t total = (int64_t)n * c4;
+    const int64_t nblocks = (total + TPB - 1) / TPB;
+    const int64_t blk = xcd_band_block(blockIdx.x, nblocks);
+    if (blk < 0) return;
+    const int64_t i = blk * TPB + threadIdx.x;
+    if (i >= total) return;
+    const int p = (int)(i / c4), c = (int)(i - (int64_t)p * c4);
+    const int4 o = off[p];
+    const float4 b = bary[p];
+    const int oo[4] = {o.x, o.y, o.z, o.w};
+    const float bb[4] = {b.x, b.y, b.z, b.w};
+    float4 v[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {                          // (the four row loads are independent: all in flight before the first FMA)
+        const bool ok = (unsigned)oo[r] < (unsigned)H;
+        v[r] = ok ? feat[(int64_t)oo[r] * ldf4 + c] : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) fma4(a, bb[r], v[r]);
+    if (bias) { const float4 bi = bias[c]; a.x += bi.x; a.y += bi.y; a.z += bi.z; a.w += bi.w; }
+    out[(int64_t)p * ldo4 + ooff4 + c] = a;
+}
+
+// ---- the inverse of an `off` array that did not come out of the lattice build (out points of the slice): vertex -> ascending list
+// of its flat positions f = 4p + r, in the build's own format.  Histogram (integer atomics), exclusive scan, scatter in arrival
+// order into a scratch list, then every entry is RANKED among the entries of its vertex (they are distinct) and stored at its
+// rank: the result does not depend on the arrival order.  Work of the last pass: sum over the vertices of (list length)^2
+// comparisons, spread over all entries (no long tail on one wave).
+constexpr int SCAN_ITEMS = 4, SCAN_TILE = TPB * SCAN_ITEMS;
+
+__global__ void __launch_bounds__(TPB)
+k_inv_hist(const int *__restrict__ off, int64_t nf, int H, int *__restrict__ count, int *__restrict__ err) {
+    const int64_t f = (int64_t)blockIdx.x * TPB + threadIdx.x;
+    if (f >= nf) return;
+    const int h = off[f];
+    if ((unsigned)h < (unsigned)H) atomicAdd(count + h, 1);
+    else atomicAdd(err, 1);
+}
+
+// exclusive scan of v over the block's TPB threads (wave shuffles, the four wave totals through LDS) -> (prefix, block total)
+__device__ __forceinline__ int block_excl_scan(int v, int *wtot, int &total) {
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    int inc = v;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const int t = __shfl_up(inc, o);
+        if (lane >= o) inc += t;
+    }
+    __syncthreads();                                // (wtot may still be read from a previous call)
+    if (lane == 63) wtot[wv] = inc;
+    __syncthreads();
+    int base = 0;
+    total = 0;
+#pragma unroll
+    for (int k = 0; k < TPB / 64; ++k) { if (k < wv) base += wtot[k]; total += wtot[k]; }
+    return base + inc - v;
+}
+
+// tile-local exclusive scan of the counts -> vseg (start within the tile, length); the tile's total -> tsum
+__global__ void __launch_bounds__(TPB)
+k_inv_scan_tiles(const int *__restrict__ count, int H, int2 *__restrict__ vseg, int *__restrict__ tsum) {
+    __shared__ int wtot[TPB / 64];
+    const int64_t h0 = (int64_t)blockIdx.x * SCAN_TILE + (int64_t)threadIdx.x * SCAN_ITEMS;
+    int cnt[SCAN_ITEMS], s = 0;
+#pragma unroll
+    for (int k = 0; k < SCAN_ITEMS; ++k) { cnt[k] = h0 + k < H ? count[h0 + k] : 0; s += cnt[k]; }
+    int total;
+    int pre = block_excl_scan(s, wtot, total);
+#pragma unroll
+    for (int k = 0; k < SCAN_ITEMS; ++k) {
+        if (h0 + k < H) vseg[h0 + k] = make_int2(pre, cnt[k]);
+        pre += cnt[k];
+    }
+    if (threadIdx.x == 0) tsum[blockIdx.x] = total;
+}
+
+// one block: exclusive scan of the tile totals in place
+__global__ void __launch_bounds__(TPB)
+k_inv_scan_totals(int *__restrict__ tsum, int ntiles) {
+    __shared__ int wtot[TPB / 64];
+    int carry = 0;
+    for (int base = 0; base < ntiles; base += TPB) {
+        const int i = base + threadIdx.x;
+        const int v = i < ntiles ? tsum[i] : 0;
+        int total;
+        const int pre = block_excl_scan(v, wtot, total);
+        if (i < ntiles) tsum[i] = carry + pre;
+        carry += total;
+    }
+}
+
+// vseg starts made global; the counts become the scatter's cursors (zero again)
+__global__ void __launch_bounds__(TPB)
+k_inv_scan_apply(int2 *__restrict__ vseg, int H, const int *__restrict__ tsum, int *__restrict__ count) {
+    const int64_t h = (int64_t)blockIdx.x * TPB + threadIdx.x;
+    if (h >= H) return;
+    vseg[h].x += tsum[h / SCAN_TILE];
+    count[h] = 0;
+}
+
+__global__ void __launch_bounds__(TPB)
+k_inv_scatter(const int *__restrict__ off, int64_t nf, int H, const int2 *__restrict__ vseg, int *__restrict__ cursor,
+              int *__restrict__ tmp) {
+    const int64_t f = (int64_t)blockIdx.x * TPB + threadIdx.x;
+    if (f >= nf) return;
+    const int h = off[f];
+    if ((unsigned)h >= (unsigned)H) return;
+    tmp[vseg[h].x + atomicAdd(cursor + h, 1)] = (int)f;          // (slot < length: the histogram counted the same entries)
+}
+
+__global__ void __launch_bounds__(TPB)
+k_inv_rank(const int *__restrict__ off, int64_t nf, int H, const int2 *__restrict__ vseg, const int *__restrict__ tmp,
+           int *__restrict__ list) {
+    const int64_t f = (int64_t)blockIdx.x * TPB + threadIdx.x;
+    if (f >= nf) return;
+    const int h = off[f];
+    if ((unsigned)h >= (unsigned)H) return;
+    const int2 seg = vseg[h];
+    int r = 0;
+    for (int j = 0; j < seg.y; ++j) r += tmp[seg.x + j] < (int)f ? 1 : 0;
+    list[seg.x + r] = (int)f;
+}
+
+// ---- bias gradient of the slice: column sums of gout's channel slice, a two-stage fold with a fixed tree (no atomics; a running
+// sum of a few thousand like-signed values drifts by far more than a tree's log2 n roundings).  Stage 1: block b sums the rows
+// [b*rows_per, (b+1)*rows_per): thread (row slot, chunk) takes every (TPB / c4)-th row of them in ascending order, the row slots are
+// folded pairwise in LDS.  Stage 2: one block per chunk folds the <= 4 TPB block partials: every TPB-th one per thread, then pairwise.
+__device__ __forceinline__ void add4(float4 &a, const float4 &v) { a.x += v.x; a.y += v.y; a.z += v.z; a.w += v.w; }
+
+__global__ void __launch_bounds__(TPB)
+k_colsum_part(const float4 *__restrict__ g, int64_t ld4, int off4, int n, int c4, int rows_per, float4 *__restrict__ part) {
+    __shared__ float4 sm[TPB];
+    const int slots = TPB / c4, sl = threadIdx.x / c4, c = threadIdx.x - sl * c4;
+    const int r0 = blockIdx.x * rows_per, r1 = min(n, r0 + rows_per);
+    float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (sl < slots)
+        for (int p = r0 + sl; p < r1; p += slots) add4(a, g[(int64_t)p * ld4 + off4 + c]);
+    sm[threadIdx.x] = a;
+    int half = 1;
+    while (half * 2 < slots) half *= 2;                 // (the largest power of two below the slot count; 0 rounds at slots == 1)
+    for (int s = half; s > 0 && slots > 1; s >>= 1) {
+        __syncthreads();
+        if (sl < s && sl + s < slots) { add4(a, sm[(sl + s) * c4 + c]); sm[threadIdx.x] = a; }
+    }
+    if (sl == 0) part[(int64_t)blockIdx.x * c4 + c] = a;
+}
+
+__global__ void __launch_bounds__(TPB)
+k_colsum_fold(const float4 *__restrict__ part, int nparts, int c4, float4 *__restrict__ dst) {
+    __shared__ float4 sm[TPB];
+    const int c = blockIdx.x, t = threadIdx.x;
+    float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int i = t; i < nparts; i += TPB) add4(a, part[(int64_t)i * c4 + c]);      // (<= COLSUM_PARTS / TPB terms)
+    sm[t] = a;
+    for (int s = TPB / 2; s > 0; s >>= 1) {
+        __syncthreads();
+        if (t < s) { add4(a, sm[t + s]); sm[t] = a; }
+    }
+    if (t == 0) dst[c] = a;
+}
+
+constexpr int COLSUM_PARTS = 4 * TPB;            // most stage-1 blocks of the bias gradient (efgh_slice_bwd_workspace)
+
 }  // namespace
 
 extern "C" int efgh_splat_gather(const float *emg, const float *feat, int64_t ldf, int32_t Cf, const float *bary,
@@ -242,13 +414,13 @@ extern "C" int efgh_splat_gather(const float *emg, const float *feat, int64_t ld
     const int64_t grid = (nblocks + 7) / 8 * 8;
     if (lpv == 16)
         k_splat_gather<16><<<(unsigned)grid, TPB, 0, st>>>((const float4 *)emg, (const float4 *)feat, ldf / 4, Cf / 4, bary, list,
-                                                           (const int2 *)vseg, H, (float4 *)splat, wsum, normalize);
+                                                           (const int2 *)vseg, H, (float4 *)splat, CH, wsum, normalize);
     else if (lpv == 32)
         k_splat_gather<32><<<(unsigned)grid, TPB, 0, st>>>((const float4 *)emg, (const float4 *)feat, ldf / 4, Cf / 4, bary, list,
-                                                           (const int2 *)vseg, H, (float4 *)splat, wsum, normalize);
+                                                           (const int2 *)vseg, H, (float4 *)splat, CH, wsum, normalize);
     else
         k_splat_gather<64><<<(unsigned)grid, TPB, 0, st>>>((const float4 *)emg, (const float4 *)feat, ldf / 4, Cf / 4, bary, list,
-                                                           (const int2 *)vseg, H, (float4 *)splat, wsum, normalize);
+                                                           (const int2 *)vseg, H, (float4 *)splat, CH, wsum, normalize);
     EFGH_CHECK_LAUNCH();
     return EFGH_OK;
 }
@@ -286,6 +458,97 @@ extern "C" int efgh_blur_dgrad_alias(const float *dy, int64_t ldy, int32_t N, co
     hipStream_t st = (hipStream_t)stream_;
     EFGH_CHECK_ARG(dy && w && alist && n_alias && dx && N > 0 && C > 0 && alias_cap > 0 && alias_cap <= ALIAS_LDS);
     k_blur_dgrad_alias<<<64, TPB, 0, st>>>(dy, ldy, N, w, C, (const int2 *)alist, n_alias, alias_cap, dx, ldx);
+    EFGH_CHECK_LAUNCH();
+    return EFGH_OK;
+}
+
+// ---- slice step of the BCL (bilateralNN.py:248-263): out[p][ooff + c] = sum_r bary[p][r] * feat[off[p][r]][c] (+ bias[c])
+extern "C" int efgh_slice(const float *feat, int64_t ldf, int32_t H, const float *bary, const int32_t *off, int32_t n_out, int32_t C,
+                          const float *bias, float *out, int64_t ldo, int32_t ooff, void *stream_) {
+    hipStream_t st = (hipStream_t)stream_;
+    EFGH_CHECK_ARG(feat && bary && off && out && H > 0 && n_out > 0 && C > 0 && C % 4 == 0 && ldf % 4 == 0 && ldf >= C &&
+                   ldo % 4 == 0 && ooff >= 0 && ooff % 4 == 0 && (int64_t)ooff + C <= ldo);
+    const int64_t nblocks = ((int64_t)n_out * (C / 4) + TPB - 1) / TPB;
+    const int64_t grid = (nblocks + 7) / 8 * 8;
+    EFGH_CHECK_ARG(grid < (1ll << 31));
+    k_slice<<<(unsigned)grid, TPB, 0, st>>>((const float4 *)feat, ldf / 4, H, (const float4 *)bary, (const int4 *)off, n_out, C / 4,
+                                            (const float4 *)bias, (float4 *)out, ldo / 4, ooff / 4);
+    EFGH_CHECK_LAUNCH();
+    return EFGH_OK;
+}
+
+static inline int64_t inv_align(int64_t b) { return (b + 255) / 256 * 256; }
+static inline int64_t inv_tiles(int64_t H) { return (H + SCAN_TILE - 1) / SCAN_TILE; }
+
+extern "C" int64_t efgh_offsets_invert_workspace(int32_t n_out, int32_t H) {
+    if (n_out <= 0 || H <= 0) return 0;
+    // counts / cursors [H], tile totals, the arrival-order list [4 n_out]
+    return inv_align(4ll * H) + inv_align(4ll * inv_tiles(H)) + inv_align(16ll * n_out);
+}
+
+// ---- inverse lists of an out-point set (the slice's backward walks them): what the lattice build leaves for its own points
+// (lattice.hip: list, vseg), rebuilt from `off` alone
+extern "C" int efgh_offsets_invert(const int32_t *off, int32_t n_out, int32_t H, int32_t *vseg, int32_t *list, int32_t *err,
+                                   void *workspace, void *stream_) {
+    hipStream_t st = (hipStream_t)stream_;
+    EFGH_CHECK_ARG(off && vseg && list && err && workspace && n_out > 0 && H > 0 && n_out <= (1 << 29) &&
+                   ((uintptr_t)workspace & 255) == 0);
+    const int64_t nf = 4ll * n_out;
+    const int ntiles = (int)inv_tiles(H);
+    char *ws = (char *)workspace;
+    int *count = (int *)ws;
+    int *tsum = (int *)(ws + inv_align(4ll * H));
+    int *tmp = (int *)(ws + inv_align(4ll * H) + inv_align(4ll * ntiles));
+    if (hipMemsetAsync(count, 0, 4ll * H, st) != hipSuccess || hipMemsetAsync(err, 0, 4, st) != hipSuccess) {
+        efgh_set_error("%s:%d: hipMemsetAsync failed", __FILE__, __LINE__);
+        return EFGH_E_LAUNCH;
+    }
+    const unsigned gf = (unsigned)((nf + TPB - 1) / TPB), gh = (unsigned)(((int64_t)H + TPB - 1) / TPB);
+    k_inv_hist<<<gf, TPB, 0, st>>>(off, nf, H, count, err);
+    k_inv_scan_tiles<<<(unsigned)ntiles, TPB, 0, st>>>(count, H, (int2 *)vseg, tsum);
+    k_inv_scan_totals<<<1, TPB, 0, st>>>(tsum, ntiles);
+    k_inv_scan_apply<<<gh, TPB, 0, st>>>((int2 *)vseg, H, tsum, count);
+    k_inv_scatter<<<gf, TPB, 0, st>>>(off, nf, H, (const int2 *)vseg, count, tmp);
+    k_inv_rank<<<gf, TPB, 0, st>>>(off, nf, H, (const int2 *)vseg, tmp, list);
+    EFGH_CHECK_LAUNCH();
+    return EFGH_OK;
+}
+
+extern "C" int64_t efgh_slice_bwd_workspace(int32_t C) { return C > 0 ? 4ll * COLSUM_PARTS * C : 0; }
+
+// ---- backward of the slice w.r.t. the lattice rows (autograd of bilateralNN.py:251-257) as a gather over the vertex lists of the
+// out points, and w.r.t. the bias (:260-261): k_splat_gather without el_minus_gr and without the density factor
+extern "C" int efgh_slice_bwd(const float *gout, int64_t ldo, int32_t ooff, int32_t C, const float *bary, const int32_t *list,
+                              const int32_t *vseg, int32_t H, int32_t n_out, int32_t lanes_per_vertex, float *gfeat, int64_t ldg,
+                              float *gbias, void *workspace, void *stream_) {
+    hipStream_t st = (hipStream_t)stream_;
+    EFGH_CHECK_ARG(gout && bary && list && vseg && gfeat && H > 0 && n_out > 0 && C > 0 && C % 4 == 0 && C <= 508 && ldo % 4 == 0 &&
+                   ooff >= 0 && ooff % 4 == 0 && (int64_t)ooff + C <= ldo && ldg % 4 == 0 && ldg >= C && (!gbias || workspace));
+    const int CH = C / 4;
+    const int avg_len = (int)std::max<int64_t>(1, 4ll * n_out / H);
+    int lpv = lanes_per_vertex;
+    if (lpv == 0) lpv = (CH <= 32 && avg_len <= 32) ? 32 : 64;          // (the splat's rule, efgh_splat_gather)
+    EFGH_CHECK_ARG(lpv == 64 || (lpv == 32 && CH <= 32) || (lpv == 16 && CH <= 16));
+    const int vpb = TPB / lpv;
+    const int64_t nblocks = ((int64_t)H + vpb - 1) / vpb;
+    const int64_t grid = (nblocks + 7) / 8 * 8;
+    EFGH_CHECK_ARG(grid < (1ll << 31));
+    const float4 *rows = (const float4 *)(gout + ooff);
+    if (lpv == 16)
+        k_splat_gather<16><<<(unsigned)grid, TPB, 0, st>>>(nullptr, rows, ldo / 4, CH, bary, list, (const int2 *)vseg, H,
+                                                           (float4 *)gfeat, ldg / 4, nullptr, 0);
+    else if (lpv == 32)
+        k_splat_gather<32><<<(unsigned)grid, TPB, 0, st>>>(nullptr, rows, ldo / 4, CH, bary, list, (const int2 *)vseg, H,
+                                                           (float4 *)gfeat, ldg / 4, nullptr, 0);
+    else
+        k_splat_gather<64><<<(unsigned)grid, TPB, 0, st>>>(nullptr, rows, ldo / 4, CH, bary, list, (const int2 *)vseg, H,
+                                                           (float4 *)gfeat, ldg / 4, nullptr, 0);
+    if (gbias) {
+        const int rows_per = (n_out + COLSUM_PARTS - 1) / COLSUM_PARTS;
+        const int nparts = (n_out + rows_per - 1) / rows_per;
+        k_colsum_part<<<(unsigned)nparts, TPB, 0, st>>>((const float4 *)gout, ldo / 4, ooff / 4, n_out, CH, rows_per, (float4 *)workspace);
+        k_colsum_fold<<<(unsigned)CH, TPB, 0, st>>>((const float4 *)workspace, nparts, CH, (float4 *)gbias);
+    }
     EFGH_CHECK_LAUNCH();
     return EFGH_OK;
 }

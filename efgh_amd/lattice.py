@@ -146,6 +146,52 @@ class _SampleView:
 
 
 
+class OutPoints:
+    """where the slice step of a BCL puts lattice features (bilateralNN.py:251-257 out_barycentric / out_lattice_offset): bary
+    [n_out][4] float32 and off [n_out][4] int32, point-major like LatticeLevel.bary_pm / off_pm, off in GLOBAL row indices of the
+    level's [H]-row arrays (sample-major).  The inverse of off (vseg, list: what the slice's backward walks) is built on first
+    use; that is also the one time the count of offsets outside [0, H) is read, and a nonzero count raises EfghError."""
+    __slots__ = ('n_out', 'H', 'bary', 'off', '_vseg', '_list')
+
+    def __init__(self, bary, off, H, vseg=None, lst=None):
+        _C.require_cuda(bary, off)
+        if bary.dtype != torch.float32 or off.dtype != torch.int32 or bary.dim() != 2 or bary.shape[1] != 4 or \
+                tuple(off.shape) != tuple(bary.shape) or bary.shape[0] < 1 or int(H) < 1:
+            raise _C.EfghError('OutPoints: bary [n_out][4] float32 and off [n_out][4] int32 of one shape, n_out >= 1, H >= 1 expected, '
+                               'got %s %s / %s %s' % (tuple(bary.shape), bary.dtype, tuple(off.shape), off.dtype))
+        self.bary, self.off = bary.contiguous(), off.contiguous()
+        self.n_out, self.H = int(bary.shape[0]), int(H)
+        self._vseg, self._list = vseg, lst
+
+    @classmethod
+    def of_level(cls, lv):
+        """the level's own points: its arrays as they are, the build's own vseg / list - nothing is launched"""
+        if lv.off_pm is None:
+            raise _C.EfghError('this lattice was built with need_off=False (inference): lattice_offset was not produced')
+        return cls(lv.bary_pm[:lv.n_in], lv.off_pm[:lv.n_in], lv.H, lv.vseg, lv.list)
+
+    @classmethod
+    def select(cls, lv, idx):
+        """rows idx (int tensor, any order, repetition allowed) of the level's points: a subset or another ordering without a
+        lattice query"""
+        if lv.off_pm is None:
+            raise _C.EfghError('this lattice was built with need_off=False (inference): lattice_offset was not produced')
+        idx = torch.as_tensor(idx, device=lv.bary_pm.device).long().reshape(-1)
+        return cls(lv.bary_pm[:lv.n_in].index_select(0, idx), lv.off_pm[:lv.n_in].index_select(0, idx), lv.H)
+
+    def lists(self):
+        """(vseg [H][2], list): every vertex's flat positions 4p + r into these out points, ascending"""
+        if self._vseg is None:
+            from . import ops
+            vseg, lst, err = ops.offsets_invert(self.off, self.H)
+            bad = int(err.item())                  # the one read of the error word
+            if bad:
+                raise _C.EfghError('OutPoints: %d lattice offsets outside [0, %d) (the reference would wrap a -1 to the last vertex; '
+                                   'here that is an error)' % (bad, self.H))
+            self._vseg, self._list = vseg, lst
+        return self._vseg, self._list
+
+
 def _pow2ceil(v):
     return 1 << max(0, int(v) - 1).bit_length()
 

@@ -23,17 +23,15 @@ class Enet(nn.Module):
         # the reference's E-net switches (enet.py:25-83 -> net_utils.py:6-11, bilateralNN.py:121-135,196): the shipped configurations
         # set use_leaky / bcn_use_norm and clear last_relu (configs/train_rellis.yaml:8-12); the other values are honoured as well
         self.use_leaky, self.use_norm, self.last_relu = bool(args['use_leaky']), bool(args['bcn_use_norm']), bool(args['last_relu'])
-        if not args.get('bcn_use_bias', True):
-            # (use_bias only adds a parameter behind the SLICE step, which enet.py:37-81 never enables: do_slice=False)
-            pass
+        ub = bool(args.get('bcn_use_bias', True))
         self.device = args['DEVICE']
         self.conv_in = nn.Sequential(conv_1x1(dim, 32, True), conv_1x1(32, 32, True), conv_1x1(32, 32, True))
         rr = self.radii
-        self.bcn1 = BilateralConvFlex(32 + dim + 1, [32, 32], rr[0])          # enet.py:30-83
-        self.bcn2 = BilateralConvFlex(32 + dim + 1, [64, 64], rr[1])
-        self.bcn3 = BilateralConvFlex(64 + dim + 1, [128, 128], rr[2])
-        self.bcn4 = BilateralConvFlex(128 + dim + 1, [256, 256], rr[3])
-        self.bcn5 = BilateralConvFlex(256 + dim + 1, [256, 256], rr[4])
+        self.bcn1 = BilateralConvFlex(32 + dim + 1, [32, 32], rr[0], use_bias=ub)          # enet.py:30-83
+        self.bcn2 = BilateralConvFlex(32 + dim + 1, [64, 64], rr[1], use_bias=ub)
+        self.bcn3 = BilateralConvFlex(64 + dim + 1, [128, 128], rr[2], use_bias=ub)
+        self.bcn4 = BilateralConvFlex(128 + dim + 1, [256, 256], rr[3], use_bias=ub)
+        self.bcn5 = BilateralConvFlex(256 + dim + 1, [256, 256], rr[4], use_bias=ub)
         self.conv_gn_1 = nn.Conv1d(256, 128, 1)
         self.conv_gn_2 = nn.Conv1d(128, 128, 1)
         self.conv_gn_3 = nn.Conv1d(128, 128, 1)

@@ -565,6 +565,25 @@ class SplatFn(torch.autograd.Function):
         return gfeat, None, None, None, None
 
 
+class SliceFn(torch.autograd.Function):
+    """slice step of a BCL (bilateralNN.py:248-263) onto `pts` (lattice.OutPoints): rows [H][ld] -> [n_out][C], plus the bias;
+    bary / off carry no gradient (generate_data.py:119)."""
+
+    @staticmethod
+    def forward(ctx, feat, bias, pts, C):
+        feat = as_rows(feat)
+        ctx.meta = (pts, C, feat.shape[-1], bias)
+        return ops.slice_fwd(pts, feat, C, None if bias is None else bias.detach())
+
+    @staticmethod
+    def backward(ctx, g):
+        pts, C, ldf, bias = ctx.meta
+        want_b = bias is not None and ctx.needs_input_grad[1]
+        gfeat = torch.zeros((pts.H, ldf), dtype=torch.float32, device=g.device) if ldf != C else None
+        gfeat, gbias = ops.slice_bwd(pts, as_rows(g), C, 0, want_b, gfeat)
+        return (gfeat if ctx.needs_input_grad[0] else None), gbias, None, None
+
+
 class Softmax2ToNchwFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x):

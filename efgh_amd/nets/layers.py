@@ -10,7 +10,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from .. import ops
+from .. import lattice, ops
 from ..ops import ACT_LEAKY, ACT_NONE, ACT_RELU, ceil4
 from . import fn as FN
 
@@ -350,10 +350,9 @@ def linear_rows(ctx, x, M, C, weight, bias, bn=None, act=ACT_NONE, slope=0.0, ou
     return out_t
 
 
-def blur_conv(ctx, splat, H, C, table, conv0, conv1, out=None, last_act=ACT_NONE, last_slope=0.0):
-    """BCL blur: gather 15 neighbour rows + Conv2d(C,C0,(15,1)) + ReLU + Conv2d(C0,C1,1)
-    (nets/bilateralNN.py:240-246).  splat [H][C]; `table` = the lattice level (efgh_amd.lattice.LatticeLevel: its neighbour
-    table also serves the adjoint of the gather) or a bare [H][16] neighbour table -> [H][ld]."""
+def _blur_first(ctx, splat, H, C, table, conv0, act=ACT_RELU, slope=0.0):
+    """the first convolution of a BCL's blur stack: gather F neighbour rows + Conv2d(C, C0, (F, 1)) + activation
+    (nets/bilateralNN.py:240-244).  splat [H][C]; `table` = the lattice level or a bare [H][16] neighbour table -> [H][C0]."""
     C0 = conv0.out_channels
     lv = table if hasattr(table, 'nbr') else None
     if lv is not None:
@@ -364,18 +363,71 @@ def blur_conv(ctx, splat, H, C, table, conv0, conv1, out=None, last_act=ACT_NONE
         if conv0.kernel_size != (lv.F, 1):
             raise ops._C.EfghError('BCL blur weight %s does not match the radius-%d lattice level (F = %d taps)'
                                    % (tuple(conv0.weight.shape), lv.radius, lv.F))
-        spec = FN.LayerSpec(C0, C, lv.F, ops.MODE_BLUR_R, [(None, H)], [ops.BlurRLayout()], H, (H,), act=ACT_RELU, table=table)
+        spec = FN.LayerSpec(C0, C, lv.F, ops.MODE_BLUR_R, [(None, H)], [ops.BlurRLayout()], H, (H,), act=act, slope=slope, table=table)
     else:
         lay = ops.WeightLayout(C0, 15, C, C * 15, 15, 1, list(range(15)), key=('blur0',))
-        spec = FN.LayerSpec(C0, C, 15, 2, [(None, H)], [lay], H, (H,), act=ACT_RELU, table=table)
+        spec = FN.LayerSpec(C0, C, 15, 2, [(None, H)], [lay], H, (H,), act=act, slope=slope, table=table)
     if ctx.grad:
-        assert out is None
-        mid = _apply(spec.for_tape(_blur_dgrad(lv, table, H, C, C0)), splat, conv0.weight, conv0.bias)
+        return _apply(spec.for_tape(_blur_dgrad(lv, table, H, C, C0)), splat, conv0.weight, conv0.bias)
+    assert C0 % 4 == 0
+    mid = torch.empty((H, C0), dtype=torch.float32, device=splat.device)
+    _run(ctx, spec, splat, FN.ld_of(splat), conv0.weight, conv0.bias, mid, C0, 0)      # (rows may be a column slice of wider rows)
+    return mid
+
+
+def blur_conv(ctx, splat, H, C, table, conv0, conv1, out=None, last_act=ACT_NONE, last_slope=0.0):
+    """BCL blur: gather 15 neighbour rows + Conv2d(C,C0,(15,1)) + ReLU + Conv2d(C0,C1,1)
+    (nets/bilateralNN.py:240-246).  splat [H][C]; `table` = the lattice level (efgh_amd.lattice.LatticeLevel: its neighbour
+    table also serves the adjoint of the gather) or a bare [H][16] neighbour table -> [H][ld]."""
+    assert out is None or not ctx.grad
+    mid = _blur_first(ctx, splat, H, C, table, conv0)
+    return linear_rows(ctx, mid, H, conv0.out_channels, conv1.weight, conv1.bias, out=out, act=last_act, slope=last_slope)   # (last_relu, bilateralNN.py:121-135)
+
+
+def bilateral_conv(ctx, module, feat_rows, lv, out_points=None):
+    """the whole BilateralConvFlex layer (nets/bilateralNN.py:148-263) of `module` (builders.BilateralConvFlex) on one lattice level.
+    feat_rows: [n_in][num_input] point rows (do_splat) or [H][num_input] lattice rows (do_splat=False, :215-221; a missing
+    neighbour reads zeros, the reference's zero row); all samples of a batch in one array, sample-major as the level's own arrays.
+    Splat (:176-211, no el_minus_gr channels, density normalisation by module.use_norm), the blur stack (:240-246: the (F,1)
+    convolution through the level's neighbour table, every later (1,1) convolution as a row GEMM, ReLU between, the last_relu /
+    use_leaky activation behind the last), then the slice (:248-263) onto out_points (lattice.OutPoints; None = the level's own
+    points) with the bias.  -> [n_out][C_last] (do_slice) or [H][C_last]."""
+    E = ops._C.EfghError
+    ops._C.require_cuda(feat_rows)
+    ops._C.require_f32(feat_rows)
+    C = module.num_input
+    if module.neighborhood_size != lv.radius:
+        raise E('BilateralConvFlex of radius %d on a lattice level built with radius %d' % (module.neighborhood_size, lv.radius))
+    rows = lv.n_in if module.do_splat else lv.H
+    if feat_rows.dim() != 2 or feat_rows.shape[0] != rows or feat_rows.shape[1] != C:
+        raise E('BilateralConvFlex: features [%d][%d] (%s rows, channels last) expected, got %s'
+                % (rows, C, 'point' if module.do_splat else 'lattice', tuple(feat_rows.shape)))
+    H = lv.H
+    if module.do_splat:
+        if ctx.grad:
+            cur = FN.SplatFn.apply(feat_rows, lv, C, False, module.use_norm)
+        else:
+            cur, _ = ops.splat_fwd(lv, FN.as_rows(feat_rows), C, use_emg=False, normalize=module.use_norm)
     else:
-        assert C0 % 4 == 0
-        mid = torch.empty((H, C0), dtype=torch.float32, device=splat.device)
-        _run(ctx, spec, splat, C, conv0.weight, conv0.bias, mid, C0, 0)
-    return linear_rows(ctx, mid, H, C0, conv1.weight, conv1.bias, out=out, act=last_act, slope=last_slope)   # (last_relu, bilateralNN.py:121-135)
+        cur = FN.as_rows(feat_rows)
+    convs = [m for m in module.blur_conv if isinstance(m, nn.Conv2d)]
+    last = (ACT_LEAKY if module.use_leaky else ACT_RELU) if module.last_relu else ACT_NONE
+    last_slope = 0.1 if (module.last_relu and module.use_leaky) else 0.0
+    for i, conv in enumerate(convs):
+        act, slope = (last, last_slope) if i == len(convs) - 1 else (ACT_RELU, 0.0)
+        if i == 0:
+            cur = _blur_first(ctx, cur, H, C, lv, conv, act, slope)
+        else:
+            cur = linear_rows(ctx, cur, H, conv.in_channels, conv.weight, conv.bias, act=act, slope=slope)
+    if not module.do_slice:
+        return cur
+    pts = out_points if out_points is not None else lattice.OutPoints.of_level(lv)
+    if pts.H != H:
+        raise E('BilateralConvFlex: out points of a %d-vertex lattice on a level of %d vertices' % (pts.H, H))
+    bias = module.bias if module.use_bias else None
+    if ctx.grad:
+        return FN.SliceFn.apply(cur, bias, pts, convs[-1].out_channels)
+    return ops.slice_fwd(pts, cur, convs[-1].out_channels, None if bias is None else bias.detach())
 
 
 def _blur_dgrad(lv, table, H, C, C0):

@@ -1113,6 +1113,87 @@ def neighbor_gather_adjoint(lv, src, C):
     return dst
 
 
+# ----------------------------------------------------------------------------------------------
+# BCL slice (bilateralNN.py:248-263): lattice rows back onto points.  `pts` is a lattice.OutPoints
+# ----------------------------------------------------------------------------------------------
+def _slice_bytes(n_out, H, C):
+    """algorithmic bytes of a slice pass, forward or backward: per out point its bary + off (32) or bary + four list entries, four
+    C-wide lattice rows gathered (forward) / one point row per list entry (backward: 4 n_out row reads as well), one row written
+    per point (forward) / per vertex (backward) + its vseg - the splat's model with the two sides exchanged"""
+    return float(n_out) * (4 * C + 48) + float(H) * (4 * C + 8)
+
+
+def slice_fwd(pts, feat, C, bias=None, out=None):
+    """out[p][ooff + c] = sum_r bary[p][r] * feat[off[p][r]][c] (+ bias[c]): feat [H][ld] lattice rows (as layers.blur_conv leaves
+    them), C channels -> [n_out][C], or into columns [ooff, ooff + C) of `out` = (buffer [n_out][ldo], ooff); the other columns
+    are not touched"""
+    _C.require_cuda(feat, bias)
+    _C.require_f32(feat, bias)
+    if feat.dim() != 2 or feat.shape[0] < pts.H or feat.stride(1) != 1 or feat.stride(0) % 4 or C % 4 or C <= 0 or feat.shape[1] < C:
+        raise _C.EfghError('slice: lattice rows [>= %d][>= %d] float32 with a row stride that is a multiple of 4 expected, got %s'
+                           % (pts.H, C, tuple(feat.shape)))
+    if bias is not None and (bias.numel() != C or not bias.is_contiguous()):
+        raise _C.EfghError('slice: bias of %d values expected, got %s' % (C, tuple(bias.shape)))
+    if out is None:
+        buf, ooff = torch.empty((pts.n_out, C), dtype=torch.float32, device=feat.device), 0
+    else:
+        buf, ooff = out
+        if buf.dim() != 2 or buf.shape[0] < pts.n_out or buf.stride(1) != 1 or buf.stride(0) % 4 or ooff % 4 or ooff < 0 or \
+                ooff + C > buf.shape[1] or buf.dtype != torch.float32 or not buf.is_cuda:
+            raise _C.EfghError('slice: out = ([>= %d][ldo] float32 buffer, column offset) with %d columns from a multiple of 4 expected'
+                               % (pts.n_out, C))
+    with _bcl_prof('slice', _slice_bytes(pts.n_out, pts.H, C)):
+        _C.check(_L().efgh_slice(ptr(feat), c_int64(feat.stride(0)), c_int32(pts.H), ptr(pts.bary), ptr(pts.off), c_int32(pts.n_out),
+                                 c_int32(C), ptr(bias), ptr(buf), c_int64(buf.stride(0)), c_int32(ooff), _st()))
+    return buf
+
+
+def offsets_invert(off, H):
+    """off [n_out][4] int32 (rows of a [H]-row lattice array) -> (vseg [H][2], list [4 n_out], err [1]): every vertex's flat
+    positions f = 4p + r, ascending, in the lattice build's format; err counts the entries outside [0, H) (left out).  All on the
+    device - the caller reads err (lattice.OutPoints does, once)"""
+    _C.require_cuda(off)
+    if off.dtype != torch.int32 or off.dim() != 2 or off.shape[1] != 4 or not off.is_contiguous() or off.shape[0] < 1 or H < 1:
+        raise _C.EfghError('offsets_invert: off [n_out >= 1][4] int32, contiguous, and H >= 1 expected, got %s %s' % (tuple(off.shape), off.dtype))
+    n_out, dev = off.shape[0], off.device
+    L = _L()
+    vseg = torch.empty((H, 2), dtype=torch.int32, device=dev)
+    lst = torch.empty(4 * n_out, dtype=torch.int32, device=dev)
+    err = torch.empty(1, dtype=torch.int32, device=dev)
+    ws = torch.empty(L.efgh_offsets_invert_workspace(c_int32(n_out), c_int32(H)), dtype=torch.uint8, device=dev)
+    with _bcl_prof('offsets invert', float(n_out) * 16 * 5 + float(H) * 24):      # off x3, scratch list w + r, list w; counts, vseg
+        _C.check(L.efgh_offsets_invert(ptr(off), c_int32(n_out), c_int32(H), ptr(vseg), ptr(lst), ptr(err), ptr(ws), _st()))
+    return vseg, lst, err
+
+
+def slice_bwd(pts, gout, C, ooff=0, want_bias=False, gfeat=None):
+    """backward of slice_fwd: gout [n_out][ldo] (its columns [ooff, ooff + C)) -> gfeat [H][C] (or into the given [H][>= C] buffer;
+    every row is written, zeros where no out point touches the vertex), and the bias gradient [C] when want_bias"""
+    _C.require_cuda(gout)
+    _C.require_f32(gout)
+    if gout.dim() != 2 or gout.shape[0] < pts.n_out or gout.stride(1) != 1 or gout.stride(0) % 4 or C % 4 or ooff % 4 or \
+            ooff < 0 or ooff + C > gout.shape[1]:
+        raise _C.EfghError('slice_bwd: gradient rows [>= %d][ldo] with %d columns from column %d expected, got %s'
+                           % (pts.n_out, C, ooff, tuple(gout.shape)))
+    vseg, lst = pts.lists()
+    dev = gout.device
+    if gfeat is None:
+        gfeat = torch.empty((pts.H, C), dtype=torch.float32, device=dev)
+    if not gfeat.is_cuda or gfeat.dtype != torch.float32 or gfeat.dim() != 2 or gfeat.shape[0] < pts.H or gfeat.stride(1) != 1 or \
+            gfeat.stride(0) % 4 or gfeat.shape[1] < C:
+        raise _C.EfghError('slice_bwd: gfeat = a [>= %d][>= %d] float32 GPU buffer with a row stride that is a multiple of 4 expected, got %s %s'
+                           % (pts.H, C, tuple(gfeat.shape), gfeat.dtype))
+    gbias = ws = None
+    if want_bias:
+        gbias = torch.empty(C, dtype=torch.float32, device=dev)
+        ws = torch.empty(_L().efgh_slice_bwd_workspace(c_int32(C)), dtype=torch.uint8, device=dev)
+    with _bcl_prof('slice bwd', _slice_bytes(pts.n_out, pts.H, C) + (4.0 * C * pts.n_out if want_bias else 0.0)):
+        _C.check(_L().efgh_slice_bwd(ptr(gout), c_int64(gout.stride(0)), c_int32(ooff), c_int32(C), ptr(pts.bary), ptr(lst), ptr(vseg),
+                                     c_int32(pts.H), c_int32(pts.n_out), c_int32(SPLAT_LANES), ptr(gfeat), c_int64(gfeat.stride(0)),
+                                     ptr(gbias), ptr(ws), _st()))
+    return gfeat, gbias
+
+
 # BatchNorm-backward column sums in the epilogue of the Winograd dgrad that produces dy (saves the reduction pass's read of dy).
 # OPT-IN: measured on a batch-8 training step it LOSES 6 ms (313.8 vs 307.8 ms, same box, alternating runs): the epilogue's 64
 # extra 4-byte loads per thread of the producer's raw output sit at the end of the kernel, behind the MFMA loop, and cost

@@ -52,7 +52,9 @@ const char *efgh_last_error(void);
  *      efgh_plane_wgrad_x6_batched (the plane GEMMs with a three-way bf16 split: fp32 'high' matmul precision). */
 /*   4  the one-launch tail of the lattice pyramid (round 5: its build entry point, its two size queries efgh_lattice_tail_max_points /
  *      efgh_lattice_tail_lds_bytes and its two descriptor structs) is removed: it was slower than the per-level entry points at every
- *      batch size and nothing called it.  Nothing else changed. */
+ *      batch size and nothing called it.  Nothing else changed.
+ *      Added later WITHOUT moving the number (no existing signature or struct changed): efgh_slice, efgh_slice_bwd,
+ *      efgh_slice_bwd_workspace, efgh_offsets_invert, efgh_offsets_invert_workspace (the slice step of the BCL). */
 #define EFGH_ABI_VERSION 4
 int efgh_version(void);
 
@@ -181,6 +183,36 @@ int efgh_table_gather_transposed(const float *src, const int32_t *nbr, int32_t H
  * [N][C][15] (bilateralNN.py:107).  Records are applied in a fixed order (sorted, one owner block per target): no atomics. */
 int efgh_blur_dgrad_alias(const float *dy, int64_t ldy, int32_t N, const float *w, int32_t C, const int32_t *alist,
                           const int32_t *n_alias, int32_t alias_cap, float *dx, int64_t ldx, void *stream);
+
+/* ------------------------------------------------------------------ BCL slice --------------
+ * replaces the slice step of BilateralConvFlex.forward, nets/bilateralNN.py:248-263 (do_slice, out_barycentric,
+ * out_lattice_offset, bias): lattice rows back onto points,
+ *     out[p*ldo + ooff + c] = sum_{r<4} bary[p][r] * feat[off[p][r]*ldf + c] (+ bias[c]),  p < n_out, c < C,
+ * products added in the order r = 0..3, then the bias (NULL: none).  feat [H][ldf] as the blur leaves it; off [n_out][4] indexes
+ * its rows directly (no +1 row, :251-253); bary [n_out][4].  ldo / ooff: the result lands in columns [ooff, ooff + C) of rows of
+ * ldo floats, the other columns are not touched.  C, ldf, ldo, ooff: multiples of 4.  An offset outside [0, H) contributes
+ * nothing and reads nothing (a caller error that efgh_offsets_invert counts).                                                */
+int efgh_slice(const float *feat, int64_t ldf, int32_t H, const float *bary, const int32_t *off, int32_t n_out, int32_t C,
+               const float *bias, float *out, int64_t ldo, int32_t ooff, void *stream);
+/* The inverse of `off` in the lattice build's own format (efgh_lattice_level_build: vseg, list), for out points that are not the
+ * points that built the lattice: vseg [H][2] (start, length), list [4*n_out] the flat positions f = 4*p + r of every vertex,
+ * ASCENDING within a vertex whatever order the entries arrived in (integer atomics serve the histogram only); a vertex no point
+ * touches gets length 0.  Entries outside [0, H) are left out and counted in *err (device, overwritten) - in the reference an
+ * index of -1 would wrap to the last vertex (:251-253).  workspace: efgh_offsets_invert_workspace(n_out, H) bytes, 256-byte
+ * aligned.  When the out points are the level's own points the build's list / vseg serve and this is not needed.            */
+int64_t efgh_offsets_invert_workspace(int32_t n_out, int32_t H);
+int efgh_offsets_invert(const int32_t *off, int32_t n_out, int32_t H, int32_t *vseg, int32_t *list, int32_t *err,
+                        void *workspace, void *stream);
+/* backward of efgh_slice (autograd of :251-261) without floating-point atomics:
+ *     gfeat[h*ldg + c] = sum over the list of h of bary[f] * gout[(f >> 2)*ldo + ooff + c]   (every row h < H is written: zeros
+ *                        for an empty list), the list walk of efgh_splat_gather (same lanes_per_vertex rule, 0 = chosen from
+ *                        4*n_out / H; a given mapping is bit-reproducible), C <= 508;
+ *     gbias[c] = sum_{p < n_out} gout[p*ldo + ooff + c]   (gbias NULL: not wanted) - block partials over fixed row ranges in
+ *                        `workspace` (efgh_slice_bwd_workspace(C) bytes), folded by a fixed pairwise tree.                              */
+int64_t efgh_slice_bwd_workspace(int32_t C);
+int efgh_slice_bwd(const float *gout, int64_t ldo, int32_t ooff, int32_t C, const float *bary, const int32_t *list,
+                   const int32_t *vseg, int32_t H, int32_t n_out, int32_t lanes_per_vertex, float *gfeat, int64_t ldg,
+                   float *gbias, void *workspace, void *stream);
 
 /* ------------------------------------------------------------------ gather-GEMM (K4,K6,K8) -
  * One implicit-GEMM kernel family on fp32 MFMA (v_mfma_f32_32x32x2_f32):
