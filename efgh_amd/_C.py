@@ -93,6 +93,8 @@ def lib():
         _lib.efgh_lattice_part_workspace_bytes.argtypes = [c_int32, c_int32, c_int32, c_int32, c_int32]
         _lib.efgh_lattice_neighbors_r_workspace.restype = c_int64
         _lib.efgh_lattice_neighbors_r_workspace.argtypes = [c_int32, c_int32]
+        _lib.efgh_lattice_index_bytes.restype = c_int64
+        _lib.efgh_lattice_index_bytes.argtypes = [c_int32, c_int32]
         _lib.efgh_offsets_invert_workspace.restype = c_int64
         _lib.efgh_offsets_invert_workspace.argtypes = [c_int32, c_int32]
         _lib.efgh_slice_bwd_workspace.restype = c_int64

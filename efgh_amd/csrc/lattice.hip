@@ -737,6 +737,69 @@ k_rn_probe(const int4 *__restrict__ vkeys, const int *__restrict__ mm, const int
     }
 }
 
+// ---- point query of a finished level through the same table (efgh_lattice_locate): one thread per query point, point_keys once,
+// four independent probe chains (the table's load is <= 1/2: a chain is one or two L2 / HBM reads, and the four of a thread are in
+// flight together), bary as one float4 store and the four vertex rows as one int4 store.  A corner is ABSENT (-1) when a coordinate
+// of its key lies outside its sample's key box - decided BEFORE the key integer is formed: key2int has no range check and a key
+// outside the box can carry the key integer of a real vertex (the alias masks of the neighbour tables exist for that) - or when its
+// probe chain ends on an empty slot.  counters[0] += absent corners, counters[1] += points without any corner: ballots, one integer
+// atomic per wave and counter (exact, order-independent).
+__global__ void __launch_bounds__(TPB)
+k_locate(const float *__restrict__ q, int64_t cstride, const int *__restrict__ qsid, int qpps, int n_q, float scale32, float std32,
+         const unsigned long long *__restrict__ hkeys, const int *__restrict__ hvals, int64_t hmask, const int *__restrict__ mm,
+         int nsamples, const int *__restrict__ info, int h_cap, float4 *__restrict__ bary, int4 *__restrict__ off,
+         int *__restrict__ counters) {
+    int H = info[EFGH_LATTICE_INFO_H];
+    if (H > h_cap) H = h_cap;
+    const int64_t p = (int64_t)blockIdx.x * TPB + threadIdx.x;
+    const bool ok = p < n_q;
+    int res[4] = {-1, -1, -1, -1};
+    if (ok) {
+        PointKeys pk;
+        point_keys(q[p], q[cstride + p], q[2 * cstride + p], scale32, std32, pk);
+        bary[p] = make_float4(pk.bary[0], pk.bary[1], pk.bary[2], pk.bary[3]);
+        const int b = qsid ? qsid[p] : (int)(p / qpps);
+        if (b >= 0 && b < nsamples) {                        // (a sample the level does not have: every corner absent)
+            const int *m8 = mm + 8 * b;
+            uint64_t s[4];
+            unsigned long long ki[4];
+            bool live[4];
+#pragma unroll
+            for (int rem = 0; rem < 4; ++rem) {
+                int k[4];
+                entry_key(pk, rem, k);
+                live[rem] = k[0] >= m8[0] && k[0] <= m8[4] && k[1] >= m8[1] && k[1] <= m8[5] && k[2] >= m8[2] && k[2] <= m8[6] &&
+                            k[3] >= m8[3] && k[3] <= m8[7];
+                ki[rem] = live[rem] ? (unsigned long long)(key2int(k, m8) * nsamples + b) : 0ULL;      // (inside the box: >= 0)
+                s[rem] = mix64(ki[rem]) & (uint64_t)hmask;
+            }
+            for (int64_t probe = 0; probe <= hmask && (live[0] || live[1] || live[2] || live[3]); ++probe) {
+                unsigned long long cur[4];
+#pragma unroll
+                for (int rem = 0; rem < 4; ++rem) cur[rem] = live[rem] ? hkeys[s[rem]] : EMPTY;
+#pragma unroll
+                for (int rem = 0; rem < 4; ++rem) {
+                    if (!live[rem]) continue;
+                    if (cur[rem] == ki[rem]) { res[rem] = hvals[s[rem]]; live[rem] = false; }
+                    else if (cur[rem] == EMPTY) live[rem] = false;
+                    else s[rem] = (s[rem] + 1) & (uint64_t)hmask;
+                }
+            }
+#pragma unroll
+            for (int rem = 0; rem < 4; ++rem) if (res[rem] >= H) res[rem] = -1;
+        }
+        off[p] = make_int4(res[0], res[1], res[2], res[3]);
+    }
+    int nabs = 0;
+#pragma unroll
+    for (int rem = 0; rem < 4; ++rem) nabs += __popcll(__ballot(ok && res[rem] < 0));
+    const int nnone = __popcll(__ballot(ok && res[0] < 0 && res[1] < 0 && res[2] < 0 && res[3] < 0));
+    if ((threadIdx.x & 63) == 0) {
+        if (nabs) atomicAdd(&counters[0], nabs);
+        if (nnone) atomicAdd(&counters[1], nnone);
+    }
+}
+
 // =====================================================================================================================
 // Partitioned build (round 3): the same lattice, built WITHOUT a global hash insert and without scattered global stores.
 //
@@ -1617,6 +1680,34 @@ RnLayout rn_layout(int32_t h_cap, int32_t nsamples) {
     w.total = o;
     return w;
 }
+
+// the vertex table of a finished level (k_rn_init, k_rn_keys, k_rn_insert) into `ws`, laid out by rn_layout: what the radius-r
+// neighbour probes and the point query (efgh_lattice_index_build / efgh_lattice_locate) both start from
+struct RnTable { unsigned long long *hkeys; int *hvals; int4 *vkeys; int *mm; int64_t hs; };
+RnTable rn_table(void *workspace, int32_t h_cap, int32_t nsamples) {
+    const RnLayout w = rn_layout(h_cap, nsamples);
+    char *ws = (char *)workspace;
+    return RnTable{(unsigned long long *)(ws + w.hkeys), (int *)(ws + w.hvals), (int4 *)(ws + w.vkeys), (int *)(ws + w.mm),
+                   rn_slots(h_cap)};
+}
+float rn_std32() {
+    const uint32_t std_bits = 0x405105ECu;         // float32(4*sqrt(2/3)), generate_data.py:19
+    float std32;
+    memcpy(&std32, &std_bits, 4);
+    return std32;
+}
+void rn_table_build(const RnTable &t, const float *pts, int64_t pts_cstride, const int32_t *sid, int32_t pts_per_sample,
+                    int32_t nsamples, float scale32, const int32_t *list, const int32_t *vseg, const int32_t *vsid,
+                    const int32_t *info, int32_t h_cap, hipStream_t st) {
+    const int pps = sid ? 1 : pts_per_sample;
+    int gi = cdiv(t.hs, TPB * 4);
+    if (gi < cdiv((int64_t)nsamples * 8, TPB)) gi = cdiv((int64_t)nsamples * 8, TPB);
+    if (gi > 8192) gi = 8192;
+    k_rn_init<<<gi, TPB, 0, st>>>(t.hkeys, t.hs, t.mm, nsamples);
+    k_rn_keys<<<cdiv(h_cap, TPB), TPB, 0, st>>>(pts, pts_cstride, sid, pps, scale32, rn_std32(), list, (const int2 *)vseg, vsid, info,
+                                                h_cap, t.vkeys, t.mm);
+    k_rn_insert<<<cdiv(h_cap, TPB), TPB, 0, st>>>(t.vkeys, t.mm, vsid, info, h_cap, nsamples, t.hkeys, t.hvals, t.hs - 1);
+}
 }  // namespace
 
 extern "C" int64_t efgh_lattice_neighbors_r_workspace(int32_t h_cap, int32_t nsamples) {
@@ -1633,26 +1724,47 @@ extern "C" int efgh_lattice_neighbors_r(const float *pts, int64_t pts_cstride, c
     EFGH_CHECK_ARG(h_cap > 0 && nsamples >= 1 && nsamples <= EFGH_LATTICE_MAX_SAMPLES && F >= 1 && F <= 1024);
     const int nw = (F + 31) / 32;
     EFGH_CHECK_ARG(ld >= F + nw && (((uintptr_t)offsets) & 15) == 0);
-    const RnLayout w = rn_layout(h_cap, nsamples);
-    const int64_t hs = rn_slots(h_cap);
-    char *ws = (char *)workspace;
-    unsigned long long *hkeys = (unsigned long long *)(ws + w.hkeys);
-    int *hvals = (int *)(ws + w.hvals), *mm = (int *)(ws + w.mm);
-    int4 *vkeys = (int4 *)(ws + w.vkeys);
-    const uint32_t std_bits = 0x405105ECu;         // float32(4*sqrt(2/3)), generate_data.py:19
-    float std32;
-    memcpy(&std32, &std_bits, 4);
-    const int pps = sid ? 1 : pts_per_sample;
-    int gi = cdiv(hs, TPB * 4);
-    if (gi < cdiv((int64_t)nsamples * 8, TPB)) gi = cdiv((int64_t)nsamples * 8, TPB);
-    if (gi > 8192) gi = 8192;
-    k_rn_init<<<gi, TPB, 0, st>>>(hkeys, hs, mm, nsamples);
-    k_rn_keys<<<cdiv(h_cap, TPB), TPB, 0, st>>>(pts, pts_cstride, sid, pps, scale32, std32, list, (const int2 *)vseg, vsid, info, h_cap,
-                                                vkeys, mm);
-    k_rn_insert<<<cdiv(h_cap, TPB), TPB, 0, st>>>(vkeys, mm, vsid, info, h_cap, nsamples, hkeys, hvals, hs - 1);
+    const RnTable t = rn_table(workspace, h_cap, nsamples);
+    rn_table_build(t, pts, pts_cstride, sid, pts_per_sample, nsamples, scale32, list, vseg, vsid, info, h_cap, st);
     int gp = cdiv((int64_t)h_cap * nw * 32, TPB);
     if (gp > 16384) gp = 16384;
-    k_rn_probe<<<gp, TPB, 0, st>>>(vkeys, mm, vsid, info, h_cap, nsamples, hkeys, hvals, hs - 1, (const int4 *)offsets, F, nw, ld, nbr);
+    k_rn_probe<<<gp, TPB, 0, st>>>(t.vkeys, t.mm, vsid, info, h_cap, nsamples, t.hkeys, t.hvals, t.hs - 1, (const int4 *)offsets, F, nw,
+                                   ld, nbr);
+    EFGH_CHECK_LAUNCH();
+    return EFGH_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// persistent vertex index of a level + point query: host side.  The index memory is the neighbour stage's workspace kept: the
+// table (hkeys, hvals), the per-sample key boxes (mm) and the vertex keys the insert read
+extern "C" int64_t efgh_lattice_index_bytes(int32_t h_cap, int32_t nsamples) {
+    if (h_cap <= 0 || nsamples <= 0) return 0;
+    return rn_layout(h_cap, nsamples).total;
+}
+
+extern "C" int efgh_lattice_index_build(const float *pts, int64_t pts_cstride, const int32_t *sid, int32_t pts_per_sample,
+                                        int32_t nsamples, float scale32, const int32_t *list, const int32_t *vseg,
+                                        const int32_t *vsid, const int32_t *info, int32_t h_cap, void *index, void *stream_) {
+    hipStream_t st = (hipStream_t)stream_;
+    EFGH_CHECK_ARG(pts && list && vseg && vsid && info && index && (sid || pts_per_sample > 0));
+    EFGH_CHECK_ARG(h_cap > 0 && nsamples >= 1 && nsamples <= EFGH_LATTICE_MAX_SAMPLES && (((uintptr_t)index) & 15) == 0);
+    rn_table_build(rn_table(index, h_cap, nsamples), pts, pts_cstride, sid, pts_per_sample, nsamples, scale32, list, vseg, vsid, info,
+                   h_cap, st);
+    EFGH_CHECK_LAUNCH();
+    return EFGH_OK;
+}
+
+extern "C" int efgh_lattice_locate(const float *q, int64_t q_cstride, const int32_t *q_sid, int32_t q_pts_per_sample, int32_t n_q,
+                                   float scale32, const void *index, int32_t nsamples, int32_t h_cap, const int32_t *info,
+                                   float *bary_out, int32_t *off_out, int32_t *counters, void *stream_) {
+    hipStream_t st = (hipStream_t)stream_;
+    EFGH_CHECK_ARG(q && index && info && bary_out && off_out && counters && (q_sid || q_pts_per_sample > 0));
+    EFGH_CHECK_ARG(n_q > 0 && q_cstride >= n_q && h_cap > 0 && nsamples >= 1 && nsamples <= EFGH_LATTICE_MAX_SAMPLES);
+    EFGH_CHECK_ARG(((((uintptr_t)index) | ((uintptr_t)bary_out) | ((uintptr_t)off_out)) & 15) == 0);
+    const RnTable t = rn_table(const_cast<void *>(index), h_cap, nsamples);
+    k_locate<<<cdiv(n_q, TPB), TPB, 0, st>>>(q, q_cstride, q_sid, q_sid ? 1 : q_pts_per_sample, n_q, scale32, rn_std32(), t.hkeys,
+                                             t.hvals, t.hs - 1, t.mm, nsamples, info, h_cap, (float4 *)bary_out, (int4 *)off_out,
+                                             counters);
     EFGH_CHECK_LAUNCH();
     return EFGH_OK;
 }

@@ -104,9 +104,23 @@ class LatticeLevel:
 
     point-major device arrays (16 B per point): bary_pm, emg_pm (float32 [n][4]), off_pm (int32 [n][4]);
     per vertex: nbr [H][ld] (F = filter_size(radius) neighbours + alias-mask words; [H][16] at radius 1), vseg [H][2] + list [4n] (vertex -> ascending flat positions
-    4p + r), pts_next [3][H]; info = the level's device counters (INFO_*), alist = aliased neighbour records."""
+    4p + r), pts_next [3][H]; info = the level's device counters (INFO_*), alist = aliased neighbour records.
+    _src = (pts, cstride, sid, pps, scale): the points the level was built from, kept for the point query (OutPoints.locate) - the
+    previous level's arrays, or the [3][B N] form of the cloud for level 0 (for B = 1 a VIEW of the caller's cloud: it must not be
+    overwritten before the first query); _index: the vertex index of the level, built on the first query."""
     __slots__ = ('n_in', 'H', 'bary_pm', 'emg_pm', 'off_pm', 'nbr', 'vseg', 'list', 'pts_next_buf', 'info', 'alist',
-                 'seg_in', 'seg', 'vsid', '_ws', '_caps', '_mode', '_geom', '_zeroed', 'n_alias', 'radius', 'F', 'ld')
+                 'seg_in', 'seg', 'vsid', '_ws', '_caps', '_mode', '_geom', '_zeroed', 'n_alias', 'radius', 'F', 'ld',
+                 '_src', '_index')
+
+    def vertex_index(self):
+        """the persistent vertex index (efgh_lattice_index_build): key integer -> vertex row and the per-sample key boxes, whichever
+        plan built the level; made on the first call, kept"""
+        if self._index is None:
+            from . import ops
+            pts, cstride, sid, pps, s = self._src
+            self._index = ops.lattice_index(pts, cstride, sid, pps, len(self.seg) - 1, s, self.list, self.vseg, self.vsid, self.info,
+                                            self.H)
+        return self._index
 
     # the reference's (4, n) / (3, H) arrays as views
     @property
@@ -150,10 +164,13 @@ class OutPoints:
     """where the slice step of a BCL puts lattice features (bilateralNN.py:251-257 out_barycentric / out_lattice_offset): bary
     [n_out][4] float32 and off [n_out][4] int32, point-major like LatticeLevel.bary_pm / off_pm, off in GLOBAL row indices of the
     level's [H]-row arrays (sample-major).  The inverse of off (vseg, list: what the slice's backward walks) is built on first
-    use; that is also the one time the count of offsets outside [0, H) is read, and a nonzero count raises EfghError."""
-    __slots__ = ('n_out', 'H', 'bary', 'off', '_vseg', '_list')
+    use; that is also the one time the count of offsets outside [0, H) is read, and a nonzero count raises EfghError.
+    Out points made by `locate` (a lattice query of arbitrary points) may hold -1 = the lattice has no such vertex: that corner
+    contributes nothing, forward and backward, and the other weights are not renormalised (the blur treats a missing neighbour the
+    same way).  They carry the query's device counters; the count of left-out offsets must then EQUAL the absent corners."""
+    __slots__ = ('n_out', 'H', 'bary', 'off', '_vseg', '_list', '_counters', '_missing')
 
-    def __init__(self, bary, off, H, vseg=None, lst=None):
+    def __init__(self, bary, off, H, vseg=None, lst=None, counters=None):
         _C.require_cuda(bary, off)
         if bary.dtype != torch.float32 or off.dtype != torch.int32 or bary.dim() != 2 or bary.shape[1] != 4 or \
                 tuple(off.shape) != tuple(bary.shape) or bary.shape[0] < 1 or int(H) < 1:
@@ -162,6 +179,40 @@ class OutPoints:
         self.bary, self.off = bary.contiguous(), off.contiguous()
         self.n_out, self.H = int(bary.shape[0]), int(H)
         self._vseg, self._list = vseg, lst
+        self._counters, self._missing = counters, None           # (counters: absent corners are expected - set by locate only)
+
+    @classmethod
+    def locate(cls, lv, pts, sid=None):
+        """arbitrary points on a built level: pts (3, M) or (B, 3, M) float32 on the device, in the frame of the cloud handed to
+        build_pyramid(_batched) (the level's own scale is applied inside, as the build applies it); sid: int32 [M], the sample of
+        every point of the (3, M) form (None: sample 0 of a one-sample level); the (B, 3, M) form puts M points on every sample.
+        The weights are constants (generate_data.py:119); off holds -1 where the lattice has no vertex at a corner, see missing()"""
+        from . import ops
+        _C.require_cuda(pts, sid)
+        _C.require_f32(pts)
+        B = len(lv.seg) - 1
+        if pts.dim() == 3 and pts.shape[0] == B and pts.shape[1] == 3 and pts.shape[2] >= 1 and sid is None:
+            M = pts.shape[2]
+            q, cstride, pps, n_q = pts.detach().permute(1, 0, 2).reshape(3, B * M).contiguous(), B * M, M, B * M
+        elif pts.dim() == 2 and pts.shape[0] == 3 and pts.shape[1] >= 1 and (sid is not None or B == 1):
+            q = pts.detach()
+            if q.stride(1) != 1 or q.stride(0) < q.shape[1]:
+                q = q.contiguous()
+            cstride, pps, n_q = q.stride(0), q.shape[1], q.shape[1]
+            if sid is not None and (sid.dtype != torch.int32 or tuple(sid.shape) != (n_q,) or not sid.is_contiguous()):
+                raise _C.EfghError('OutPoints.locate: sid = int32 [%d], contiguous, expected, got %s %s' % (n_q, tuple(sid.shape), sid.dtype))
+        else:
+            raise _C.EfghError('OutPoints.locate: points (3, M), with sid [M] on a level of more than one sample, or (%d, 3, M) expected '
+                               'on this level of %d sample(s), got %s' % (B, B, tuple(pts.shape)))
+        bary, off, counters = ops.lattice_locate(lv.vertex_index(), q, cstride, sid, pps, n_q, lv._src[4], B, lv.H, lv.info)
+        return cls(bary, off, lv.H, counters=counters)
+
+    def missing(self):
+        """(absent corners, points without any corner) of located points - one read, kept; (0, 0) for out points that were not
+        located (theirs hold none, or lists() raises)"""
+        if self._missing is None:
+            self._missing = (0, 0) if self._counters is None else tuple(self._counters.tolist())
+        return self._missing
 
     @classmethod
     def of_level(cls, lv):
@@ -184,10 +235,14 @@ class OutPoints:
         if self._vseg is None:
             from . import ops
             vseg, lst, err = ops.offsets_invert(self.off, self.H)
-            bad = int(err.item())                  # the one read of the error word
-            if bad:
+            if self._counters is None:
+                bad, expected = int(err.item()), 0                  # the one read of the error word
+            else:                                  # located points: the left-out entries are the query's absent corners, no other
+                bad, expected, none = torch.cat([err, self._counters]).tolist()          # (one transfer)
+                self._missing = (expected, none)
+            if bad != expected:
                 raise _C.EfghError('OutPoints: %d lattice offsets outside [0, %d) (the reference would wrap a -1 to the last vertex; '
-                                   'here that is an error)' % (bad, self.H))
+                                   'here that is an error)%s' % (bad, self.H, ', %d absent corners located' % expected if expected else ''))
             self._vseg, self._list = vseg, lst
         return self._vseg, self._list
 
@@ -267,6 +322,7 @@ def _level_arrays(L, dev, n_cap, h_cap, B, mode=('hash', 0), ctrl=None, need_off
     None = allocate and zero one here.  need_off=False (partitioned build only): lattice_offset is not produced"""
     lv = LatticeLevel()
     lv._mode = mode = _as_plan(mode)
+    lv._src = lv._index = None
     lv.radius, lv.F, lv.ld = 1, 15, 16
     lv.bary_pm = torch.empty((n_cap, 4), dtype=torch.float32, device=dev)
     lv.emg_pm = torch.empty((n_cap, 4), dtype=torch.float32, device=dev)
@@ -296,6 +352,7 @@ def _launch_build(L, lv, pts, cstride, n_dev, sid, pps, B, s, st):
     head = (_C.ptr(pts), _C.c_int64(cstride), _C.ptr(n_dev), _C.c_int32(n_cap), _C.ptr(sid), _C.c_int32(pps), _C.c_int32(B),
             _C.c_float(np.float32(s)))
     lv._geom = (pts, cstride, n_dev, sid, pps, s)          # (kept alive for the neighbours call)
+    lv._src = (pts, cstride, sid, pps, s)                  # (kept with the level: OutPoints.locate)
     plan = lv._mode
     if plan.kind == 'part':
         _C.check(L.efgh_lattice_part_build(*head, _C.ptr(lv.bary_pm), _C.ptr(lv.emg_pm), _C.ptr(lv.list), _C.c_int32(h_cap),

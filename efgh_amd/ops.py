@@ -1166,6 +1166,33 @@ def offsets_invert(off, H):
     return vseg, lst, err
 
 
+def lattice_index(pts, cstride, sid, pps, B, scale, lst, vseg, vsid, info, H):
+    """the persistent vertex index of a finished lattice level (efgh_lattice_index_build): pts [3][cstride] / sid / pps / scale as the
+    level was built from them, lst / vseg / vsid / info as the build left them, H vertex rows, B samples -> the index (uint8)"""
+    L = _L()
+    index = torch.empty(L.efgh_lattice_index_bytes(c_int32(H), c_int32(B)), dtype=torch.uint8, device=info.device)
+    with _bcl_prof('lattice index', float(H) * (12 + 16 * 2 + 24 + 16)):      # point + vertex records, vkeys w + r, table (2 slots), mm
+        _C.check(L.efgh_lattice_index_build(ptr(pts), c_int64(cstride), ptr(sid), c_int32(pps), c_int32(B), c_float(scale), ptr(lst),
+                                            ptr(vseg), ptr(vsid), ptr(info), c_int32(H), ptr(index), _st()))
+    return index
+
+
+def lattice_locate(index, q, cstride, qsid, qpps, n_q, scale, B, H, info):
+    """n_q query points q [3][cstride] (sample of point p: qsid[p], or p // qpps) on the level that `index` was built from ->
+    (bary [n_q][4] float32, off [n_q][4] int32 with -1 = no such vertex, counters [2] int32: absent corners, points without any
+    corner).  All on the device, nothing is read back (efgh_lattice_locate)"""
+    _C.require_cuda(q, qsid)
+    _C.require_f32(q)
+    dev = q.device
+    bary = torch.empty((n_q, 4), dtype=torch.float32, device=dev)
+    off = torch.empty((n_q, 4), dtype=torch.int32, device=dev)
+    counters = torch.zeros(2, dtype=torch.int32, device=dev)
+    with _bcl_prof('lattice locate', float(n_q) * (12 + 32 + 4 * 12)):        # point, bary + off, four probes (key + value)
+        _C.check(_L().efgh_lattice_locate(ptr(q), c_int64(cstride), ptr(qsid), c_int32(qpps), c_int32(n_q), c_float(scale), ptr(index),
+                                          c_int32(B), c_int32(H), ptr(info), ptr(bary), ptr(off), ptr(counters), _st()))
+    return bary, off, counters
+
+
 def slice_bwd(pts, gout, C, ooff=0, want_bias=False, gfeat=None):
     """backward of slice_fwd: gout [n_out][ldo] (its columns [ooff, ooff + C)) -> gfeat [H][C] (or into the given [H][>= C] buffer;
     every row is written, zeros where no out point touches the vertex), and the bias gradient [C] when want_bias"""

@@ -54,7 +54,8 @@ const char *efgh_last_error(void);
  *      efgh_lattice_tail_lds_bytes and its two descriptor structs) is removed: it was slower than the per-level entry points at every
  *      batch size and nothing called it.  Nothing else changed.
  *      Added later WITHOUT moving the number (no existing signature or struct changed): efgh_slice, efgh_slice_bwd,
- *      efgh_slice_bwd_workspace, efgh_offsets_invert, efgh_offsets_invert_workspace (the slice step of the BCL). */
+ *      efgh_slice_bwd_workspace, efgh_offsets_invert, efgh_offsets_invert_workspace (the slice step of the BCL);
+ *      efgh_lattice_index_bytes, efgh_lattice_index_build, efgh_lattice_locate (point query of a built level). */
 #define EFGH_ABI_VERSION 4
 int efgh_version(void);
 
@@ -445,6 +446,31 @@ int efgh_lattice_neighbors_r(const float *pts, int64_t pts_cstride, const int32_
                              float scale32, const int32_t *list, const int32_t *vseg, const int32_t *vsid, const int32_t *info,
                              int32_t h_cap, const int32_t *offsets, int32_t F, int32_t ld, int32_t *nbr, void *workspace,
                              void *stream);
+/* ------------------------------------------------------------------ point query of a built level ------
+ * Where do ARBITRARY points fall on a finished level: barycentric weights and the four enclosing vertices' rows, the out points of
+ * efgh_slice (out_barycentric / out_lattice_offset of nets/bilateralNN.py:248-257) for points that did not build the lattice.
+ *
+ * efgh_lattice_index_build keeps, in caller-owned memory of efgh_lattice_index_bytes(h_cap, nsamples) bytes (256-byte aligned), the
+ * vertex table that efgh_lattice_neighbors_r builds for its probes (the same launches): key integer * nsamples + sample -> vertex,
+ * load <= 1/2, and the per-sample key boxes.  Arguments as efgh_lattice_neighbors_r takes them; it may run at any time after the
+ * build as long as pts / list / vseg / vsid / info are unchanged.
+ *
+ * efgh_lattice_locate: q [3][q_cstride] query points (n_q of them) in the frame of the points that built the level, scale32 the
+ * level's scale; the sample of point p is q_sid[p], or p / q_pts_per_sample when q_sid is NULL, and a point is looked up in its own
+ * sample's lattice only.  index / nsamples / h_cap / info: as passed to efgh_lattice_index_build.  Per point the recipe of the build
+ * (nets/generate_data.py:56-112, bit for bit) gives bary_out[p][0..3] and the four keys; off_out[p][r] = the GLOBAL row of corner r
+ * (as `off` of the build, point-major) or -1 where the lattice has no such vertex: a key outside its sample's key box (tested on
+ * the key, before the key integer: out-of-box keys can carry a real vertex's key integer) or not in the table; a sample outside
+ * [0, nsamples) has none.  counters[0] += absent corners, counters[1] += points without any corner (int32, device; the caller
+ * zeroes them; integer atomics, one per wave: exact).  Nothing is read back.  The weights of the present corners are NOT
+ * renormalised: efgh_slice skips a -1, efgh_offsets_invert leaves it out and counts it.                                        */
+int64_t efgh_lattice_index_bytes(int32_t h_cap, int32_t nsamples);
+int efgh_lattice_index_build(const float *pts, int64_t pts_cstride, const int32_t *sid, int32_t pts_per_sample, int32_t nsamples,
+                             float scale32, const int32_t *list, const int32_t *vseg, const int32_t *vsid, const int32_t *info,
+                             int32_t h_cap, void *index, void *stream);
+int efgh_lattice_locate(const float *q, int64_t q_cstride, const int32_t *q_sid, int32_t q_pts_per_sample, int32_t n_q,
+                        float scale32, const void *index, int32_t nsamples, int32_t h_cap, const int32_t *info, float *bary_out,
+                        int32_t *off_out, int32_t *counters, void *stream);
 /* blur Conv2d(C, N, (F, 1)) through that table (replaces bilateralNN.py:240-246 at any F): as efgh_gather_gemm mode 2 with
  * d->mode = 2, d->T = F, the table row stride `ld`; no batching, no alias masking (d->table_alias_mask = 0).  The data gradient is
  * the same call on the upstream gradient with the taps permuted by inv and the weight transposed. */
