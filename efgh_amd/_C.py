@@ -45,6 +45,19 @@ class WgradOutDesc(ctypes.Structure):
                 ('sn', c_int64), ('sc', c_int64), ('st', c_int64), ('taps', c_int32 * 16), ('accumulate', c_int32)]
 
 
+GUARD_MAX_SEGMENTS = 8   # EFGH_GUARD_MAX_SEGMENTS
+GUARD_RUN = 4096         # EFGH_GUARD_RUN
+
+
+class GuardState(ctypes.Structure):
+    """mirror of efgh_guard_state (include/efgh_hip.h): the device-resident result of efgh_grad_guard_measure"""
+    _fields_ = [('sumsq', ctypes.c_double * GUARD_MAX_SEGMENTS), ('sumsq_total', ctypes.c_double), ('norm', ctypes.c_double),
+                ('nonfinite', c_int64 * GUARD_MAX_SEGMENTS), ('nonfinite_total', c_int64),
+                ('applied', c_int64), ('skipped', c_int64),
+                ('coef', c_float), ('scale', c_float), ('bc1', c_float), ('bc2_sqrt', c_float),
+                ('skip', c_int32), ('nseg', c_int32)]
+
+
 WROTE_OUT = 1            # EFGH_WROTE_OUT
 
 
@@ -99,6 +112,12 @@ def lib():
         _lib.efgh_offsets_invert_workspace.argtypes = [c_int32, c_int32]
         _lib.efgh_slice_bwd_workspace.restype = c_int64
         _lib.efgh_slice_bwd_workspace.argtypes = [c_int32]
+        _lib.efgh_grad_guard_workspace.restype = c_int64
+        _lib.efgh_grad_guard_workspace.argtypes = [c_int64]
+        _lib.efgh_grad_guard_measure.argtypes = [c_void_p, c_int64, ctypes.POINTER(c_int64), c_int32, ctypes.c_double, c_float,
+                                                 c_int32, c_float, c_float, c_int32, c_void_p, c_void_p, c_int32, c_void_p]
+        _lib.efgh_adam_step_guarded.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_float, c_float, c_float,
+                                                c_float, c_float, c_void_p, c_void_p]
     return _lib
 
 

@@ -66,9 +66,10 @@ def adam_state_dict(opt, lr=None):
     """`torch.optim.Adam.state_dict()`-compatible view of a train.FusedAdam (one entry per parameter)."""
     flat = opt.flat
     state = {}
+    t = opt.t           # read ONCE: with the gradient guard's skip_nonfinite the count of APPLIED steps lives on the device
     for i, (p, (off, k)) in enumerate(zip(flat.params, flat.offsets)):
-        if opt.t > 0:
-            state[i] = {'step': torch.tensor(float(opt.t)),
+        if t > 0:
+            state[i] = {'step': torch.tensor(float(t)),
                         'exp_avg': opt.m[off:off + k].view(p.shape).detach().clone(),
                         'exp_avg_sq': opt.v[off:off + k].view(p.shape).detach().clone()}
     group = {'lr': opt.lr if lr is None else lr, 'betas': tuple(opt.betas), 'eps': opt.eps,
@@ -90,7 +91,7 @@ def load_adam_state(opt, sd):
         opt.m[off:off + k].copy_(st['exp_avg'].reshape(-1))
         opt.v[off:off + k].copy_(st['exp_avg_sq'].reshape(-1))
         steps.append(int(st['step']))
-    opt.t = max(steps) if steps else 0
+    opt.t = max(steps) if steps else 0          # (a property: with skip_nonfinite it also sets the device-side count)
 
 
 def save_checkpoint(ckpt_dir, model, opt, it, min_loss, is_best=False, iter_interval=1000,

@@ -47,7 +47,10 @@ What makes the reference's REAL main.py safe under N processes (round 5; every r
   * the parent polls its children: the first non-zero exit terminates the siblings and becomes the exit code, and the process
     group has a timeout (`EFGH_RUN_TIMEOUT_S`, default 1800 s), so a rank that skips a step's `optimizer.step()` - the
     reference's "CUDA out of memory: continue" path, iterater.py:108-116, taken on one rank only - ends the job with an error
-    instead of hanging it: a skipped step must be skipped on ALL ranks.
+    instead of hanging it: a skipped step must be skipped on ALL ranks.  (`efgh_amd.train.Trainer(skip_nonfinite=True)` skips
+    a non-finite step on all ranks by construction: its decision is taken on the device from the all-reduced gradient, which
+    holds the same bits on every rank.  The stock-optimizer loop behind this launcher has no such guard: a script that clips
+    or checks its gradients calls torch's own `clip_grad_norm_` on every rank alike.)
 """
 import os
 import runpy

@@ -212,17 +212,108 @@ class OverlappedAllReduce:
             w.wait()
 
 
-class FusedAdam:
-    """torch.optim.Adam(lr, betas=(0.9,0.999), eps=1e-8, weight_decay) on a FlatParams, one HIP launch."""
+def check_max_grad_norm(value):
+    """`max_grad_norm` of FusedAdam / Trainer: None (no clipping) or a real number > 0 (`inf`: measure only) -> None | float"""
+    if value is None:
+        return None
+    if isinstance(value, bool) or not isinstance(value, (int, float)):
+        raise _C.EfghError('max_grad_norm must be a real number > 0 (or None), got %r' % (value,))
+    v = float(value)
+    if not v > 0.0:                                         # (also catches NaN)
+        raise _C.EfghError('max_grad_norm must be a real number > 0 (or None), got %r' % (value,))
+    return v
 
-    def __init__(self, flat, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
+
+def name_segments(names, sizes, limit=_C.GUARD_MAX_SEGMENTS):
+    """segments of a flat parameter buffer for the gradient guard's per-segment norms: the consecutive runs of equal top-level
+    module name (`E.bcn1.weight` -> `E`) in flat order, as [(name, start, end)]; one segment `all` when there would be more than
+    `limit` runs (or no parameters have names)"""
+    segs, off = [], 0
+    for name, k in zip(names, sizes):
+        top = name.split('.')[0]
+        if k > 0:
+            if segs and segs[-1][0] == top:
+                segs[-1][2] = off + k
+            else:
+                segs.append([top, off, off + k])
+        off += k
+    if not segs or len(segs) > limit:
+        return [('all', 0, off)]
+    return [tuple(s) for s in segs]
+
+
+class FusedAdam:
+    """torch.optim.Adam(lr, betas=(0.9,0.999), eps=1e-8, weight_decay) on a FlatParams, one HIP launch.
+
+    Gradient guard (off by default; with both options off `step` is the single efgh_adam_step launch and nothing below exists):
+      max_grad_norm   `torch.nn.utils.clip_grad_norm_(params, max_grad_norm)` in front of the update; `float('inf')` measures only
+      skip_nonfinite  a step whose gradient holds an inf or NaN leaves weights and moments untouched and does not count as a step
+                      (`optimizer.step()` not called); without it non-finite values propagate as in torch
+      segments        [(name, start, end)] cutting [0, n) into at most 8 contiguous pieces whose norms are reported separately
+    A guarded step is three launches (measure, decide, Adam): the norm, the clip coefficient and the skip decision stay in a
+    device-resident state block, nothing is read back.  In a data-parallel run the measure pass sees the all-reduced (summed)
+    gradient, which is bit-identical on every rank, so every rank takes the same decision.  `guard_stats()` reads the block.
+    With skip_nonfinite the step count `t` lives on the device too (reading `opt.t` costs one device read)."""
+
+    def __init__(self, flat, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_grad_norm=None,
+                 skip_nonfinite=False, segments=None):
+        self.max_grad_norm = check_max_grad_norm(max_grad_norm)
+        self.skip_nonfinite = bool(skip_nonfinite)
+        self.guarded = self.max_grad_norm is not None or self.skip_nonfinite
         self.flat, self.lr, self.betas, self.eps, self.wd = flat, lr, betas, eps, weight_decay
         self.m = torch.zeros_like(flat.w)
         self.v = torch.zeros_like(flat.w)
-        self.t = 0
+        self._t = 0
+        self.segments = self.state = self.workspace = None
+        if self.guarded:
+            segs = [(str(a), int(b), int(c)) for a, b, c in segments] if segments is not None else [('all', 0, flat.n)]
+            ends = [0] + [c for _, _, c in segs]
+            if not (1 <= len(segs) <= _C.GUARD_MAX_SEGMENTS) or ends[-1] != flat.n or \
+                    any(b != e0 or c <= b for (_, b, c), e0 in zip(segs, ends)):
+                raise _C.EfghError('segments must cut [0, %d) into 1..%d non-empty contiguous pieces in order, got %r'
+                                   % (flat.n, _C.GUARD_MAX_SEGMENTS, segs))
+            self.segments = segs
+            self._bounds = (_C.c_int64 * (len(segs) + 1))(*ends)
+            nbytes = _C.lib().efgh_grad_guard_workspace(flat.n)
+            if nbytes < 0:
+                raise _C.EfghError('the gradient guard handles 1 <= n < 2^31 parameters, got %d' % flat.n)
+            self.state = torch.zeros(_C.ctypes.sizeof(_C.GuardState), dtype=torch.uint8, device=flat.w.device)
+            self.workspace = torch.empty(nbytes, dtype=torch.uint8, device=flat.w.device)
+            self._grad_scale = 1.0
+
+    @property
+    def t(self):
+        """Adam's step count: a host integer, except with skip_nonfinite, where the device decides which steps count (one read)"""
+        if self.skip_nonfinite:
+            self._t = int(self._read_state().applied)
+        return self._t
+
+    @t.setter
+    def t(self, value):
+        self._t = int(value)
+        if self.skip_nonfinite:
+            off = _C.GuardState.applied.offset
+            self.state[off:off + 8].view(torch.int64).fill_(self._t)
+
+    def _read_state(self):
+        return _C.GuardState.from_buffer_copy(self.state.cpu().numpy().tobytes())
+
+    def guard_stats(self):
+        """what the guard saw at the last step and did so far, from ONE device read: applied / skipped step counts, `norm` (global
+        2-norm of the gradient as applied, i.e. of the mean gradient over the ranks), `norms` per segment, the clip coefficient
+        `coef` and the number of non-finite gradient elements"""
+        if not self.guarded:
+            raise _C.EfghError('guard_stats(): the gradient guard is off (construct with max_grad_norm= and / or skip_nonfinite=True)')
+        st = self._read_state()
+        gs = self._grad_scale
+        return {'applied': int(st.applied), 'skipped': int(st.skipped), 'norm': float(st.norm),
+                'norms': {name: float(st.sumsq[i]) ** 0.5 * gs for i, (name, _, _) in enumerate(self.segments)},
+                'coef': float(st.coef), 'nonfinite': int(st.nonfinite_total)}
 
     def step(self, grad_scale=1.0):
         _C.require_cuda(self.flat.w)
+        if self.guarded:
+            return self._step_guarded(grad_scale)
         self.t += 1
         f = self.flat
         _C.check(_C.lib().efgh_adam_step(_C.ptr(f.w), _C.ptr(f.g), _C.ptr(self.m), _C.ptr(self.v), _C.c_int64(f.n),
@@ -231,6 +322,19 @@ class FusedAdam:
                                          _C.c_float(grad_scale), _C.stream_ptr()))
         ops.bump_epoch(self.flat.epoch)            # packed-weight / folded-BN caches are stale now
 
+    def _step_guarded(self, grad_scale):
+        f, lib, stream = self.flat, _C.lib(), _C.stream_ptr()
+        if not self.skip_nonfinite:
+            self._t += 1                           # (with skip_nonfinite the device counts: a skipped step is not one)
+        self._grad_scale = float(grad_scale)
+        max_norm = self.max_grad_norm if self.max_grad_norm is not None else float('inf')
+        _C.check(lib.efgh_grad_guard_measure(f.g.data_ptr(), f.n, self._bounds, len(self.segments), max_norm, grad_scale,
+                                             int(self.skip_nonfinite), self.betas[0], self.betas[1], self._t,
+                                             self.workspace.data_ptr(), self.state.data_ptr(), 0, stream))
+        _C.check(lib.efgh_adam_step_guarded(f.w.data_ptr(), f.g.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), f.n, self.lr,
+                                            self.betas[0], self.betas[1], self.eps, self.wd, self.state.data_ptr(), stream))
+        ops.bump_epoch(self.flat.epoch)            # (also after a skipped step: the host does not know, a repack is harmless)
+
 
 def adjust_learning_rate(base_lr, it, every=50000, gamma=0.7):
     """common/helper.py:28-38"""
@@ -238,9 +342,18 @@ def adjust_learning_rate(base_lr, it, every=50000, gamma=0.7):
 
 
 class Trainer:
-    """one data-parallel training step; `world`/`rank` from torch.distributed when initialised."""
+    """one data-parallel training step; `world`/`rank` from torch.distributed when initialised.
 
-    def __init__(self, model, criterion, lr=1e-4, weight_decay=0.0):
+    `max_grad_norm` / `skip_nonfinite` switch on FusedAdam's gradient guard (global-norm clipping, skipping of steps with an inf /
+    NaN gradient; both off by default, and then nothing changes).  The guard measures the gradient after `comm.finish()`, i.e. the
+    all-reduced sum, which holds the same bits on every rank: all ranks clip by the same coefficient and skip the same steps, so
+    no rank waits for another's `optimizer.step()`.  The norms are reported per sub-network (`E`, `H`, `F`, `G`: the runs of
+    equal top-level module name in flat parameter order; one segment `all` if there were more than 8).  `step` never reads the
+    guard's state; `guard_stats()` does, once per call.  The guard protects weights and moments from non-finite GRADIENTS: a NaN
+    that appears in the training forward has reached BatchNorm's running statistics before the guard runs and is not rolled back."""
+
+    def __init__(self, model, criterion, lr=1e-4, weight_decay=0.0, max_grad_norm=None, skip_nonfinite=False):
+        max_grad_norm = check_max_grad_norm(max_grad_norm)                       # (before anything is re-homed or broadcast)
         self.model, self.criterion = model, criterion
         self.world = dist.get_world_size() if dist.is_initialized() else 1
         self.flat = FlatParams(model)
@@ -250,11 +363,21 @@ class Trainer:
             for t in list(model.parameters()) + list(model.buffers()):
                 if id(t) not in flat_ids:
                     dist.broadcast(t.data, 0)
-        self.opt = FusedAdam(self.flat, lr=lr, weight_decay=weight_decay)
+        segments = None
+        if max_grad_norm is not None or skip_nonfinite:
+            names = [k for k, p in model.named_parameters() if p.requires_grad]
+            segments = name_segments(names, [k for _, k in self.flat.offsets])
+        self.opt = FusedAdam(self.flat, lr=lr, weight_decay=weight_decay, max_grad_norm=max_grad_norm,
+                             skip_nonfinite=skip_nonfinite, segments=segments)
         self.comm = OverlappedAllReduce(self.flat, self.world)
         if self.world > 1:
             ops.reserve_comm_queue()
         self.base_lr, self.it = lr, 0
+
+    def guard_stats(self):
+        """FusedAdam.guard_stats(): {'applied', 'skipped', 'norm', 'norms': {segment: norm}, 'coef', 'nonfinite'} of the last step,
+        from one device read made here and nowhere else; EfghError when the guard is off"""
+        return self.opt.guard_stats()
 
     def load_checkpoint(self, ckpt):
         """resume from a checkpoint in the reference's layout (common/helper.py:40-61, main.py:149-160,190-198): model state,

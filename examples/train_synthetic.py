@@ -45,6 +45,8 @@ def main(argv=None):
     ap.add_argument('--batch', type=int, default=2)
     ap.add_argument('--raw', type=int, nargs=2, default=[128, 256])
     ap.add_argument('--points', type=int, default=2048)
+    ap.add_argument('--max-grad-norm', type=float, default=None, help='clip the global gradient norm (torch clip_grad_norm_) inside the fused step')
+    ap.add_argument('--skip-nonfinite', action='store_true', help='leave weights and Adam moments untouched on a step whose gradient holds inf / NaN')
     a = ap.parse_args(argv)
     raw = tuple(a.raw)
     args = syn.default_args(raw, 'cuda')
@@ -52,7 +54,7 @@ def main(argv=None):
                  'dclb': {'l_rot_range': 1 / 12., 'l_trs_range': 1.0, 'c_rot_range': 1 / 12.}})
     torch.manual_seed(0)
     model = EFGHBackbone(args).cuda()
-    trainer = Trainer(model, EFGHCriterion(args), lr=1e-4)
+    trainer = Trainer(model, EFGHCriterion(args), lr=1e-4, max_grad_norm=a.max_grad_norm, skip_nonfinite=a.skip_nonfinite)
     prep = ProcessKITTIODOM(args)
     err = Err(args['dataset'])
     calib0, _ = syn.calib_and_A(raw)
@@ -69,6 +71,8 @@ def main(argv=None):
         err.update({'sensor2_T_sensor1': gt['sensor2_T_sensor1'].float().cuda()}, pred)
         hist.append(float(losses['total'].detach()))
         print('iter %d  total %.4f  %s' % (it, hist[-1], '  '.join('%s %.3f' % kv for kv in err.dict.items())))
+    if a.max_grad_norm is not None or a.skip_nonfinite:
+        print('gradient guard:', trainer.guard_stats())        # the one host read of the guard's state
     return hist
 
 

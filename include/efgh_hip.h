@@ -55,7 +55,9 @@ const char *efgh_last_error(void);
  *      batch size and nothing called it.  Nothing else changed.
  *      Added later WITHOUT moving the number (no existing signature or struct changed): efgh_slice, efgh_slice_bwd,
  *      efgh_slice_bwd_workspace, efgh_offsets_invert, efgh_offsets_invert_workspace (the slice step of the BCL);
- *      efgh_lattice_index_bytes, efgh_lattice_index_build, efgh_lattice_locate (point query of a built level). */
+ *      efgh_lattice_index_bytes, efgh_lattice_index_build, efgh_lattice_locate (point query of a built level);
+ *      efgh_grad_guard_workspace, efgh_grad_guard_measure, efgh_adam_step_guarded and the struct efgh_guard_state (global-norm
+ *      clipping and non-finite-step skipping inside the fused optimizer step). */
 #define EFGH_ABI_VERSION 4
 int efgh_version(void);
 
@@ -604,6 +606,58 @@ int efgh_corr_unpad(const float *drp, int32_t B, int32_t h, int32_t w, int32_t C
  * caller's).  g is multiplied by grad_scale first (1/world for a summed all-reduce).          */
 int efgh_adam_step(float *w, const float *g, float *m, float *v, int64_t n, float lr, float beta1,
                    float beta2, float eps, float weight_decay, int32_t step, float grad_scale, void *stream);
+
+/* ---- gradient guard: global-norm clipping and non-finite-step skipping decided ON THE DEVICE (no host read) ----
+ * Replaces `torch.nn.utils.clip_grad_norm_(params, max_norm, norm_type=2, error_if_nonfinite=False)` and the
+ * `if torch.isfinite(norm): optimizer.step()` idiom around torch.optim.Adam: 353 small launches and a host synchronisation per step
+ * there, three launches here (measure, decide, Adam) with the decision left in a device-resident state block.
+ *
+ * The flat gradient g[n] is cut into nseg <= EFGH_GUARD_MAX_SEGMENTS contiguous segments (bounds[0] = 0 < bounds[1] < ... <
+ * bounds[nseg] = n, a HOST array read during the call).  Every segment is cut from its start into runs of EFGH_GUARD_RUN elements;
+ * a run is reduced by one workgroup, the runs of a segment are folded by the decide launch, both in trees that depend on the
+ * element indices only: the result does not depend on the launch grid, the CU count or the order workgroups finish in (no
+ * floating-point atomics).  Every element is widened to float64 before it is squared and all sums are float64.  Elements that
+ * are inf or NaN are counted per segment; the sum of a segment that holds one is not defined (inf or NaN), its count is exact. */
+#define EFGH_GUARD_MAX_SEGMENTS 8
+#define EFGH_GUARD_RUN 4096
+typedef struct efgh_guard_state {
+    double sumsq[EFGH_GUARD_MAX_SEGMENTS];      /* per segment: sum of g^2 of the SUMMED gradient (before grad_scale) */
+    double sumsq_total;                         /* sumsq[0] + sumsq[1] + ... in index order */
+    double norm;                                /* sqrt(sumsq_total) * grad_scale: the norm clip_grad_norm_ returns for the mean gradient */
+    int64_t nonfinite[EFGH_GUARD_MAX_SEGMENTS]; /* per segment: elements that are inf or NaN */
+    int64_t nonfinite_total;
+    int64_t applied;                            /* optimizer steps applied so far == Adam's step count t */
+    int64_t skipped;                            /* steps skipped because of a non-finite gradient */
+    float coef;                                 /* min(1, max_norm / (norm + 1e-6)) in float64, rounded once (torch's clip coefficient) */
+    float scale;                                /* grad_scale * coef: what efgh_adam_step_guarded multiplies g by */
+    float bc1;                                  /* 1 - beta1^applied */
+    float bc2_sqrt;                             /* sqrt(1 - beta2^applied) */
+    int32_t skip;                               /* 1: efgh_adam_step_guarded leaves w, m and v untouched */
+    int32_t nseg;
+} efgh_guard_state;
+/* bytes of the caller-owned workspace of efgh_grad_guard_measure for a gradient of n elements (one float64 and one int32 per run);
+ * -1 for n outside [1, 2^31) */
+int64_t efgh_grad_guard_workspace(int64_t n);
+/* measure + decide (two launches): fills *state (DEVICE memory, zeroed once by the caller before the first call; `applied` and
+ * `skipped` are carried from call to call) from g.
+ *   norm  = sqrt(sumsq_total) * grad_scale               (grad_scale = 1/world after a summed all-reduce: the mean gradient's norm)
+ *   coef  = min(1, max_norm / (norm + 1e-6))             (torch.nn.utils.clip_grad_norm_; max_norm = +inf: measure only, coef = 1;
+ *                                                         a non-finite norm gives the coefficient torch gives, NaN or 0: no repair)
+ *   skip_nonfinite != 0 and nonfinite_total != 0: skip = 1, skipped += 1, applied unchanged (optimizer.step() not called);
+ *   otherwise skip = 0, applied += 1.  The bias corrections are those of step `applied`.
+ * skip_nonfinite == 0: the step count cannot diverge from the caller's, who passes it as `step` >= 1: applied = step and the bias
+ * corrections are computed on the host exactly as efgh_adam_step computes them.  skip_nonfinite != 0: `step` is ignored, the count
+ * lives in *state.  `grid`: workgroups of the measure launch, 0 = the library's choice (the result does not depend on it).
+ * g 16-byte, workspace and state 8-byte aligned. */
+int efgh_grad_guard_measure(const float *g, int64_t n, const int64_t *bounds, int32_t nseg, double max_norm, float grad_scale,
+                            int32_t skip_nonfinite, float beta1, float beta2, int32_t step, void *workspace,
+                            efgh_guard_state *state, int32_t grid, void *stream);
+/* efgh_adam_step (torch.optim.Adam.step over all parameters) with the gradient scale, the bias corrections and the skip flag read from
+ * *state (device memory, written by efgh_grad_guard_measure earlier on the same stream) instead of passed by value.  With
+ * state->skip set nothing is written (the `optimizer.step()` that was not called).  With coef == 1 the result has the bits of
+ * efgh_adam_step(step = applied, grad_scale).  w, g, m, v 16-byte aligned as there. */
+int efgh_adam_step_guarded(float *w, const float *g, float *m, float *v, int64_t n, float lr, float beta1, float beta2,
+                           float eps, float weight_decay, const efgh_guard_state *state, void *stream);
 
 /* "thin" layers (<= 4 channels on one side: RGB/range/depth input convs, the 1-/2-channel heads and
  * their dgrad/wgrad): HBM-bound VALU kernels with the descriptor, gather modes and epilogue of

@@ -18,12 +18,14 @@ ap = argparse.ArgumentParser()
 ap.add_argument('--steps', type=int, default=40)
 ap.add_argument('--batch', type=int, default=8)
 ap.add_argument('--npts', type=int, nargs='+', default=[131072])
+ap.add_argument('--max-grad-norm', type=float, default=None, help='clip the global gradient norm inside the fused step')
+ap.add_argument('--skip-nonfinite', action='store_true', help='skip steps whose gradient holds inf / NaN')
 a = ap.parse_args()
 raw = (768, 2560)
 args = syn.default_args(raw, 'cuda')
 torch.manual_seed(0)
 model = EFGHBackbone(args).cuda()
-tr = Trainer(model, EFGHCriterion(args), lr=1e-4)
+tr = Trainer(model, EFGHCriterion(args), lr=1e-4, max_grad_norm=a.max_grad_norm, skip_nonfinite=a.skip_nonfinite)
 times, mem0 = [], None
 for it in range(a.steps):
     npts = a.npts[it % len(a.npts)]
@@ -47,3 +49,5 @@ for it in range(a.steps):
             list(lattice._SIZES.values())[-1]))
 print('median step %.1f ms, max after warm-up %.1f ms; allocated now vs step 3: %+.2f GB' % (
     sorted(times[3:])[len(times[3:]) // 2], max(times[3:]), (torch.cuda.memory_allocated() - mem0) / 1e9))
+if tr.opt.guarded:
+    print('gradient guard:', tr.guard_stats())
