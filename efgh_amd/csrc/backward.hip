@@ -733,8 +733,8 @@ extern "C" int efgh_corr1d_bwd(const float *rp, const float *cam, const float *c
     hipStream_t st = (hipStream_t)stream_;
     EFGH_CHECK_ARG(rp && cam && cam_mm && dlogit && dcam_n && drp && B > 0 && h > 0 && wc > 0 && wp >= wc);
     int nj = wp - wc + 1;
+    EFGH_CHECK_ARG((size_t)wc * 64 + (size_t)nj * 4 <= 64 * 1024);      // LDS of k_corr_bwd_rng: a rejected call launches nothing
     k_corr_bwd_cam<<<dim3(cdiv(wc * 4, TPB), h, B), TPB, 0, st>>>(rp, dlogit, h, wc, wp, nj, dcam_n);
-    EFGH_CHECK_ARG((size_t)wc * 64 + (size_t)nj * 4 <= 64 * 1024);
     k_corr_bwd_rng<<<dim3(cdiv(wp * 4, TPB * 4), h, B), TPB, (size_t)wc * 64 + (size_t)nj * 4, st>>>(cam, cam_mm, dlogit, h, wc, wp, nj,
                                                                                               drp);
     EFGH_CHECK_LAUNCH();

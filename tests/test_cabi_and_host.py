@@ -41,6 +41,24 @@ def test_header_symbols_exported(so_path):
     assert b'invalid argument' in lib.efgh_last_error()
 
 
+def test_corr1d_bwd_checks_its_lds_size_before_the_first_launch(so_path):
+    """wc * 64 + nj * 4 bytes of LDS must fit 64 KiB: the call is rejected before either of its two kernels is launched, so it
+    returns the argument error (not a launch error - there is no device here) and leaves dcam alone"""
+    lib = ctypes.CDLL(so_path)
+    lib.efgh_last_error.restype = ctypes.c_char_p
+    B, h, wc, wp = 1, 1, 1000, 2000                    # 64 000 + 4 004 > 65 536
+    f = lambda n, v: (ctypes.c_float * n)(*([v] * n))
+    rp, cam, mm, dl = f(h * wp * 16, 1.0), f(h * wc * 16, 1.0), f(2, 0.0), f(wp - wc + 1, 1.0)
+    mm[1] = 1.0
+    dcam, drp = f(h * wc * 16, -7777.0), f(h * wp * 16, -7777.0)
+    rc = lib.efgh_corr1d_bwd(rp, cam, mm, dl, ctypes.c_int32(B), ctypes.c_int32(h), ctypes.c_int32(wc), ctypes.c_int32(wp), dcam, drp,
+                             None)
+    assert rc == -1
+    msg = lib.efgh_last_error()
+    assert b'invalid argument' in msg and b'64 * 1024' in msg
+    assert all(v == -7777.0 for v in dcam) and all(v == -7777.0 for v in drp)
+
+
 def test_gemm_desc_layout_matches_header():
     from efgh_amd import _C
     # sizeof(efgh_gemm_desc) as the C compiler lays it out (LP64): checked against a tiny C probe
