@@ -118,6 +118,8 @@ def lib():
                                                  c_int32, c_float, c_float, c_int32, c_void_p, c_void_p, c_int32, c_void_p]
         _lib.efgh_adam_step_guarded.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_float, c_float, c_float,
                                                 c_float, c_float, c_void_p, c_void_p]
+        _lib.efgh_grad_drain.argtypes = [c_void_p, c_void_p, c_int64, c_int32, c_void_p]
+        _lib.efgh_gimg_valid_count.argtypes = [c_void_p, c_void_p, c_int32, c_int64, c_void_p, c_void_p]
     return _lib
 
 

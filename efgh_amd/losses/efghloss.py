@@ -133,8 +133,16 @@ class EFGHCriterion(nn.Module):
         (one 4-byte all-reduce, issued here in the forward, before any gradient bucket): the all-reduced mean of the ranks' losses
         and gradients then equals the single global loss EXACTLY, whatever the samples' valid-pixel counts
         (tests/test_gpu_dp.py::test_two_ranks_equal_dataparallel_on_the_real_net measures both forms).  The F term selects the same
-        number of scores per sample (positive_num * (1 + neg_ratio), loss_utils.py:96-115), so its mean needs no weight."""
+        number of scores per sample (positive_num * (1 + neg_ratio), loss_utils.py:96-115), so its mean needs no weight.
+
+        Gradient accumulation (Trainer.step_accumulated) is the same situation with micro-batches in place of ranks: the trainer
+        has counted the valid pixels of all micro-batches (and ranks) before the first forward and hands this micro-batch's weight
+        over in `ops.TLS.depth_weight` - a device scalar, or the float 1.0 for "plain mean of the micro-batch losses".  Then
+        nothing is all-reduced here.  With nothing handed over (None) this method is what it was."""
         import torch.distributed as dist
+        w = ops.TLS.depth_weight
+        if w is not None:
+            return l_dep if isinstance(w, float) else l_dep * w.reshape(()).detach()
         if not (self.dp_exact and dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1):
             return l_dep
         n_mean = n_valid.detach().clone().reshape(1)

@@ -71,9 +71,12 @@ class _ThreadState(threading.local):
     """per-thread switches (two Python threads may drive two models on one GPU; autograd's device thread is a third):
     train_step - inside a training step (forward: set by EFGHBackbone.forward; backward: GemmLayerFn.backward restores the value
     its forward saw); planes_split - the plane-GEMM precision of the layer being run (GemmLayerFn: resolved once in its forward,
-    restored in its backward); w2v_wanted - set by GemmLayerFn.forward around its launches when the weight gradient will be asked for"""
+    restored in its backward); w2v_wanted - set by GemmLayerFn.forward around its launches when the weight gradient will be asked for;
+    depth_weight - the g_depth weight of the micro-batch whose loss is being computed (Trainer.step_accumulated hands it to
+    EFGHCriterion._dp_weight_masked_mean: a one-element device tensor, or the float 1.0 for "no weight"; None: nothing handed over)"""
 
     def __init__(self):
+        self.depth_weight = None
         self.train_step = False
         self.w2v_wanted = False
         self.nbt_pending = None        # see bn_tick
@@ -1796,6 +1799,29 @@ def gimg_loss_fwd(pred_depth, pred_mask, gdep4, img_mask):
     _C.check(_L().efgh_gimg_loss_fwd(ptr(pred_depth), ptr(pred_mask), c_int64(pred_mask.stride(0)), ptr(gdep4), ptr(img_mask),
                                      c_int32(B), c_int64(H * W), ptr(gt_depth), ptr(gt_mask), ptr(part), ptr(out3), _st()))
     return out3, gt_depth, gt_mask
+
+
+def gimg_valid_count(gdep4, img_mask, count):
+    """count (a one-element int64 device tensor, e.g. a slice of a vector) += pixels with depth > 0 and mask > 0: the pixels
+    gimg_loss_fwd takes the masked depth mean over.  gdep4: [B][H][W][4] from depth_image, img_mask: uint8 [B][H][W]"""
+    _C.require_cuda(gdep4, img_mask, count)
+    _C.require_f32(gdep4)
+    if img_mask.dtype != torch.uint8 or count.dtype != torch.int64 or count.numel() != 1:
+        raise _C.EfghError('gimg_valid_count: img_mask must be uint8 and count one int64 element')
+    gdep4, img_mask = gdep4.contiguous(), img_mask.contiguous()
+    B, H, W, _ = gdep4.shape
+    if img_mask.numel() != B * H * W:
+        raise _C.EfghError('gimg_valid_count: img_mask has %d elements, the depth image %d pixels' % (img_mask.numel(), B * H * W))
+    _C.check(_L().efgh_gimg_valid_count(ptr(gdep4), ptr(img_mask), c_int32(B), c_int64(H * W), ptr(count), _st()))
+
+
+def grad_drain(acc, g, first):
+    """acc = g (first) or acc += g, then g = 0: one launch over two flat fp32 device buffers (train.GradAccumulator)"""
+    _C.require_cuda(acc, g)
+    _C.require_f32(acc, g)
+    if acc.numel() != g.numel() or not (acc.is_contiguous() and g.is_contiguous()):
+        raise _C.EfghError('grad_drain: acc and g must be contiguous and of equal size')
+    _C.check(_L().efgh_grad_drain(ptr(acc), ptr(g), c_int64(g.numel()), c_int32(1 if first else 0), _st()))
 
 
 def gimg_loss_bwd(pred_depth, pred_mask, gt_depth, img_mask, out3, g_depth, g_mask):

@@ -37,7 +37,8 @@ class FlatParams:
         # gradients written straight into the flat slices by the layer backward (nets/fn.py `claim_grad`) instead of handed to
         # autograd's AccumulateGrad (which costs an allocation, a copy and an `add` launch per parameter).  `arrived[i]` is set
         # by whichever route delivers parameter i's gradient first; later deliveries in the same step go through autograd and
-        # accumulate, so shared parameters and gradient accumulation over several backward calls keep their meaning.
+        # accumulate, so shared parameters keep their meaning.  A direct write OVERWRITES its slice: gradients of several backward
+        # calls are summed by draining this buffer into a second one in between (GradAccumulator), not by leaving them here.
         self.direct = True
         # BatchNorm's `num_batches_tracked` counters re-homed as views of ONE int64 vector: a training forward notes which layers
         # ran (GemmLayerFn.forward -> tick) and Trainer.step adds the whole step's counts with one launch instead of one per layer
@@ -119,6 +120,67 @@ class FlatParams:
                 p.grad = self.g[off:off + k].view(p.shape)
 
 
+class GradAccumulator:
+    """Sum of the flat gradient over the micro-batches of one optimizer step, in a second flat buffer `acc` (same shape and device
+    as flat.g, allocated on first use: 191 MB for the full net).  After every micro-batch's backward `drain()` moves flat.g into
+    acc - acc = g for the first micro-batch (acc is not read), acc = acc + g after that, one fp32 add per element - and leaves
+    flat.g zeroed and re-armed for the next backward, in ONE launch (efgh_grad_drain) and without an aten op.  The 1 / k factor is
+    not applied here: the optimizer reads acc with grad_scale = 1 / (k * world).  CPU tensors (the gloo plumbing tests run
+    FlatParams on the CPU) take copy_ / add_ / zero_, the same arithmetic."""
+
+    def __init__(self, flat):
+        self.flat, self.acc, self.count = flat, None, 0
+
+    def drain(self):
+        f = self.flat
+        if self.acc is None or self.acc.shape != f.g.shape or self.acc.device != f.g.device:
+            self.acc = torch.empty_like(f.g)
+        if f.g.is_cuda:
+            cur = torch.cuda.current_stream()
+            for s in ops.side_streams():               # weight gradients are written on side streams (see Trainer.step)
+                cur.wait_stream(s)
+            ops.grad_drain(self.acc, f.g, self.count == 0)
+        else:
+            if self.count == 0:
+                self.acc.copy_(f.g)
+            else:
+                self.acc.add_(f.g)
+            f.g.zero_()
+        # what zero_grad does, without the memset
+        f.arrived = [False] * len(f.params)
+        base = f.g.data_ptr()
+        for p, (off, k) in zip(f.params, f.offsets):   # autograd may have replaced .grad
+            if p.grad is None or p.grad.data_ptr() != base + 4 * off:
+                p.grad = f.g[off:off + k].view(p.shape)
+        self.count += 1
+        return self.count
+
+    def reset(self):
+        """ends an optimizer step: the next drain() starts a new sum (acc keeps its contents until then)"""
+        self.count = 0
+
+
+def split_micro_batches(pc, img, calib, A, gt, k):
+    """(pc, img, calib, A, gt) of batch size B -> k tuples of batch size B / k (slices of dimension 0, no copies).  Every entry of
+    `gt` must be a tensor or array with leading dimension B."""
+    if isinstance(k, bool) or not isinstance(k, int) or k < 1:
+        raise _C.EfghError('micro_batches must be an integer >= 1 (or None), got %r' % (k,))
+    B = int(pc.shape[0])
+    if B % k != 0:
+        raise _C.EfghError('micro_batches=%d does not divide the batch size %d' % (k, B))
+    for name, t in (('img', img), ('calib', calib), ('A', A)):
+        if not hasattr(t, 'shape') or len(t.shape) < 1 or int(t.shape[0]) != B:
+            raise _C.EfghError('micro_batches: %s has no leading batch dimension of %d (shape %s)'
+                               % (name, B, tuple(getattr(t, 'shape', ()))))
+    for name, t in gt.items():
+        if not hasattr(t, 'shape') or len(t.shape) < 1 or int(t.shape[0]) != B:
+            raise _C.EfghError("micro_batches: gt['%s'] has no leading batch dimension of %d (%s)"
+                               % (name, B, 'shape %s' % (tuple(t.shape),) if hasattr(t, 'shape') else type(t).__name__))
+    b = B // k
+    return [(pc[i * b:(i + 1) * b], img[i * b:(i + 1) * b], calib[i * b:(i + 1) * b], A[i * b:(i + 1) * b],
+             {name: t[i * b:(i + 1) * b] for name, t in gt.items()}) for i in range(k)]
+
+
 def allreduce_mean_(flat_g, world, bucket_elems=8 * 1024 * 1024):
     """sum all-reduce in ~32 MB buckets (fully connected xGMI: large messages, few of them); the 1/world
     factor is folded into the optimizer kernel.  No-op for world == 1."""
@@ -158,10 +220,15 @@ class OverlappedAllReduce:
         self.next_b, self.order = len(self.buckets) - 1, []
         self.main_stream = None           # the stream backward() is called on (set by start_step)
         self.written = [[] for _ in self.buckets]         # per bucket: events recorded behind the gradient writes into it
+        # set while gradients are accumulated over micro-batches (Trainer.step_accumulated): flat.g then holds ONE micro-batch's
+        # gradient, which must not go on the wire - deliveries are ignored and finish() issues nothing
+        self.paused = False
         if world > 1:
             flat.listeners.append(self._arrived)
 
     def _arrived(self, i, stream=None):
+        if self.paused:
+            return
         b = self.bucket_of[i]
         if self.flat.g.is_cuda:
             # an event right behind the write, on the stream that carries it: the bucket's all-reduce waits for exactly the work
@@ -204,7 +271,7 @@ class OverlappedAllReduce:
         self.written = [[] for _ in self.buckets]
 
     def finish(self):
-        if self.world <= 1:
+        if self.world <= 1 or self.paused:
             return
         for b in range(len(self.buckets) - 1, -1, -1):          # whatever is left (parameters without a gradient), same order
             self._launch(b)
@@ -310,28 +377,39 @@ class FusedAdam:
                 'norms': {name: float(st.sumsq[i]) ** 0.5 * gs for i, (name, _, _) in enumerate(self.segments)},
                 'coef': float(st.coef), 'nonfinite': int(st.nonfinite_total)}
 
-    def step(self, grad_scale=1.0):
+    def step(self, grad_scale=1.0, grad=None):
+        """`grad`: a flat fp32 buffer to read the gradient from instead of flat.g (GradAccumulator.acc: the sum over the
+        micro-batches, with grad_scale = 1 / (micro-batches * world)); None, the default, is flat.g"""
         _C.require_cuda(self.flat.w)
+        g = self.flat.g if grad is None else self._check_grad(grad)
         if self.guarded:
-            return self._step_guarded(grad_scale)
+            return self._step_guarded(grad_scale, g)
         self.t += 1
         f = self.flat
-        _C.check(_C.lib().efgh_adam_step(_C.ptr(f.w), _C.ptr(f.g), _C.ptr(self.m), _C.ptr(self.v), _C.c_int64(f.n),
+        _C.check(_C.lib().efgh_adam_step(_C.ptr(f.w), _C.ptr(g), _C.ptr(self.m), _C.ptr(self.v), _C.c_int64(f.n),
                                          _C.c_float(self.lr), _C.c_float(self.betas[0]), _C.c_float(self.betas[1]),
                                          _C.c_float(self.eps), _C.c_float(self.wd), _C.c_int32(self.t),
                                          _C.c_float(grad_scale), _C.stream_ptr()))
         ops.bump_epoch(self.flat.epoch)            # packed-weight / folded-BN caches are stale now
 
-    def _step_guarded(self, grad_scale):
+    def _check_grad(self, grad):
+        w = self.flat.w
+        if not (torch.is_tensor(grad) and grad.dtype == w.dtype and grad.device == w.device and grad.dim() == 1
+                and grad.numel() == self.flat.n and grad.is_contiguous()):
+            raise _C.EfghError('FusedAdam.step(grad=): expected a contiguous flat float32 buffer of %d elements on %s'
+                               % (self.flat.n, w.device))
+        return grad
+
+    def _step_guarded(self, grad_scale, g):
         f, lib, stream = self.flat, _C.lib(), _C.stream_ptr()
         if not self.skip_nonfinite:
             self._t += 1                           # (with skip_nonfinite the device counts: a skipped step is not one)
-        self._grad_scale = float(grad_scale)
+        self._grad_scale = _C.c_float(grad_scale).value      # as the kernels see it (an fp32 argument: 1/3 is not 1/3.0)
         max_norm = self.max_grad_norm if self.max_grad_norm is not None else float('inf')
-        _C.check(lib.efgh_grad_guard_measure(f.g.data_ptr(), f.n, self._bounds, len(self.segments), max_norm, grad_scale,
+        _C.check(lib.efgh_grad_guard_measure(g.data_ptr(), f.n, self._bounds, len(self.segments), max_norm, grad_scale,
                                              int(self.skip_nonfinite), self.betas[0], self.betas[1], self._t,
                                              self.workspace.data_ptr(), self.state.data_ptr(), 0, stream))
-        _C.check(lib.efgh_adam_step_guarded(f.w.data_ptr(), f.g.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), f.n, self.lr,
+        _C.check(lib.efgh_adam_step_guarded(f.w.data_ptr(), g.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), f.n, self.lr,
                                             self.betas[0], self.betas[1], self.eps, self.wd, self.state.data_ptr(), stream))
         ops.bump_epoch(self.flat.epoch)            # (also after a skipped step: the host does not know, a repack is harmless)
 
@@ -373,6 +451,7 @@ class Trainer:
         if self.world > 1:
             ops.reserve_comm_queue()
         self.base_lr, self.it = lr, 0
+        self.accum = None                                   # GradAccumulator of step_accumulated, built on first use
 
     def guard_stats(self):
         """FusedAdam.guard_stats(): {'applied', 'skipped', 'norm', 'norms': {segment: norm}, 'coef', 'nonfinite'} of the last step,
@@ -396,10 +475,49 @@ class Trainer:
         ops.bump_epoch()
         return self.it
 
-    def step(self, pc, img, calib, A, gt):
+    def _check_frozen(self):
         if tuple(bool(p.requires_grad) for p in self.flat.all_params) != self.flat.frozen:
             raise _C.EfghError('the set of trainable parameters changed after the Trainer was built (FlatParams snapshots '
                                'requires_grad): freeze parameters first, then construct the Trainer')
+
+    def _raw_size(self):
+        """(H, W) of the raw camera image: the criterion's, or - behind a wrapper that does not forward attributes - the model's"""
+        for owner in [self.criterion] + list(self.model.modules()):
+            raw = getattr(owner, 'raw_cam_img_size', None)
+            if raw is not None:
+                return int(raw[0]), int(raw[1])
+        raise _C.EfghError('step_accumulated(exact_depth_mean=True) needs raw_cam_img_size on the criterion or the model')
+
+    def depth_weights(self, micro_batches):
+        """g_depth weights of the micro-batches, w_i = n_i / mean(n) over all micro-batches (and ranks), as an fp32 device vector
+        [k]; 1 everywhere when no pixel is valid at all.  n_i, the valid pixels of micro-batch i, depends on its inputs only (point
+        cloud, cam_T_velo, img_mask): the ground-truth depth image is rasterised here as compute_loss will rasterise it, and
+        counted by efgh_gimg_valid_count into one int64 vector - all-reduced once when world > 1.  Nothing is read back."""
+        rawH, rawW = self._raw_size()
+        dev = self.flat.w.device
+        counts = torch.zeros(len(micro_batches), dtype=torch.int64, device=dev)
+        with torch.no_grad():
+            for i, (pc, _img, _calib, _A, gt) in enumerate(micro_batches):
+                gdep, _ = ops.depth_image(pc, torch.as_tensor(gt['cam_T_velo']).to(dev).float(), rawH, rawW)
+                imask = torch.as_tensor(gt['img_mask']).to(dev).to(torch.uint8).contiguous()
+                ops.gimg_valid_count(gdep, imask, counts[i:i + 1])
+                del gdep, imask
+            total = counts
+            if self.world > 1:                         # one small all-reduce per optimizer step (element i: micro-batch i of every rank)
+                total = counts.clone()
+                dist.all_reduce(total, op=dist.ReduceOp.SUM)
+            # float64 on the device (counts are exact there), ONE rounding to fp32; the zero-mean rule of _dp_weight_masked_mean
+            n = counts.double()
+            mean = total.sum().double() / float(len(micro_batches) * self.world)
+            w = torch.where(mean > 0, n / mean.clamp_min(1e-300), torch.ones_like(n))
+        return w.float()
+
+    def step(self, pc, img, calib, A, gt, micro_batches=None):
+        """one optimizer step on one batch.  `micro_batches=k`: the batch is cut into k equal chunks along dimension 0 whose
+        gradients are accumulated (step_accumulated): the activation memory of B / k samples, the update of B."""
+        if micro_batches is not None:
+            return self.step_accumulated(split_micro_batches(pc, img, calib, A, gt, micro_batches))
+        self._check_frozen()
         self.opt.lr = adjust_learning_rate(self.base_lr, self.it)
         ops.w2v_clear()
         self.flat.uses = [0] * len(self.flat.params)
@@ -421,3 +539,69 @@ class Trainer:
         self.opt.step(grad_scale=1.0 / self.world)
         self.it += 1
         return losses, pred
+
+    def step_accumulated(self, micro_batches, exact_depth_mean=True):
+        """ONE optimizer step on the gradient accumulated over k >= 1 micro-batches, a sequence of (pc, img, calib, A, gt) tuples
+        of equal batch size: per micro-batch forward, loss and backward into the zeroed flat gradient exactly as `step` runs them,
+        then GradAccumulator.drain(); each micro-batch's graph is gone before the next forward, so the activation memory is that
+        of ONE micro-batch.  After the last drain the sum is all-reduced once (world > 1; not overlapped with backward - the
+        bucket listeners are paused meanwhile) and the optimizer kernels read it with grad_scale = 1 / (k * world).
+
+        The meaning is that of k data-parallel ranks (`torch.nn.DataParallel` replicas): one loss over the global batch, BatchNorm
+        statistics per micro-batch.  Every term of efghloss is a batch mean except g_depth, a mean over the valid pixels of the
+        whole batch: with `exact_depth_mean` micro-batch i's term is weighted by n_i / mean(n) (depth_weights: counted on the
+        device before the first forward, no host read); False takes the plain mean of the micro-batch losses.
+
+        Once per call: `it`, the learning-rate schedule and Adam's step count advance.  Per micro-batch, as torch would: BatchNorm's
+        running statistics and num_batches_tracked.  With skip_nonfinite a non-finite value in any micro-batch's gradient reaches
+        the sum and the whole accumulated step is skipped.
+        -> (losses, preds): the criterion's `loss_name` entries as detached device scalars of the global batch (the mean over the
+        micro-batches of their weighted terms), and the list of the k prediction dicts (detached)."""
+        mbs = [tuple(mb) for mb in micro_batches]
+        if not mbs or any(len(mb) != 5 for mb in mbs):
+            raise _C.EfghError('step_accumulated takes a sequence of k >= 1 tuples (pc, img, calib, A, gt)')
+        sizes = [int(mb[0].shape[0]) for mb in mbs]
+        if len(set(sizes)) != 1:
+            raise _C.EfghError('step_accumulated: the micro-batches must have equal batch sizes, got %s' % sizes)
+        self._check_frozen()
+        k = len(mbs)
+        self.opt.lr = adjust_learning_rate(self.base_lr, self.it)
+        weights = self.depth_weights(mbs) if exact_depth_mean else None
+        if self.accum is None:
+            self.accum = GradAccumulator(self.flat)
+        acc = self.accum
+        acc.reset()
+        self.model.train()
+        names = list(getattr(self.criterion, 'loss_name', None) or [])
+        rows, preds = [], []
+        paused, self.comm.paused = self.comm.paused, True
+        try:
+            for i, (pc, img, calib, A, gt) in enumerate(mbs):
+                ops.w2v_clear()
+                self.flat.uses = [0] * len(self.flat.params)
+                self.flat.collect_ticks = True
+                try:
+                    pred = self.model(pc, img, calib, A)
+                finally:
+                    self.flat.flush_ticks()
+                ops.TLS.depth_weight = weights[i] if weights is not None else 1.0
+                try:
+                    losses = self.criterion.compute_loss(pc, img, calib, A, gt, pred)[0]
+                finally:
+                    ops.TLS.depth_weight = None
+                if i == 0:
+                    self.flat.zero_grad()             # (later micro-batches find the buffer zeroed and re-armed by drain)
+                losses['total'].backward()
+                acc.drain()                           # (joins the side streams first, as `step` does after backward)
+                names = names or list(losses)
+                rows.append(torch.stack([losses[n].detach().reshape(()) for n in names]))
+                preds.append({n: (v.detach() if torch.is_tensor(v) else v) for n, v in pred.items()})
+                del losses, pred
+        finally:
+            self.comm.paused = paused
+        allreduce_mean_(acc.acc, self.world)
+        self.opt.step(grad_scale=1.0 / (k * self.world), grad=acc.acc)
+        acc.reset()
+        self.it += 1
+        mean = rows[0] if k == 1 else torch.stack(rows).sum(0) / k
+        return {n: mean[j] for j, n in enumerate(names)}, preds

@@ -3,6 +3,7 @@
 loop of the reference's iterater.py:25-60 with nothing on the CPU between the decoded frame and the optimizer step.
 
     python examples/train_synthetic.py --iters 3 --raw 128 256 --points 2048
+    python examples/train_synthetic.py --iters 3 --batch 4 --accumulate 2        # gradient accumulation over micro-batches
 """
 import argparse
 import os
@@ -47,6 +48,8 @@ def main(argv=None):
     ap.add_argument('--points', type=int, default=2048)
     ap.add_argument('--max-grad-norm', type=float, default=None, help='clip the global gradient norm (torch clip_grad_norm_) inside the fused step')
     ap.add_argument('--skip-nonfinite', action='store_true', help='leave weights and Adam moments untouched on a step whose gradient holds inf / NaN')
+    ap.add_argument('--accumulate', type=int, default=None, metavar='K',
+                    help='cut every batch into K micro-batches and accumulate their gradients: the update of --batch, the memory of --batch / K')
     a = ap.parse_args(argv)
     raw = tuple(a.raw)
     args = syn.default_args(raw, 'cuda')
@@ -67,7 +70,11 @@ def main(argv=None):
             sweep = np.concatenate([syn.lidar_sweep(a.points * 2, seed).T, np.ones((a.points * 2, 1), np.float32)], 1)
             samples.append(prep(sweep, raw_frame(raw, seed), {'P2': P2, 'Tr': np.eye(4)}, np.eye(4), 'f%06d' % seed)[:5])
         pc, img, calib, A, gt = collate(samples, 'cuda')
-        losses, pred = trainer.step(pc, img, calib, A, gt)
+        if a.accumulate:                                     # one loss over the whole batch, BatchNorm statistics per micro-batch
+            losses, preds = trainer.step(pc, img, calib, A, gt, micro_batches=a.accumulate)
+            pred = {k: (torch.cat([p[k] for p in preds], 0) if torch.is_tensor(preds[0][k]) and preds[0][k].dim() else preds[0][k]) for k in preds[0]}
+        else:
+            losses, pred = trainer.step(pc, img, calib, A, gt)
         err.update({'sensor2_T_sensor1': gt['sensor2_T_sensor1'].float().cuda()}, pred)
         hist.append(float(losses['total'].detach()))
         print('iter %d  total %.4f  %s' % (it, hist[-1], '  '.join('%s %.3f' % kv for kv in err.dict.items())))

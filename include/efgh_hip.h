@@ -57,7 +57,8 @@ const char *efgh_last_error(void);
  *      efgh_slice_bwd_workspace, efgh_offsets_invert, efgh_offsets_invert_workspace (the slice step of the BCL);
  *      efgh_lattice_index_bytes, efgh_lattice_index_build, efgh_lattice_locate (point query of a built level);
  *      efgh_grad_guard_workspace, efgh_grad_guard_measure, efgh_adam_step_guarded and the struct efgh_guard_state (global-norm
- *      clipping and non-finite-step skipping inside the fused optimizer step). */
+ *      clipping and non-finite-step skipping inside the fused optimizer step);
+ *      efgh_grad_drain, efgh_gimg_valid_count (gradient accumulation over micro-batches). */
 #define EFGH_ABI_VERSION 4
 int efgh_version(void);
 
@@ -658,6 +659,24 @@ int efgh_grad_guard_measure(const float *g, int64_t n, const int64_t *bounds, in
  * efgh_adam_step(step = applied, grad_scale).  w, g, m, v 16-byte aligned as there. */
 int efgh_adam_step_guarded(float *w, const float *g, float *m, float *v, int64_t n, float lr, float beta1, float beta2,
                            float eps, float weight_decay, const efgh_guard_state *state, void *stream);
+
+/* ---- gradient accumulation over micro-batches: a second flat buffer `acc` that the flat gradient g is DRAINED into after every
+ * micro-batch's backward; the optimizer entry points above then read acc instead of g (they take the gradient pointer) with
+ * grad_scale = 1 / (micro-batches * world).  No kernel that writes g knows about accumulation.
+ *
+ * efgh_grad_drain: one pass over n elements,
+ *   first != 0:  acc[i] = g[i]              (acc is NOT read: it may hold garbage or NaN; -0 stays -0)     12 n bytes
+ *   first == 0:  acc[i] = acc[i] + g[i]     (ONE IEEE fp32 add, no scale: after k drains acc holds the bits of the sequential
+ *                                            sum ((g1 + g2) + g3) + ...; inf / NaN propagate as the add propagates them)   16 n bytes
+ *   and in both cases g[i] = +0 afterwards (the memset of the next micro-batch's zero_grad).
+ * acc and g 16-byte aligned and not overlapping; acc == g, a null pointer or n < 1: EFGH_E_INVALID, nothing is launched. */
+int efgh_grad_drain(float *acc, float *g, int64_t n, int32_t first, void *stream);
+/* *count (DEVICE memory, 8-byte aligned, carried from call to call: the caller zeroes it) += the number of pixels of the
+ * rasterised ground-truth depth image gdep4[B][HW][4] (efgh_depth_image; depth = channel 3) with depth > 0 and img_mask[B][HW] > 0:
+ * the pixels efgh_gimg_loss_fwd takes its masked depth mean over (a NaN depth is not valid).  An exact integer, whatever the order
+ * the workgroups finish in.  Used to weight the micro-batches' g_depth terms by their valid-pixel counts BEFORE their forwards run
+ * (the counts depend on the inputs only), so that the accumulated loss is the one loss over the global batch. */
+int efgh_gimg_valid_count(const float *gdep4, const uint8_t *img_mask, int32_t B, int64_t HW, int64_t *count, void *stream);
 
 /* "thin" layers (<= 4 channels on one side: RGB/range/depth input convs, the 1-/2-channel heads and
  * their dgrad/wgrad): HBM-bound VALU kernels with the descriptor, gather modes and epilogue of
