@@ -58,6 +58,12 @@ class GuardState(ctypes.Structure):
                 ('skip', c_int32), ('nseg', c_int32)]
 
 
+class TxnState(ctypes.Structure):
+    """mirror of efgh_txn_state (include/efgh_hip.h): the device-resident record of the transactional BatchNorm state"""
+    _fields_ = [('forward_nonfinite', c_int64), ('rolled_back', c_int64), ('vetoed_total', c_int64),
+                ('first_bad', c_int32), ('vetoed', c_int32)]
+
+
 WROTE_OUT = 1            # EFGH_WROTE_OUT
 
 
@@ -120,6 +126,11 @@ def lib():
                                                 c_float, c_float, c_void_p, c_void_p]
         _lib.efgh_grad_drain.argtypes = [c_void_p, c_void_p, c_int64, c_int32, c_void_p]
         _lib.efgh_gimg_valid_count.argtypes = [c_void_p, c_void_p, c_int32, c_int64, c_void_p, c_void_p]
+        _lib.efgh_txn_snapshot.argtypes = [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]
+        _lib.efgh_txn_probe.argtypes = [c_void_p, c_void_p, c_int64, c_void_p, c_int32, c_void_p, c_int32, c_int64, c_void_p,
+                                        c_void_p]
+        _lib.efgh_txn_resolve.argtypes = [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_float,
+                                          c_float, c_void_p]
     return _lib
 
 

@@ -1824,6 +1824,46 @@ def grad_drain(acc, g, first):
     _C.check(_L().efgh_grad_drain(ptr(acc), ptr(g), c_int64(g.numel()), c_int32(1 if first else 0), _st()))
 
 
+def _txn_vectors(name, live_f, shadow_f, live_c, shadow_c):
+    _C.require_cuda(live_f, shadow_f, live_c, shadow_c)
+    _C.require_f32(live_f, shadow_f)
+    if live_f.numel() != shadow_f.numel() or live_c.numel() != shadow_c.numel() or live_c.dtype != torch.int64 \
+            or shadow_c.dtype != torch.int64 or not all(t.is_contiguous() for t in (live_f, shadow_f, live_c, shadow_c)):
+        raise _C.EfghError('%s: live and shadow must be contiguous float32 / int64 vectors of equal sizes' % name)
+
+
+def txn_snapshot(live_f, shadow_f, live_c, shadow_c, txn):
+    """shadow = live (running statistics and counters) and the per-step fields of the txn block cleared: one launch
+    (train.BnTransaction).  `txn`: the uint8 device tensor holding an efgh_txn_state"""
+    _txn_vectors('txn_snapshot', live_f, shadow_f, live_c, shadow_c)
+    _C.check(_L().efgh_txn_snapshot(live_f.data_ptr(), shadow_f.data_ptr(), live_f.numel(), live_c.data_ptr(), shadow_c.data_ptr(),
+                                    live_c.numel(), txn.data_ptr(), _st()))
+
+
+def txn_probe(live_f, shadow_f, starts, txn, losses=None, k=0, stride=1, offset=0):
+    """counts what became non-finite in live since the snapshot, and the non-finite ones of the k float32 device scalars
+    losses[offset + j * stride] (j < k; `losses` contiguous, any shape), into the txn block: one launch.  `starts`: int64 device
+    table of nseg + 1 buffer starts"""
+    _C.require_cuda(live_f, shadow_f, starts, losses)
+    _C.require_f32(live_f, shadow_f, losses)
+    if live_f.numel() != shadow_f.numel() or starts.dtype != torch.int64 or starts.numel() < 2:
+        raise _C.EfghError('txn_probe: live and shadow must have equal sizes and starts be an int64 table of nseg + 1 entries')
+    if k and (losses is None or not losses.is_contiguous() or stride < 1 or offset < 0
+              or offset + (k - 1) * stride >= losses.numel()):
+        raise _C.EfghError('txn_probe: %d loss scalars at offset %d, stride %d do not fit the given (contiguous) tensor'
+                           % (k, offset, stride))
+    _C.check(_L().efgh_txn_probe(live_f.data_ptr(), shadow_f.data_ptr(), live_f.numel(), starts.data_ptr(), starts.numel() - 1,
+                                 losses.data_ptr() + 4 * offset if k else 0, k, stride, txn.data_ptr(), _st()))
+
+
+def txn_resolve(live_f, shadow_f, live_c, shadow_c, guard, txn, beta1, beta2):
+    """between the guard's measure / decide and the guarded Adam: a non-finite forward vetoes the step in the guard block, a skipped
+    step puts live back to shadow: one launch"""
+    _txn_vectors('txn_resolve', live_f, shadow_f, live_c, shadow_c)
+    _C.check(_L().efgh_txn_resolve(live_f.data_ptr(), shadow_f.data_ptr(), live_f.numel(), live_c.data_ptr(), shadow_c.data_ptr(),
+                                   live_c.numel(), guard.data_ptr(), txn.data_ptr(), beta1, beta2, _st()))
+
+
 def gimg_loss_bwd(pred_depth, pred_mask, gt_depth, img_mask, out3, g_depth, g_mask):
     B, _, H, W = pred_depth.shape
     d_depth = torch.empty_like(pred_depth)

@@ -160,6 +160,125 @@ class GradAccumulator:
         self.count = 0
 
 
+class BnTransaction:
+    """The BatchNorm state a training forward writes - running_mean / running_var of every `_BatchNorm` module that tracks running
+    statistics (frozen sub-networks included: they update theirs in train mode too) and the num_batches_tracked counters - held so
+    that a skipped optimizer step can put it back (Trainer(skip_nonfinite=True, transactional=True)).
+
+    The float buffers are re-homed as views of ONE fp32 vector `live`, as FlatParams re-homes the counters in `flat.nbt`: values
+    bit for bit, state_dict names / shapes / order unchanged, and load_state_dict / Trainer.load_checkpoint keep working because
+    they copy in place.  Every buffer starts on a 512-byte boundary of `live` (ALIGN elements: the alignment its own allocation
+    had, so no kernel that reads it through a raw pointer sees anything new); the padding is zero, is never written and belongs to
+    the buffer in front of it.  `shadow_f` / `shadow_c` hold the snapshot, `starts` (device, int64) the buffer starts.
+
+    Per optimizer step: snapshot() before the first forward, probe() after the last one, resolve() between the guard's decision
+    and the Adam launch - one HIP launch each (efgh_txn_*), no host read, no aten op.  CPU tensors (the host suite) take plain
+    torch operations with the same arithmetic, and the block is a host struct.  snapshot() checks by data_ptr that every view
+    still aliases `live` / `flat.nbt`: a model.to() / .double() / rebinding after construction raises EfghError naming the
+    buffer - there is no silent fall-back, the point is a guarantee."""
+    ALIGN = 128
+
+    def __init__(self, model, flat):
+        bns = flat._bns
+        if not bns:
+            raise _C.EfghError('transactional: the model has no BatchNorm layer that tracks running statistics')
+        prefix = {id(m): (name + '.' if name else '') for name, m in model.named_modules()}
+        dev = flat.nbt.device
+        self.flat, self.bns, self.names, self.slots = flat, bns, [], []
+        off = 0
+        for m in bns:
+            for attr in ('running_mean', 'running_var'):
+                b = getattr(m, attr)
+                name = prefix[id(m)] + attr
+                if not torch.is_tensor(b) or b.dtype != torch.float32 or b.device != dev:
+                    raise _C.EfghError('transactional: %s must be a float32 tensor on %s' % (name, dev))
+                self.names.append(name)
+                self.slots.append((m, attr, off, b.numel()))
+                off += -(-b.numel() // self.ALIGN) * self.ALIGN
+        self.nf = off
+        self.live = torch.zeros(off, dtype=torch.float32, device=dev)
+        for m, attr, a, k in self.slots:
+            b = getattr(m, attr)
+            self.live[a:a + k].copy_(b.detach().reshape(-1))
+            setattr(m, attr, self.live[a:a + k].view(b.shape))
+        self.shadow_f = torch.zeros_like(self.live)
+        self.shadow_c = torch.zeros_like(flat.nbt)
+        self._starts = [a for _, _, a, _ in self.slots] + [off]
+        self.starts = torch.tensor(self._starts, dtype=torch.int64).to(dev)
+        self.cuda = self.live.is_cuda
+        # the efgh_txn_state: a device block (FusedAdam re-points it behind its guard block, so that guard_stats() reads both
+        # with one copy), or a host struct for CPU tensors
+        self.block = torch.zeros(_C.ctypes.sizeof(_C.TxnState), dtype=torch.uint8, device=dev) if self.cuda else None
+        self.host = None if self.cuda else _C.TxnState()
+
+    def forward_count(self):
+        """txn->forward_nonfinite as a one-element int64 view of the device block (the data-parallel all-reduce's operand)"""
+        off = _C.TxnState.forward_nonfinite.offset
+        return self.block[off:off + 8].view(torch.int64)
+
+    def check(self):
+        base, cbase = self.live.data_ptr(), self.flat.nbt.data_ptr()
+        for name, (m, attr, a, k) in zip(self.names, self.slots):
+            if getattr(m, attr).data_ptr() != base + 4 * a:
+                raise _C.EfghError('transactional: %s no longer aliases the transaction\'s buffer (model.to() / .double() / a '
+                                   'rebinding after the Trainer was built): build the Trainer last' % name)
+        for j, m in enumerate(self.bns):
+            if m.num_batches_tracked.data_ptr() != cbase + 8 * j:
+                name = self.names[2 * j].rsplit('running_mean', 1)[0] + 'num_batches_tracked'
+                raise _C.EfghError('transactional: %s no longer aliases the flat counter vector (model.to() / a rebinding after '
+                                   'the Trainer was built): build the Trainer last' % name)
+
+    def snapshot(self):
+        """before the first forward of an optimizer step, on the stream the forward is called on (its side streams fork from
+        that stream afterwards, and the previous step joined them): shadow = live, per-step fields cleared"""
+        self.check()
+        if self.cuda:
+            ops.txn_snapshot(self.live, self.shadow_f, self.flat.nbt, self.shadow_c, self.block)
+            return
+        self.shadow_f.copy_(self.live)
+        self.shadow_c.copy_(self.flat.nbt)
+        self.host.forward_nonfinite, self.host.first_bad, self.host.vetoed = 0, -1, 0
+
+    def probe(self, losses=None, k=0, stride=1, offset=0):
+        """after the last forward, side streams joined: counts the elements of `live` that are inf / NaN now and were finite at the
+        snapshot, plus the non-finite ones of the k float32 scalars losses.reshape(-1)[offset + j * stride] (losses contiguous)"""
+        if self.cuda:
+            ops.txn_probe(self.live, self.shadow_f, self.starts, self.block, losses, k, stride, offset)
+            return
+        new = ~torch.isfinite(self.live) & torch.isfinite(self.shadow_f)
+        count = int(new.sum())
+        if count:
+            first = int(torch.nonzero(new)[0])
+            seg = max(s for s, a in enumerate(self._starts[:-1]) if a <= first)
+            self.host.first_bad = seg if self.host.first_bad < 0 else min(self.host.first_bad, seg)
+        if k:
+            count += int((~torch.isfinite(losses.detach().reshape(-1)[offset:offset + (k - 1) * stride + 1:stride])).sum())
+        self.host.forward_nonfinite += count
+
+    def resolve(self, guard=None, betas=(0.9, 0.999), skip=None):
+        """between the guard's decision and the Adam launch.  GPU: `guard` is the device block efgh_grad_guard_measure wrote; a
+        non-finite forward vetoes the step there.  CPU: `skip` is the guard's own decision (a bool), the final one is returned."""
+        if self.cuda:
+            ops.txn_resolve(self.live, self.shadow_f, self.flat.nbt, self.shadow_c, guard, self.block, betas[0], betas[1])
+            return None
+        h = self.host
+        if h.forward_nonfinite != 0 and not skip:
+            h.vetoed, h.vetoed_total, skip = 1, h.vetoed_total + 1, True
+        if skip:
+            self.live.copy_(self.shadow_f)
+            self.flat.nbt.copy_(self.shadow_c)
+            h.rolled_back += 1
+        return bool(skip)
+
+    def stats(self, st=None):
+        """the four transactional keys of guard_stats() from an efgh_txn_state (None: this object's own block, one device read)"""
+        if st is None:
+            st = self.host if not self.cuda else _C.TxnState.from_buffer_copy(self.block.cpu().numpy().tobytes())
+        named = st.forward_nonfinite != 0 and 0 <= st.first_bad < len(self.names)
+        return {'forward_nonfinite': int(st.forward_nonfinite), 'vetoed': int(st.vetoed), 'rolled_back': int(st.rolled_back),
+                'first_bad_buffer': self.names[st.first_bad] if named else None}
+
+
 def split_micro_batches(pc, img, calib, A, gt, k):
     """(pc, img, calib, A, gt) of batch size B -> k tuples of batch size B / k (slices of dimension 0, no copies).  Every entry of
     `gt` must be a tensor or array with leading dimension B."""
@@ -317,15 +436,21 @@ class FusedAdam:
       skip_nonfinite  a step whose gradient holds an inf or NaN leaves weights and moments untouched and does not count as a step
                       (`optimizer.step()` not called); without it non-finite values propagate as in torch
       segments        [(name, start, end)] cutting [0, n) into at most 8 contiguous pieces whose norms are reported separately
+      txn             a BnTransaction (needs skip_nonfinite): its resolve launch runs between decide and Adam, so a non-finite forward
+                      skips the step too and every skipped step restores BatchNorm's running statistics and counters; its state
+                      block lives behind the guard's, and guard_stats() reports both from its one read
     A guarded step is three launches (measure, decide, Adam): the norm, the clip coefficient and the skip decision stay in a
     device-resident state block, nothing is read back.  In a data-parallel run the measure pass sees the all-reduced (summed)
     gradient, which is bit-identical on every rank, so every rank takes the same decision.  `guard_stats()` reads the block.
     With skip_nonfinite the step count `t` lives on the device too (reading `opt.t` costs one device read)."""
 
     def __init__(self, flat, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_grad_norm=None,
-                 skip_nonfinite=False, segments=None):
+                 skip_nonfinite=False, segments=None, txn=None):
         self.max_grad_norm = check_max_grad_norm(max_grad_norm)
         self.skip_nonfinite = bool(skip_nonfinite)
+        if txn is not None and not self.skip_nonfinite:
+            raise _C.EfghError('a transactional step needs skip_nonfinite=True: only a skipped step is rolled back')
+        self.txn = txn
         self.guarded = self.max_grad_norm is not None or self.skip_nonfinite
         self.flat, self.lr, self.betas, self.eps, self.wd = flat, lr, betas, eps, weight_decay
         self.m = torch.zeros_like(flat.w)
@@ -344,7 +469,11 @@ class FusedAdam:
             nbytes = _C.lib().efgh_grad_guard_workspace(flat.n)
             if nbytes < 0:
                 raise _C.EfghError('the gradient guard handles 1 <= n < 2^31 parameters, got %d' % flat.n)
-            self.state = torch.zeros(_C.ctypes.sizeof(_C.GuardState), dtype=torch.uint8, device=flat.w.device)
+            nstate = _C.ctypes.sizeof(_C.GuardState)
+            self.state = torch.zeros(nstate + (_C.ctypes.sizeof(_C.TxnState) if txn is not None else 0), dtype=torch.uint8,
+                                     device=flat.w.device)
+            if txn is not None and txn.cuda:
+                txn.block = self.state[nstate:]
             self.workspace = torch.empty(nbytes, dtype=torch.uint8, device=flat.w.device)
             self._grad_scale = 1.0
 
@@ -362,20 +491,30 @@ class FusedAdam:
             off = _C.GuardState.applied.offset
             self.state[off:off + 8].view(torch.int64).fill_(self._t)
 
+    def _read_raw(self):
+        return self.state.cpu().numpy().tobytes()
+
     def _read_state(self):
-        return _C.GuardState.from_buffer_copy(self.state.cpu().numpy().tobytes())
+        return _C.GuardState.from_buffer_copy(self._read_raw())
 
     def guard_stats(self):
         """what the guard saw at the last step and did so far, from ONE device read: applied / skipped step counts, `norm` (global
         2-norm of the gradient as applied, i.e. of the mean gradient over the ranks), `norms` per segment, the clip coefficient
-        `coef` and the number of non-finite gradient elements"""
+        `coef` and the number of non-finite gradient elements.  With a BnTransaction also `forward_nonfinite` (BatchNorm statistics
+        that became non-finite in the last step's forwards + non-finite losses; summed over the ranks), `vetoed` (1: the last step
+        was skipped because of the forward alone), `rolled_back` (steps restored so far) and `first_bad_buffer` (state_dict key of
+        the first spoiled buffer on THIS rank, or None)"""
         if not self.guarded:
             raise _C.EfghError('guard_stats(): the gradient guard is off (construct with max_grad_norm= and / or skip_nonfinite=True)')
-        st = self._read_state()
+        raw = self._read_raw()
+        st = _C.GuardState.from_buffer_copy(raw)
         gs = self._grad_scale
-        return {'applied': int(st.applied), 'skipped': int(st.skipped), 'norm': float(st.norm),
-                'norms': {name: float(st.sumsq[i]) ** 0.5 * gs for i, (name, _, _) in enumerate(self.segments)},
-                'coef': float(st.coef), 'nonfinite': int(st.nonfinite_total)}
+        out = {'applied': int(st.applied), 'skipped': int(st.skipped), 'norm': float(st.norm),
+               'norms': {name: float(st.sumsq[i]) ** 0.5 * gs for i, (name, _, _) in enumerate(self.segments)},
+               'coef': float(st.coef), 'nonfinite': int(st.nonfinite_total)}
+        if self.txn is not None:
+            out.update(self.txn.stats(_C.TxnState.from_buffer_copy(raw, _C.ctypes.sizeof(_C.GuardState)) if self.txn.cuda else None))
+        return out
 
     def step(self, grad_scale=1.0, grad=None):
         """`grad`: a flat fp32 buffer to read the gradient from instead of flat.g (GradAccumulator.acc: the sum over the
@@ -409,6 +548,8 @@ class FusedAdam:
         _C.check(lib.efgh_grad_guard_measure(g.data_ptr(), f.n, self._bounds, len(self.segments), max_norm, grad_scale,
                                              int(self.skip_nonfinite), self.betas[0], self.betas[1], self._t,
                                              self.workspace.data_ptr(), self.state.data_ptr(), 0, stream))
+        if self.txn is not None:                   # veto / restore: after decide, before Adam reads state->skip, same stream
+            self.txn.resolve(self.state, self.betas)
         _C.check(lib.efgh_adam_step_guarded(f.w.data_ptr(), g.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), f.n, self.lr,
                                             self.betas[0], self.betas[1], self.eps, self.wd, self.state.data_ptr(), stream))
         ops.bump_epoch(self.flat.epoch)            # (also after a skipped step: the host does not know, a repack is harmless)
@@ -427,11 +568,22 @@ class Trainer:
     all-reduced sum, which holds the same bits on every rank: all ranks clip by the same coefficient and skip the same steps, so
     no rank waits for another's `optimizer.step()`.  The norms are reported per sub-network (`E`, `H`, `F`, `G`: the runs of
     equal top-level module name in flat parameter order; one segment `all` if there were more than 8).  `step` never reads the
-    guard's state; `guard_stats()` does, once per call.  The guard protects weights and moments from non-finite GRADIENTS: a NaN
-    that appears in the training forward has reached BatchNorm's running statistics before the guard runs and is not rolled back."""
+    guard's state; `guard_stats()` does, once per call.
 
-    def __init__(self, model, criterion, lr=1e-4, weight_decay=0.0, max_grad_norm=None, skip_nonfinite=False):
+    On its own the guard protects weights, moments and the step count from non-finite GRADIENTS; BatchNorm's running statistics
+    and num_batches_tracked have been written by the forward (of every micro-batch) before it runs, and the deferred activations
+    can hide a NaN forward from the loss altogether.  `transactional=True` (needs skip_nonfinite=True, off by default: nothing is
+    allocated, re-homed or launched then) makes a skipped step all or nothing: the BatchNorm state is snapshotted before the first
+    forward (BnTransaction), a probe after the last forward counts running statistics that became inf / NaN and non-finite `total`
+    losses - such a step is skipped even when its gradient came out finite - and a skipped step restores statistics and counters,
+    for an accumulated step those of ALL its micro-batches.  Three more launches per optimizer step, no host read; with world > 1
+    one 8-byte all-reduce of the count, so that every rank takes the same decision and restores its own buffers.  `guard_stats()`
+    then also reports `forward_nonfinite`, `vetoed`, `rolled_back` and `first_bad_buffer`.  Only BatchNorm buffers are rolled back."""
+
+    def __init__(self, model, criterion, lr=1e-4, weight_decay=0.0, max_grad_norm=None, skip_nonfinite=False, transactional=False):
         max_grad_norm = check_max_grad_norm(max_grad_norm)                       # (before anything is re-homed or broadcast)
+        if transactional and not skip_nonfinite:
+            raise _C.EfghError('transactional=True needs skip_nonfinite=True: only a skipped step is rolled back')
         self.model, self.criterion = model, criterion
         self.world = dist.get_world_size() if dist.is_initialized() else 1
         self.flat = FlatParams(model)
@@ -445,8 +597,9 @@ class Trainer:
         if max_grad_norm is not None or skip_nonfinite:
             names = [k for k, p in model.named_parameters() if p.requires_grad]
             segments = name_segments(names, [k for _, k in self.flat.offsets])
+        self.txn = BnTransaction(model, self.flat) if transactional else None     # (after the broadcast: it copies the values)
         self.opt = FusedAdam(self.flat, lr=lr, weight_decay=weight_decay, max_grad_norm=max_grad_norm,
-                             skip_nonfinite=skip_nonfinite, segments=segments)
+                             skip_nonfinite=skip_nonfinite, segments=segments, txn=self.txn)
         self.comm = OverlappedAllReduce(self.flat, self.world)
         if self.world > 1:
             ops.reserve_comm_queue()
@@ -454,9 +607,22 @@ class Trainer:
         self.accum = None                                   # GradAccumulator of step_accumulated, built on first use
 
     def guard_stats(self):
-        """FusedAdam.guard_stats(): {'applied', 'skipped', 'norm', 'norms': {segment: norm}, 'coef', 'nonfinite'} of the last step,
-        from one device read made here and nowhere else; EfghError when the guard is off"""
+        """FusedAdam.guard_stats(): {'applied', 'skipped', 'norm', 'norms': {segment: norm}, 'coef', 'nonfinite'} of the last step
+        (with transactional=True also 'forward_nonfinite', 'vetoed', 'rolled_back', 'first_bad_buffer'), from one device read made
+        here and nowhere else; EfghError when the guard is off"""
         return self.opt.guard_stats()
+
+    def _probe(self, losses, k, stride, offset=0):
+        """the transaction's probe over the k `total` losses of this optimizer step.  Ordering: BatchNorm statistics are written
+        on the current stream and on the backbone's branch streams; the forward joins its branches before it returns what depends
+        on them, and `step` (after backward) / GradAccumulator.drain (after every micro-batch's backward) make the current stream
+        wait for EVERY side stream - the probe is enqueued behind that join, the resolve launch behind the probe, and the next
+        snapshot behind both, before the next forward forks again.  world > 1: the counts are summed over the ranks (one 8-byte
+        collective), so that all ranks veto together; each restores its own buffers, `first_bad` stays rank-local."""
+        _C.require_f32(losses)
+        self.txn.probe(losses, k, stride, offset)
+        if self.world > 1:
+            dist.all_reduce(self.txn.forward_count(), op=dist.ReduceOp.SUM)
 
     def load_checkpoint(self, ckpt):
         """resume from a checkpoint in the reference's layout (common/helper.py:40-61, main.py:149-160,190-198): model state,
@@ -522,6 +688,8 @@ class Trainer:
         ops.w2v_clear()
         self.flat.uses = [0] * len(self.flat.params)
         self.model.train()
+        if self.txn is not None:
+            self.txn.snapshot()               # on the current stream, before the forward forks its branch streams from it
         self.flat.collect_ticks = True
         try:
             pred = self.model(pc, img, calib, A)
@@ -536,6 +704,8 @@ class Trainer:
         for s in ops.side_streams():
             torch.cuda.current_stream().wait_stream(s)
         self.comm.finish()
+        if self.txn is not None:
+            self._probe(losses['total'], 1, 1)
         self.opt.step(grad_scale=1.0 / self.world)
         self.it += 1
         return losses, pred
@@ -554,7 +724,8 @@ class Trainer:
 
         Once per call: `it`, the learning-rate schedule and Adam's step count advance.  Per micro-batch, as torch would: BatchNorm's
         running statistics and num_batches_tracked.  With skip_nonfinite a non-finite value in any micro-batch's gradient reaches
-        the sum and the whole accumulated step is skipped.
+        the sum and the whole accumulated step is skipped.  With transactional=True a skipped step - a non-finite gradient, loss
+        or BatchNorm statistic in ANY micro-batch - also undoes what ALL k micro-batches did to the running statistics and counters.
         -> (losses, preds): the criterion's `loss_name` entries as detached device scalars of the global batch (the mean over the
         micro-batches of their weighted terms), and the list of the k prediction dicts (detached)."""
         mbs = [tuple(mb) for mb in micro_batches]
@@ -573,7 +744,9 @@ class Trainer:
         acc.reset()
         self.model.train()
         names = list(getattr(self.criterion, 'loss_name', None) or [])
-        rows, preds = [], []
+        rows, preds, totals = [], [], []
+        if self.txn is not None:
+            self.txn.snapshot()                       # ONE snapshot for the k micro-batches: the state before the first forward
         paused, self.comm.paused = self.comm.paused, True
         try:
             for i, (pc, img, calib, A, gt) in enumerate(mbs):
@@ -596,12 +769,23 @@ class Trainer:
                 names = names or list(losses)
                 rows.append(torch.stack([losses[n].detach().reshape(()) for n in names]))
                 preds.append({n: (v.detach() if torch.is_tensor(v) else v) for n, v in pred.items()})
+                if self.txn is not None and 'total' not in names:
+                    totals.append(losses['total'].detach().reshape(()))
                 del losses, pred
         finally:
             self.comm.paused = paused
+        stacked = rows[0] if k == 1 else torch.stack(rows)
+        if self.txn is not None:
+            # ONE probe after the last drain (which joined the side streams): a running statistic that went inf / NaN in an earlier
+            # micro-batch stays so under (1 - momentum) * running + momentum * batch, so the end state shows it; the k totals are
+            # read where they already are (column `total` of the stacked loss rows)
+            if 'total' in names:
+                self._probe(stacked, k, len(names), names.index('total'))
+            else:
+                self._probe(torch.stack(totals), k, 1)
         allreduce_mean_(acc.acc, self.world)
         self.opt.step(grad_scale=1.0 / (k * self.world), grad=acc.acc)
         acc.reset()
         self.it += 1
-        mean = rows[0] if k == 1 else torch.stack(rows).sum(0) / k
+        mean = stacked if k == 1 else stacked.sum(0) / k
         return {n: mean[j] for j, n in enumerate(names)}, preds

@@ -4,6 +4,7 @@ loop of the reference's iterater.py:25-60 with nothing on the CPU between the de
 
     python examples/train_synthetic.py --iters 3 --raw 128 256 --points 2048
     python examples/train_synthetic.py --iters 3 --batch 4 --accumulate 2        # gradient accumulation over micro-batches
+    python examples/train_synthetic.py --iters 3 --transactional                 # a skipped step also restores BatchNorm's state
 """
 import argparse
 import os
@@ -48,16 +49,21 @@ def main(argv=None):
     ap.add_argument('--points', type=int, default=2048)
     ap.add_argument('--max-grad-norm', type=float, default=None, help='clip the global gradient norm (torch clip_grad_norm_) inside the fused step')
     ap.add_argument('--skip-nonfinite', action='store_true', help='leave weights and Adam moments untouched on a step whose gradient holds inf / NaN')
+    ap.add_argument('--transactional', action='store_true',
+                    help='implies --skip-nonfinite: a non-finite forward skips the step too, and a skipped step restores BatchNorm\'s '
+                         'running statistics and counters')
     ap.add_argument('--accumulate', type=int, default=None, metavar='K',
                     help='cut every batch into K micro-batches and accumulate their gradients: the update of --batch, the memory of --batch / K')
     a = ap.parse_args(argv)
+    a.skip_nonfinite = a.skip_nonfinite or a.transactional
     raw = tuple(a.raw)
     args = syn.default_args(raw, 'cuda')
     args.update({'lidar_line': None, 'num_points': a.points, 'test': False,
                  'dclb': {'l_rot_range': 1 / 12., 'l_trs_range': 1.0, 'c_rot_range': 1 / 12.}})
     torch.manual_seed(0)
     model = EFGHBackbone(args).cuda()
-    trainer = Trainer(model, EFGHCriterion(args), lr=1e-4, max_grad_norm=a.max_grad_norm, skip_nonfinite=a.skip_nonfinite)
+    trainer = Trainer(model, EFGHCriterion(args), lr=1e-4, max_grad_norm=a.max_grad_norm, skip_nonfinite=a.skip_nonfinite,
+                      transactional=a.transactional)
     prep = ProcessKITTIODOM(args)
     err = Err(args['dataset'])
     calib0, _ = syn.calib_and_A(raw)

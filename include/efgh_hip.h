@@ -58,7 +58,9 @@ const char *efgh_last_error(void);
  *      efgh_lattice_index_bytes, efgh_lattice_index_build, efgh_lattice_locate (point query of a built level);
  *      efgh_grad_guard_workspace, efgh_grad_guard_measure, efgh_adam_step_guarded and the struct efgh_guard_state (global-norm
  *      clipping and non-finite-step skipping inside the fused optimizer step);
- *      efgh_grad_drain, efgh_gimg_valid_count (gradient accumulation over micro-batches). */
+ *      efgh_grad_drain, efgh_gimg_valid_count (gradient accumulation over micro-batches);
+ *      efgh_txn_snapshot, efgh_txn_probe, efgh_txn_resolve and the struct efgh_txn_state (BatchNorm running statistics and counters
+ *      rolled back when the guarded step is skipped; a non-finite forward skips it). */
 #define EFGH_ABI_VERSION 4
 int efgh_version(void);
 
@@ -628,7 +630,7 @@ typedef struct efgh_guard_state {
     int64_t nonfinite[EFGH_GUARD_MAX_SEGMENTS]; /* per segment: elements that are inf or NaN */
     int64_t nonfinite_total;
     int64_t applied;                            /* optimizer steps applied so far == Adam's step count t */
-    int64_t skipped;                            /* steps skipped because of a non-finite gradient */
+    int64_t skipped;                            /* steps skipped by a non-finite gradient or a vetoing forward */
     float coef;                                 /* min(1, max_norm / (norm + 1e-6)) in float64, rounded once (torch's clip coefficient) */
     float scale;                                /* grad_scale * coef: what efgh_adam_step_guarded multiplies g by */
     float bc1;                                  /* 1 - beta1^applied */
@@ -677,6 +679,51 @@ int efgh_grad_drain(float *acc, float *g, int64_t n, int32_t first, void *stream
  * the workgroups finish in.  Used to weight the micro-batches' g_depth terms by their valid-pixel counts BEFORE their forwards run
  * (the counts depend on the inputs only), so that the accumulated loss is the one loss over the global batch. */
 int efgh_gimg_valid_count(const float *gdep4, const uint8_t *img_mask, int32_t B, int64_t HW, int64_t *count, void *stream);
+
+/* ---- transactional BatchNorm state: a skipped optimizer step is all or nothing ----
+ * The gradient guard above protects w, m, v and the step count.  A training forward has by then already written BatchNorm's
+ * running_mean / running_var (efgh_bn_finalize, through raw pointers) and ticked num_batches_tracked - for every micro-batch of an
+ * accumulated step - and one inf or NaN activation leaves (1 - momentum) * running + momentum * batch non-finite for good.  Worse,
+ * the guard may never see it: the deferred-activation input transforms and the affine max-pool turn a NaN pre-activation into a
+ * finite 0, so a diverged forward can reach the loss, and the gradient, finite.
+ *
+ * The caller keeps every running statistic of the model in ONE fp32 vector live_f[nf] (buffer s occupies [starts[s], starts[s + 1]),
+ * starts[0] = 0, starts[nseg] = nf, a DEVICE table) and every counter in one int64 vector live_c[nc], plus a second pair shadow_f /
+ * shadow_c of the same sizes.  Per optimizer step, on ONE stream:
+ *     efgh_txn_snapshot -> forward(s) -> backward(s) -> efgh_txn_probe -> efgh_grad_guard_measure (skip_nonfinite != 0)
+ *                       -> efgh_txn_resolve -> efgh_adam_step_guarded
+ * Three launches, no host read, no floating-point atomics (the probe adds and minimises integers: the results do not depend on the
+ * order workgroups arrive in).  live_f / shadow_f 16-byte aligned, the counters, starts and the state blocks 8-byte aligned; live and
+ * shadow must not overlap; 1 <= nf < 2^31, 0 <= nc < 2^31.  Where a buffer starts inside live_f is arbitrary (any multiple of 4 bytes). */
+typedef struct efgh_txn_state {                 /* DEVICE memory, zeroed once by the caller before the first efgh_txn_snapshot */
+    int64_t forward_nonfinite;                  /* this step: elements of live_f that became inf / NaN + non-finite loss scalars */
+    int64_t rolled_back;                        /* steps whose BatchNorm state was restored so far (every skipped step) */
+    int64_t vetoed_total;                       /* steps skipped so far ONLY because of the forward (the gradient was finite) */
+    int32_t first_bad;                          /* this step: smallest buffer index with a newly non-finite element, or -1 */
+    int32_t vetoed;                             /* this step: 1 when efgh_txn_resolve turned an applied step into a skipped one */
+} efgh_txn_state;
+/* shadow_f = live_f, shadow_c = live_c (bit copies) and forward_nonfinite = 0, first_bad = -1, vetoed = 0.  One launch; it must
+ * precede the first forward of the optimizer step on every stream that forward uses. */
+int efgh_txn_snapshot(const float *live_f, float *shadow_f, int64_t nf, const int64_t *live_c, int64_t *shadow_c, int64_t nc,
+                      efgh_txn_state *txn, void *stream);
+/* After the last forward of the step (all streams joined): txn->forward_nonfinite += the number of elements i with live_f[i] inf or
+ * NaN and shadow_f[i] finite - a buffer that was already non-finite before the step counts nothing and does not stall training -
+ * plus 1 for every j < k with losses[j * loss_stride] inf or NaN (the (micro-)batch `total` losses, DEVICE memory; k = 0: none).
+ * txn->first_bad = min(first_bad, smallest s with such an element in [starts[s], starts[s + 1])).  Non-finite running statistics
+ * are sticky, so ONE probe after k micro-batches sees what any of them did.  Nothing but *txn is written.  One launch. */
+int efgh_txn_probe(const float *live_f, const float *shadow_f, int64_t nf, const int64_t *starts, int32_t nseg, const float *losses,
+                   int32_t k, int64_t loss_stride, efgh_txn_state *txn, void *stream);
+/* After efgh_grad_guard_measure(skip_nonfinite != 0, beta1, beta2) on the same stream and before efgh_adam_step_guarded.  One launch.
+ *   veto     txn->forward_nonfinite != 0 and guard->skip == 0: *guard is rewritten as the decide launch would have left it had it
+ *            skipped - skip = 1, applied -= 1, skipped += 1, bc1 and bc2_sqrt those of the un-advanced `applied` (same expressions);
+ *            coef, scale, norm, the sums and the counts stay - and txn->vetoed = 1, txn->vetoed_total += 1.  With
+ *            forward_nonfinite == 0 *guard is not written.
+ *   restore  the final skip is 1 (guard->nonfinite_total != 0 or txn->forward_nonfinite != 0): live_f = shadow_f, live_c = shadow_c
+ *            (bit copies) and txn->rolled_back += 1.  Otherwise live is not written.
+ * efgh_adam_step_guarded then sees the veto through guard->skip.  (The workgroups that restore decide from nonfinite_total and
+ * forward_nonfinite, which this launch only reads; the rewritten fields are read and written by one thread.) */
+int efgh_txn_resolve(float *live_f, const float *shadow_f, int64_t nf, int64_t *live_c, const int64_t *shadow_c, int64_t nc,
+                     efgh_guard_state *guard, efgh_txn_state *txn, float beta1, float beta2, void *stream);
 
 /* "thin" layers (<= 4 channels on one side: RGB/range/depth input convs, the 1-/2-channel heads and
  * their dgrad/wgrad): HBM-bound VALU kernels with the descriptor, gather modes and epilogue of
