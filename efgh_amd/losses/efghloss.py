@@ -51,7 +51,8 @@ class PoseLossFn(torch.autograd.Function):
     def forward(ctx, e_abs, e_sgn, h_abs, h_sgn, f_score, g_trs, e_l, f_l, l_dep, l_msk, rand_l, rand_c, T4, cfg):
         dev = f_score.device
         t = [x.detach() for x in (e_abs, e_sgn, h_abs, h_sgn, f_score, g_trs, e_l, f_l, rand_l, rand_c, T4)]
-        t = [x if (x.dim() == 2 and x.stride(1) == 1) else x.contiguous() for x in t]
+        # the descriptor carries a row pitch for e_gn_sgn, h_hrzn_sgn and f_score only: everything else is read densely
+        t = [x if (i in (1, 3, 4) and x.dim() == 2 and x.stride(1) == 1) else x.contiguous() for i, x in enumerate(t)]
         ops._C.require_cuda(*t)
         ops._C.require_f32(*t)
         B, W = t[4].shape

@@ -1791,6 +1791,7 @@ def gimg_loss_fwd(pred_depth, pred_mask, gdep4, img_mask):
     """-> (out3 = [l_depth, l_mask, sum(valid)] device tensor, gt_depth (B,1,H,W), gt_mask (B,1,H,W))"""
     B, _, H, W = pred_depth.shape
     dev = pred_depth.device
+    gdep4, img_mask = gdep4.contiguous(), img_mask.contiguous()          # the kernel reads both densely
     gt_depth = torch.empty((B, 1, H, W), dtype=torch.float32, device=dev)
     gt_mask = torch.empty((B, 1, H, W), dtype=torch.float32, device=dev)
     G = _L().efgh_gimg_loss_groups(c_int64(B * H * W))
@@ -1866,6 +1867,7 @@ def txn_resolve(live_f, shadow_f, live_c, shadow_c, guard, txn, beta1, beta2):
 
 def gimg_loss_bwd(pred_depth, pred_mask, gt_depth, img_mask, out3, g_depth, g_mask):
     B, _, H, W = pred_depth.shape
+    gt_depth, img_mask = gt_depth.contiguous(), img_mask.contiguous()    # the kernel reads both densely
     d_depth = torch.empty_like(pred_depth)
     d_mask = torch.zeros_like(pred_mask)                   # channel 1 receives no gradient from this loss
     _C.check(_L().efgh_gimg_loss_bwd(ptr(pred_depth), ptr(pred_mask), c_int64(pred_mask.stride(0)), ptr(gt_depth), ptr(img_mask),
