@@ -131,6 +131,8 @@ def lib():
                                         c_void_p]
         _lib.efgh_txn_resolve.argtypes = [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_float,
                                           c_float, c_void_p]
+        _lib.efgh_ema_update.argtypes = [c_void_p, c_void_p, c_int64, c_float, c_int32, c_int64, c_void_p, c_void_p]
+        _lib.efgh_ema_swap.argtypes = [c_void_p, c_void_p, c_int64, c_void_p]
     return _lib
 
 

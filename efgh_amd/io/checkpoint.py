@@ -10,6 +10,8 @@ import shutil
 
 import torch
 
+from .._C import EfghError
+
 
 def strip_module_prefix(sd):
     return {(k[len('module.'):] if k.startswith('module.') else k): v for k, v in sd.items()}
@@ -94,12 +96,74 @@ def load_adam_state(opt, sd):
     opt.t = max(steps) if steps else 0          # (a property: with skip_nonfinite it also sets the device-side count)
 
 
+def _ema_named(ema, model):
+    """[(name, averaged view)] of the trainable parameters a train.WeightEma averages, under their names in `model`"""
+    avg = {id(p): v for p, v in ema.views()}
+    named = [(name, avg[id(p)]) for name, p in model.named_parameters() if id(p) in avg]
+    if len(named) != len(avg):
+        raise EfghError('the weight average holds %d parameters, %d of them are parameters of this model' % (len(avg), len(named)))
+    return named
+
+
+def ema_state(ema, model):
+    """the 'ema' entry of a checkpoint: decay, warm-up flag and the averaged trainable parameters under the reference's key names"""
+    return {'decay': ema.decay, 'warmup': ema.warmup,
+            'state_dict': {'module.' + name: v.detach().cpu().clone() for name, v in _ema_named(ema, model)}}
+
+
+def check_ema_state(ema, model, entry):
+    """EfghError unless `entry` (a checkpoint's 'ema') holds exactly the trainable parameters of `model`, with their shapes"""
+    sd = strip_module_prefix(entry['state_dict']) if isinstance(entry, dict) and 'state_dict' in entry else None
+    if sd is None:
+        raise EfghError("the checkpoint's 'ema' entry has no 'state_dict'")
+    named = _ema_named(ema, model)
+    want = [name for name, _ in named]
+    if sorted(sd) != sorted(want):
+        missing, extra = sorted(set(want) - set(sd)), sorted(set(sd) - set(want))
+        raise EfghError("the checkpoint's weight average does not match the trainable parameters: missing %s, unexpected %s"
+                        % (missing[:5], extra[:5]))
+    for name, v in named:
+        if tuple(sd[name].shape) != tuple(v.shape):
+            raise EfghError("the checkpoint's weight average has shape %s for %s, the model %s"
+                            % (tuple(sd[name].shape), name, tuple(v.shape)))
+    return sd, named
+
+
+def load_ema_state(ema, model, entry):
+    """inverse of ema_state: the averaged values go into the WeightEma's buffer (its decay and warm-up flag stay its own)"""
+    sd, named = check_ema_state(ema, model, entry)
+    for name, v in named:
+        v.copy_(sd[name])
+
+
+def ema_checkpoint(ckpt):
+    """a checkpoint saved with a weight average -> a checkpoint in the reference's layout (`iter`, `state_dict`, `min_loss`,
+    `optimizer`) whose `state_dict` carries the AVERAGED trainable parameters, every other entry (frozen parameters, buffers) as
+    saved: what the reference's test branch loads with strict=True to evaluate the averaged model"""
+    if isinstance(ckpt, (str, os.PathLike)):
+        ckpt = torch.load(ckpt, map_location='cpu')
+    if not isinstance(ckpt, dict) or 'ema' not in ckpt or 'state_dict' not in ckpt:
+        raise EfghError("ema_checkpoint: the checkpoint has no weight average (save it with save_checkpoint(..., ema=trainer.ema))")
+    avg = ckpt['ema']['state_dict']
+    sd = dict(ckpt['state_dict'])
+    for name, v in avg.items():
+        if name not in sd or tuple(sd[name].shape) != tuple(v.shape):
+            raise EfghError("ema_checkpoint: the weight average's %s is not an entry of the checkpoint's state_dict of that shape" % name)
+        sd[name] = v
+    out = {k: v for k, v in ckpt.items() if k != 'ema'}
+    out['state_dict'] = sd
+    return out
+
+
 def save_checkpoint(ckpt_dir, model, opt, it, min_loss, is_best=False, iter_interval=1000,
-                    filename='checkpoint.pth.tar'):
-    """common/helper.py:40-61 semantics: rolling file, periodic copies, best copy, pruning after 5 intervals"""
+                    filename='checkpoint.pth.tar', ema=None):
+    """common/helper.py:40-61 semantics: rolling file, periodic copies, best copy, pruning after 5 intervals.  `ema`: a
+    train.WeightEma (Trainer.ema) - one more key 'ema' (ema_state); None: exactly the reference's keys"""
     os.makedirs(ckpt_dir, exist_ok=True)
     state = {'iter': it, 'state_dict': {'module.' + k: v.detach().cpu() for k, v in model.state_dict().items()},
              'min_loss': min_loss, 'optimizer': adam_state_dict(opt)}
+    if ema is not None:
+        state['ema'] = ema_state(ema, model)
     path = os.path.join(ckpt_dir, filename)
     torch.save(state, path)
     if it % iter_interval == 0:

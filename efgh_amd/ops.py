@@ -1825,6 +1825,64 @@ def grad_drain(acc, g, first):
     _C.check(_L().efgh_grad_drain(ptr(acc), ptr(g), c_int64(g.numel()), c_int32(1 if first else 0), _st()))
 
 
+def _ema_pair(name, a, b):
+    """two flat fp32 buffers of one size on one device; -> True on the GPU, False for CPU tensors (plain torch ops)"""
+    if not (torch.is_tensor(a) and torch.is_tensor(b)) or a.device != b.device:
+        raise _C.EfghError('%s: expected two tensors on one device' % name)
+    _C.require_f32(a, b)
+    if a.numel() != b.numel() or a.numel() < 1 or not (a.is_contiguous() and b.is_contiguous()):
+        raise _C.EfghError('%s: the two buffers must be contiguous, non-empty and of equal size' % name)
+    if not a.is_cuda:
+        lo, hi = sorted((a.data_ptr(), b.data_ptr()))
+        if lo + 4 * a.numel() > hi:
+            raise _C.EfghError('%s: the two buffers overlap' % name)
+    return a.is_cuda
+
+
+def ema_decay_at(decay, warmup, t):
+    """the decay efgh_ema_update uses at step count t: min(decay, (1 + t) / (10 + t)) in float64 with `decay` as the fp32
+    argument the kernel sees, rounded once to fp32 (returned as a Python float holding that fp32 value)"""
+    ramp = (1.0 + t) / (10.0 + t) if warmup else 1.0
+    return c_float(min(c_float(decay).value, ramp)).value
+
+
+def ema_update(ema, w, decay, warmup, step, state=None):
+    """ema = fma(1 - d, w - ema, ema) with d = ema_decay_at(decay, warmup, t): one launch over two flat fp32 device buffers
+    (train.WeightEma).  `state`: the uint8 tensor holding an efgh_guard_state - t is its `applied` and a set `skip` leaves ema
+    untouched, decided on the device; None: t = `step` >= 1.  CPU tensors take lerp_ (the bits of that route are not promised)."""
+    cuda = _ema_pair('ema_update', ema, w)
+    if isinstance(decay, bool) or not isinstance(decay, (int, float)) or not 0.0 < decay < 1.0:
+        raise _C.EfghError('ema_update: decay must be a real number in (0, 1), got %r' % (decay,))
+    if state is not None:
+        if not torch.is_tensor(state) or state.dtype != torch.uint8 or state.device != ema.device \
+                or not state.is_contiguous() or state.numel() < ctypes.sizeof(_C.GuardState):
+            raise _C.EfghError('ema_update: state must be the contiguous uint8 tensor holding an efgh_guard_state on %s' % ema.device)
+    elif isinstance(step, bool) or not isinstance(step, int) or step < 1:
+        raise _C.EfghError('ema_update: step must be an integer >= 1 when there is no state block, got %r' % (step,))
+    if cuda:
+        _C.check(_L().efgh_ema_update(ema.data_ptr(), w.data_ptr(), ema.numel(), decay, 1 if warmup else 0,
+                                      0 if state is not None else step, state.data_ptr() if state is not None else 0, _st()))
+        return
+    t = step
+    if state is not None:
+        st = _C.GuardState.from_buffer_copy(state.numpy().tobytes()[:ctypes.sizeof(_C.GuardState)])
+        if st.skip:
+            return
+        t = int(st.applied)
+    d = ema_decay_at(decay, warmup, t)
+    ema.lerp_(w, c_float(1.0 - d).value)
+
+
+def ema_swap(a, b):
+    """exchanges the contents of two flat fp32 buffers by bits: one launch (CPU tensors: a three-way copy)"""
+    if _ema_pair('ema_swap', a, b):
+        _C.check(_L().efgh_ema_swap(a.data_ptr(), b.data_ptr(), a.numel(), _st()))
+        return
+    tmp = a.clone()
+    a.copy_(b)
+    b.copy_(tmp)
+
+
 def _txn_vectors(name, live_f, shadow_f, live_c, shadow_c):
     _C.require_cuda(live_f, shadow_f, live_c, shadow_c)
     _C.require_f32(live_f, shadow_f)

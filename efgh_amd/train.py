@@ -6,6 +6,7 @@ so the data-parallel exchange is a bucketed all-reduce of 191 MB whose buckets a
 parameter hooks while backward is still running, and the optimizer is one kernel launch instead of 353.
 `DataParallel` semantics (one loss over the global batch, batch-mean terms) == mean of the per-rank
 gradients for equal per-rank batches."""
+import contextlib
 import os
 
 import torch
@@ -410,6 +411,49 @@ def check_max_grad_norm(value):
     return v
 
 
+def check_ema_decay(value):
+    """`ema_decay` of Trainer / WeightEma: None (no average) or a real number in (0, 1) -> None | float"""
+    if value is None:
+        return None
+    if isinstance(value, bool) or not isinstance(value, (int, float)):
+        raise _C.EfghError('ema_decay must be a real number in (0, 1) (or None), got %r' % (value,))
+    v = float(value)
+    if not 0.0 < v < 1.0:                                   # (also catches NaN)
+        raise _C.EfghError('ema_decay must be a real number in (0, 1) (or None), got %r' % (value,))
+    return v
+
+
+class WeightEma:
+    """Exponential moving average of the trainable weights (torch.optim.swa_utils.AveragedModel with get_ema_multi_avg_fn, over
+    the parameters only) in ONE flat fp32 buffer `buf` next to flat.w: 4n bytes more memory (191 MB for the full net).  It starts
+    as a copy of flat.w; `update(opt)` is one launch (efgh_ema_update) behind the optimizer's on the same stream, without an aten
+    op or a host read:
+        t = Adam's step count, d = min(decay, (1 + t) / (10 + t)) (warmup; else d = decay), buf = fma(1 - d, w - buf, buf)
+    With a guarded optimizer t and the skip flag are read from its device state block: a skipped step is not averaged and does not
+    count towards the warm-up.  CPU tensors (the host suite) take lerp_."""
+
+    def __init__(self, flat, decay, warmup=True):
+        self.decay = check_ema_decay(decay)
+        if self.decay is None:
+            raise _C.EfghError('WeightEma needs ema_decay: a real number in (0, 1)')
+        self.flat, self.warmup = flat, bool(warmup)
+        self.buf = flat.w.clone()
+
+    def update(self, opt):
+        if opt.guarded:
+            ops.ema_update(self.buf, self.flat.w, self.decay, self.warmup, 0, opt.state)
+        else:
+            ops.ema_update(self.buf, self.flat.w, self.decay, self.warmup, opt._t)
+
+    def reset(self):
+        """the average becomes a copy of the current weights again (after a load that brought no average of its own)"""
+        self.buf.copy_(self.flat.w)
+
+    def views(self):
+        """the averaged values of the trainable parameters as views of `buf`, in flat order: [(parameter, view)]"""
+        return [(p, self.buf[off:off + k].view(p.shape)) for p, (off, k) in zip(self.flat.params, self.flat.offsets)]
+
+
 def name_segments(names, sizes, limit=_C.GUARD_MAX_SEGMENTS):
     """segments of a flat parameter buffer for the gradient guard's per-segment norms: the consecutive runs of equal top-level
     module name (`E.bcn1.weight` -> `E`) in flat order, as [(name, start, end)]; one segment `all` when there would be more than
@@ -578,10 +622,20 @@ class Trainer:
     losses - such a step is skipped even when its gradient came out finite - and a skipped step restores statistics and counters,
     for an accumulated step those of ALL its micro-batches.  Three more launches per optimizer step, no host read; with world > 1
     one 8-byte all-reduce of the count, so that every rank takes the same decision and restores its own buffers.  `guard_stats()`
-    then also reports `forward_nonfinite`, `vetoed`, `rolled_back` and `first_bad_buffer`.  Only BatchNorm buffers are rolled back."""
+    then also reports `forward_nonfinite`, `vetoed`, `rolled_back` and `first_bad_buffer`.  Only BatchNorm buffers are rolled back.
 
-    def __init__(self, model, criterion, lr=1e-4, weight_decay=0.0, max_grad_norm=None, skip_nonfinite=False, transactional=False):
+    `ema_decay` (None, the default: nothing is allocated or launched) keeps an exponential moving average of the trainable weights
+    (WeightEma: 4n bytes, one launch per optimizer step right behind Adam; `ema_warmup` ramps the decay as (1 + t) / (10 + t) over
+    Adam's step count).  A step the guard skips - a transactional veto included - leaves the average bit-unchanged, decided on the
+    device.  The ranks of a data-parallel run average bit-identical weights, so no collective is needed.  `ema_state_dict()` gives
+    the model's state_dict with the averaged parameters (BatchNorm buffers and frozen parameters keep their live values);
+    `with trainer.ema_weights():` puts the averaged weights under the model in place for validation; save_checkpoint(ema=trainer.ema)
+    / load_checkpoint carry the average."""
+
+    def __init__(self, model, criterion, lr=1e-4, weight_decay=0.0, max_grad_norm=None, skip_nonfinite=False, transactional=False,
+                 ema_decay=None, ema_warmup=True):
         max_grad_norm = check_max_grad_norm(max_grad_norm)                       # (before anything is re-homed or broadcast)
+        ema_decay = check_ema_decay(ema_decay)
         if transactional and not skip_nonfinite:
             raise _C.EfghError('transactional=True needs skip_nonfinite=True: only a skipped step is rolled back')
         self.model, self.criterion = model, criterion
@@ -605,6 +659,53 @@ class Trainer:
             ops.reserve_comm_queue()
         self.base_lr, self.it = lr, 0
         self.accum = None                                   # GradAccumulator of step_accumulated, built on first use
+        # (after the broadcast: every rank starts from, and then averages, bit-identical weights)
+        self.ema = WeightEma(self.flat, ema_decay, ema_warmup) if ema_decay is not None else None
+        self._ema_scope = False
+
+    def _need_ema(self, what):
+        if self.ema is None:
+            raise _C.EfghError('%s: the weight average is off (construct the Trainer with ema_decay=)' % what)
+
+    def _not_in_ema_scope(self, what):
+        if self._ema_scope:
+            raise _C.EfghError('%s inside `with trainer.ema_weights():` - the averaged weights are under the model' % what)
+
+    def ema_state_dict(self):
+        """model.state_dict() - same names, shapes and order - with the entries of the trainable parameters replaced by clones of
+        their averaged values.  Frozen parameters and all buffers keep their live values (BatchNorm's running statistics are
+        averages already: AveragedModel's use_buffers=False)."""
+        self._need_ema('ema_state_dict()')
+        self._not_in_ema_scope('ema_state_dict()')
+        sd = self.model.state_dict()
+        avg = {id(p): v for p, v in self.ema.views()}
+        for name, p in self.model.named_parameters(remove_duplicate=False):
+            if id(p) in avg and name in sd:
+                sd[name] = avg[id(p)].clone()
+        return sd
+
+    def _ema_exchange(self):
+        if self.flat.w.is_cuda:                             # a forward's branch streams read the weights too
+            for s in ops.side_streams():
+                torch.cuda.current_stream().wait_stream(s)
+        ops.ema_swap(self.flat.w, self.ema.buf)
+        ops.bump_epoch(self.flat.epoch)                     # packed-weight / folded-BN caches are stale now
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """scope in which the model computes with the averaged weights: flat.w and the average's buffer are exchanged in place (one
+        launch, then the content epoch moves so that packed and folded weights are rebuilt) and exchanged back on exit, also after
+        an exception.  train() / eval() mode is the caller's business.  `step`, `step_accumulated`, `load_checkpoint` and a nested
+        scope raise EfghError inside."""
+        self._need_ema('ema_weights()')
+        self._not_in_ema_scope('ema_weights()')
+        self._ema_exchange()
+        self._ema_scope = True
+        try:
+            yield self
+        finally:
+            self._ema_scope = False
+            self._ema_exchange()
 
     def guard_stats(self):
         """FusedAdam.guard_stats(): {'applied', 'skipped', 'norm', 'norms': {segment: norm}, 'coef', 'nonfinite'} of the last step
@@ -629,13 +730,22 @@ class Trainer:
         Adam moments and the iteration counter, so that the step-wise decay 0.7^(iter // 50000) continues where it stopped.
         (The reference re-evaluates the schedule once per iterater() call, iterater.py:21, i.e. per epoch; here it is evaluated
         every step from the same formula - the learning rate changes at iteration 50000*k exactly instead of at the next epoch
-        boundary.)"""
+        boundary.)  With a weight average: the file's average is restored when it has one (EfghError on a name or shape mismatch; the
+        decay and warm-up stay the Trainer's own), otherwise the average restarts as a copy of the loaded weights."""
         from .io import checkpoint as ck
+        self._not_in_ema_scope('load_checkpoint')
         if isinstance(ckpt, (str, bytes)) or hasattr(ckpt, '__fspath__'):
             ckpt = torch.load(ckpt, map_location='cpu')
+        has_ema = self.ema is not None and isinstance(ckpt, dict) and 'ema' in ckpt
+        if has_ema:
+            ck.check_ema_state(self.ema, self.model, ckpt['ema'])       # (before anything is written)
         ck.load_model_state(self.model, ckpt)
         if 'optimizer' in ckpt:
             ck.load_adam_state(self.opt, ckpt['optimizer'])
+        if has_ema:
+            ck.load_ema_state(self.ema, self.model, ckpt['ema'])
+        elif self.ema is not None:
+            self.ema.reset()                  # (it would still describe the weights from before the load)
         self.it = int(ckpt.get('iter', -1)) + 1
         ops.bump_epoch(self.flat.epoch)
         ops.bump_epoch()
@@ -683,6 +793,7 @@ class Trainer:
         gradients are accumulated (step_accumulated): the activation memory of B / k samples, the update of B."""
         if micro_batches is not None:
             return self.step_accumulated(split_micro_batches(pc, img, calib, A, gt, micro_batches))
+        self._not_in_ema_scope('step')
         self._check_frozen()
         self.opt.lr = adjust_learning_rate(self.base_lr, self.it)
         ops.w2v_clear()
@@ -707,6 +818,8 @@ class Trainer:
         if self.txn is not None:
             self._probe(losses['total'], 1, 1)
         self.opt.step(grad_scale=1.0 / self.world)
+        if self.ema is not None:
+            self.ema.update(self.opt)         # right behind Adam on the same stream; reads the guard's skip decision there
         self.it += 1
         return losses, pred
 
@@ -728,6 +841,7 @@ class Trainer:
         or BatchNorm statistic in ANY micro-batch - also undoes what ALL k micro-batches did to the running statistics and counters.
         -> (losses, preds): the criterion's `loss_name` entries as detached device scalars of the global batch (the mean over the
         micro-batches of their weighted terms), and the list of the k prediction dicts (detached)."""
+        self._not_in_ema_scope('step_accumulated')
         mbs = [tuple(mb) for mb in micro_batches]
         if not mbs or any(len(mb) != 5 for mb in mbs):
             raise _C.EfghError('step_accumulated takes a sequence of k >= 1 tuples (pc, img, calib, A, gt)')
@@ -785,6 +899,8 @@ class Trainer:
                 self._probe(torch.stack(totals), k, 1)
         allreduce_mean_(acc.acc, self.world)
         self.opt.step(grad_scale=1.0 / (k * self.world), grad=acc.acc)
+        if self.ema is not None:
+            self.ema.update(self.opt)         # once per optimizer step, not per micro-batch
         acc.reset()
         self.it += 1
         mean = stacked if k == 1 else stacked.sum(0) / k

@@ -5,6 +5,7 @@ loop of the reference's iterater.py:25-60 with nothing on the CPU between the de
     python examples/train_synthetic.py --iters 3 --raw 128 256 --points 2048
     python examples/train_synthetic.py --iters 3 --batch 4 --accumulate 2        # gradient accumulation over micro-batches
     python examples/train_synthetic.py --iters 3 --transactional                 # a skipped step also restores BatchNorm's state
+    python examples/train_synthetic.py --iters 5 --ema 0.999                     # validate the live and the averaged weights
 """
 import argparse
 import os
@@ -54,6 +55,9 @@ def main(argv=None):
                          'running statistics and counters')
     ap.add_argument('--accumulate', type=int, default=None, metavar='K',
                     help='cut every batch into K micro-batches and accumulate their gradients: the update of --batch, the memory of --batch / K')
+    ap.add_argument('--ema', type=float, default=None, metavar='DECAY',
+                    help='keep an exponential moving average of the weights inside the fused step and run the error meter on the last '
+                         'batch once with the live and once with the averaged weights')
     a = ap.parse_args(argv)
     a.skip_nonfinite = a.skip_nonfinite or a.transactional
     raw = tuple(a.raw)
@@ -63,7 +67,7 @@ def main(argv=None):
     torch.manual_seed(0)
     model = EFGHBackbone(args).cuda()
     trainer = Trainer(model, EFGHCriterion(args), lr=1e-4, max_grad_norm=a.max_grad_norm, skip_nonfinite=a.skip_nonfinite,
-                      transactional=a.transactional)
+                      transactional=a.transactional, ema_decay=a.ema)
     prep = ProcessKITTIODOM(args)
     err = Err(args['dataset'])
     calib0, _ = syn.calib_and_A(raw)
@@ -86,6 +90,19 @@ def main(argv=None):
         print('iter %d  total %.4f  %s' % (it, hist[-1], '  '.join('%s %.3f' % kv for kv in err.dict.items())))
     if a.max_grad_norm is not None or a.skip_nonfinite:
         print('gradient guard:', trainer.guard_stats())        # the one host read of the guard's state
+    if a.ema is not None:
+        def validate(tag):
+            meter = Err(args['dataset'])
+            with torch.no_grad():
+                meter.update({'sensor2_T_sensor1': gt['sensor2_T_sensor1'].float().cuda()}, model(pc, img, calib, A))
+            print('%-18s %s' % (tag, '  '.join('%s %.3f' % kv for kv in meter.dict.items())))
+            return dict(meter.dict)
+        model.eval()                                         # (the scope leaves the mode alone)
+        live = validate('live weights:')
+        with trainer.ema_weights():                          # the averaged weights under the same model, in place
+            averaged = validate('averaged weights:')
+        model.train()
+        return hist, live, averaged
     return hist
 
 

@@ -60,7 +60,8 @@ const char *efgh_last_error(void);
  *      clipping and non-finite-step skipping inside the fused optimizer step);
  *      efgh_grad_drain, efgh_gimg_valid_count (gradient accumulation over micro-batches);
  *      efgh_txn_snapshot, efgh_txn_probe, efgh_txn_resolve and the struct efgh_txn_state (BatchNorm running statistics and counters
- *      rolled back when the guarded step is skipped; a non-finite forward skips it). */
+ *      rolled back when the guarded step is skipped; a non-finite forward skips it);
+ *      efgh_ema_update, efgh_ema_swap (exponential moving average of the flat weights). */
 #define EFGH_ABI_VERSION 4
 int efgh_version(void);
 
@@ -724,6 +725,23 @@ int efgh_txn_probe(const float *live_f, const float *shadow_f, int64_t nf, const
  * forward_nonfinite, which this launch only reads; the rewritten fields are read and written by one thread.) */
 int efgh_txn_resolve(float *live_f, const float *shadow_f, int64_t nf, int64_t *live_c, const int64_t *shadow_c, int64_t nc,
                      efgh_guard_state *guard, efgh_txn_state *txn, float beta1, float beta2, void *stream);
+
+/* ---- exponential moving average of the weights: a second flat buffer `ema` next to the flat weights w, updated by ONE launch
+ * behind the optimizer entry points above on the same stream (torch.optim.swa_utils.AveragedModel with get_ema_multi_avg_fn: 353
+ * lerps there).  One pass of 12 n bytes, no atomics, no workspace, nothing outside [0, n) is touched.
+ *   t    state->applied when state is given (DEVICE memory, as efgh_grad_guard_measure / efgh_txn_resolve left it), else `step`;
+ *        state given and state->skip != 0: nothing is written (the step that was not applied is not averaged)
+ *   d    (float) fmin((double) decay, warmup ? (1.0 + t) / (10.0 + t) : 1.0)        float64 on the device, rounded once
+ *   omd  1.f - d
+ *   ema[i] = fmaf(omd, w[i] - ema[i], ema[i])
+ * Where w[i] == ema[i] the value does not move (a -0 may become +0: IEEE gives +0 for (-0) - (-0)).  ema and w 16-byte aligned and
+ * not overlapping, state 8-byte aligned; a null ema or w, n < 1, decay outside (0, 1) or NaN, state == NULL with step < 1:
+ * EFGH_E_INVALID, nothing is launched. */
+int efgh_ema_update(float *ema, const float *w, int64_t n, float decay, int32_t warmup, int64_t step,
+                    const efgh_guard_state *state /* may be NULL */, void *stream);
+/* exchanges the contents of a[n] and b[n] in one pass, by bits (NaN payloads and -0 survive; twice is the identity).  a and b 16-byte
+ * aligned and not overlapping; otherwise, for a null pointer or n < 1: EFGH_E_INVALID, nothing is launched. */
+int efgh_ema_swap(float *a, float *b, int64_t n, void *stream);
 
 /* "thin" layers (<= 4 channels on one side: RGB/range/depth input convs, the 1-/2-channel heads and
  * their dgrad/wgrad): HBM-bound VALU kernels with the descriptor, gather modes and epilogue of
