@@ -1483,6 +1483,20 @@ def side_streams():
     """every side stream this package has created (branch streams of the backbone + the weight-gradient stream)"""
     from .nets import efghbackbone as bb
     return list(bb._SIDE.values())
+
+
+def join_side_streams(t):
+    """the current stream waits for every side stream: whatever the branches and the weight-gradient stream have enqueued (writes
+    into flat buffers that no autograd node orders, BatchNorm statistics, reads of the weights) is ordered in front of what the
+    caller enqueues next.  `t`: a tensor of the buffer concerned - no torch.cuda call is made for a CPU tensor or without side streams"""
+    if t.is_cuda:
+        streams = side_streams()
+        if streams:
+            cur = torch.cuda.current_stream()
+            for s in streams:
+                cur.wait_stream(s)
+
+
 DETERMINISTIC = False     # (kept for callers that set it; a no-op since round 4: see gather_wgrad)
 
 

@@ -84,10 +84,19 @@ class FlatParams:
         """the flat gradient view of parameter i if a backward may overwrite it now (zeroed, nothing delivered yet), else None"""
         if not self.direct or self.arrived[i] or self.uses[i] > 1:
             return None
-        off, k = self.offsets[i]
-        if p.grad is None or p.grad.data_ptr() != self.g.data_ptr() + 4 * off:
-            return None
-        return p.grad
+        return p.grad if self.grad_in_place(i) else None
+
+    def grad_in_place(self, i):
+        """parameter i's .grad is still its slice of the flat gradient buffer (autograd replaces .grad when it accumulates)"""
+        grad = self.params[i].grad
+        return grad is not None and grad.data_ptr() == self.g.data_ptr() + 4 * self.offsets[i][0]
+
+    def rearm(self):
+        """before a backward into a zeroed flat gradient: nothing has arrived, every .grad is its flat slice again"""
+        self.arrived = [False] * len(self.params)
+        for i, (p, (off, k)) in enumerate(zip(self.params, self.offsets)):
+            if not self.grad_in_place(i):
+                p.grad = self.g[off:off + k].view(p.shape)
 
     def tick(self, j):
         self.ticks[j] += 1
@@ -115,10 +124,7 @@ class FlatParams:
 
     def zero_grad(self):
         self.g.zero_()
-        self.arrived = [False] * len(self.params)
-        for p, (off, k) in zip(self.params, self.offsets):      # autograd may have replaced .grad
-            if p.grad is None or p.grad.data_ptr() != self.g.data_ptr() + 4 * off:
-                p.grad = self.g[off:off + k].view(p.shape)
+        self.rearm()
 
 
 class GradAccumulator:
@@ -136,10 +142,8 @@ class GradAccumulator:
         f = self.flat
         if self.acc is None or self.acc.shape != f.g.shape or self.acc.device != f.g.device:
             self.acc = torch.empty_like(f.g)
+        ops.join_side_streams(f.g)                     # weight gradients are written on side streams (see Trainer.step)
         if f.g.is_cuda:
-            cur = torch.cuda.current_stream()
-            for s in ops.side_streams():               # weight gradients are written on side streams (see Trainer.step)
-                cur.wait_stream(s)
             ops.grad_drain(self.acc, f.g, self.count == 0)
         else:
             if self.count == 0:
@@ -147,12 +151,7 @@ class GradAccumulator:
             else:
                 self.acc.add_(f.g)
             f.g.zero_()
-        # what zero_grad does, without the memset
-        f.arrived = [False] * len(f.params)
-        base = f.g.data_ptr()
-        for p, (off, k) in zip(f.params, f.offsets):   # autograd may have replaced .grad
-            if p.grad is None or p.grad.data_ptr() != base + 4 * off:
-                p.grad = f.g[off:off + k].view(p.shape)
+        f.rearm()
         self.count += 1
         return self.count
 
@@ -399,28 +398,23 @@ class OverlappedAllReduce:
             w.wait()
 
 
-def check_max_grad_norm(value):
-    """`max_grad_norm` of FusedAdam / Trainer: None (no clipping) or a real number > 0 (`inf`: measure only) -> None | float"""
+def _check_real(value, ok, message):
+    """None, or a real number (no bool) for which `ok` holds (a NaN fails every comparison) -> None | float"""
     if value is None:
         return None
-    if isinstance(value, bool) or not isinstance(value, (int, float)):
-        raise _C.EfghError('max_grad_norm must be a real number > 0 (or None), got %r' % (value,))
-    v = float(value)
-    if not v > 0.0:                                         # (also catches NaN)
-        raise _C.EfghError('max_grad_norm must be a real number > 0 (or None), got %r' % (value,))
-    return v
+    if isinstance(value, bool) or not isinstance(value, (int, float)) or not ok(float(value)):
+        raise _C.EfghError(message % (value,))
+    return float(value)
+
+
+def check_max_grad_norm(value):
+    """`max_grad_norm` of FusedAdam / Trainer: None (no clipping) or a real number > 0 (`inf`: measure only) -> None | float"""
+    return _check_real(value, lambda v: v > 0.0, 'max_grad_norm must be a real number > 0 (or None), got %r')
 
 
 def check_ema_decay(value):
     """`ema_decay` of Trainer / WeightEma: None (no average) or a real number in (0, 1) -> None | float"""
-    if value is None:
-        return None
-    if isinstance(value, bool) or not isinstance(value, (int, float)):
-        raise _C.EfghError('ema_decay must be a real number in (0, 1) (or None), got %r' % (value,))
-    v = float(value)
-    if not 0.0 < v < 1.0:                                   # (also catches NaN)
-        raise _C.EfghError('ema_decay must be a real number in (0, 1) (or None), got %r' % (value,))
-    return v
+    return _check_real(value, lambda v: 0.0 < v < 1.0, 'ema_decay must be a real number in (0, 1) (or None), got %r')
 
 
 class WeightEma:
@@ -685,9 +679,7 @@ class Trainer:
         return sd
 
     def _ema_exchange(self):
-        if self.flat.w.is_cuda:                             # a forward's branch streams read the weights too
-            for s in ops.side_streams():
-                torch.cuda.current_stream().wait_stream(s)
+        ops.join_side_streams(self.flat.w)                  # a forward's branch streams read the weights too
         ops.ema_swap(self.flat.w, self.ema.buf)
         ops.bump_epoch(self.flat.epoch)                     # packed-weight / folded-BN caches are stale now
 
@@ -714,12 +706,10 @@ class Trainer:
         return self.opt.guard_stats()
 
     def _probe(self, losses, k, stride, offset=0):
-        """the transaction's probe over the k `total` losses of this optimizer step.  Ordering: BatchNorm statistics are written
-        on the current stream and on the backbone's branch streams; the forward joins its branches before it returns what depends
-        on them, and `step` (after backward) / GradAccumulator.drain (after every micro-batch's backward) make the current stream
-        wait for EVERY side stream - the probe is enqueued behind that join, the resolve launch behind the probe, and the next
-        snapshot behind both, before the next forward forks again.  world > 1: the counts are summed over the ranks (one 8-byte
-        collective), so that all ranks veto together; each restores its own buffers, `first_bad` stays rank-local."""
+        """the transaction's probe over the k `total` losses of this optimizer step, called by _apply (the step core's comment
+        argues why it sits behind the join of the side streams and in front of the resolve launch).  world > 1: the counts are summed
+        over the ranks (one 8-byte collective), so that all ranks veto together; each restores its own buffers, `first_bad` stays
+        rank-local."""
         _C.require_f32(losses)
         self.txn.probe(losses, k, stride, offset)
         if self.world > 1:
@@ -788,47 +778,77 @@ class Trainer:
             w = torch.where(mean > 0, n / mean.clamp_min(1e-300), torch.ones_like(n))
         return w.float()
 
-    def step(self, pc, img, calib, A, gt, micro_batches=None):
-        """one optimizer step on one batch.  `micro_batches=k`: the batch is cut into k equal chunks along dimension 0 whose
-        gradients are accumulated (step_accumulated): the activation memory of B / k samples, the update of B."""
-        if micro_batches is not None:
-            return self.step_accumulated(split_micro_batches(pc, img, calib, A, gt, micro_batches))
-        self._not_in_ema_scope('step')
+    # ---- the step core: `step` and `step_accumulated` are _begin, k x (_forward_loss, backward, join), _apply, and differ only in
+    # where the gradient lives (flat.g / the accumulator) and when it goes on the wire (from the hooks during backward / once after
+    # the last drain).  Ordering, all on the current stream: _begin enqueues the snapshot before any forward forks its branch streams
+    # (BatchNorm statistics are written there too; the forward joins its branches before it returns what depends on them); after
+    # every backward the current stream waits for EVERY side stream (ops.join_side_streams: in `step`, and at the head of drain());
+    # _apply enqueues the probe behind that join, the resolve launch (inside opt.step, between decide and Adam) behind the probe,
+    # the average behind Adam - and the next _begin's snapshot behind them all.
+    def _begin(self, what, depth_weights_of=None):
+        """checks, learning rate, train mode, the g_depth weights of the micro-batches `depth_weights_of` (if any; returned), and
+        then the transaction's ONE snapshot of this optimizer step"""
+        self._not_in_ema_scope(what)
         self._check_frozen()
         self.opt.lr = adjust_learning_rate(self.base_lr, self.it)
-        ops.w2v_clear()
-        self.flat.uses = [0] * len(self.flat.params)
         self.model.train()
+        weights = self.depth_weights(depth_weights_of) if depth_weights_of is not None else None
         if self.txn is not None:
             self.txn.snapshot()               # on the current stream, before the forward forks its branch streams from it
+        return weights
+
+    def _forward_loss(self, pc, img, calib, A, gt, depth_weight=None):
+        """forward and loss of one (micro-)batch -> (losses, gt, pred) as the criterion and the model return them"""
+        ops.w2v_clear()
+        self.flat.uses = [0] * len(self.flat.params)
         self.flat.collect_ticks = True
         try:
             pred = self.model(pc, img, calib, A)
         finally:
             self.flat.flush_ticks()
-        losses, gt = self.criterion.compute_loss(pc, img, calib, A, gt, pred)
+        ops.TLS.depth_weight = depth_weight
+        try:
+            losses, gt = self.criterion.compute_loss(pc, img, calib, A, gt, pred)
+        finally:
+            ops.TLS.depth_weight = None
+        return losses, gt, pred
+
+    def _apply(self, k, totals, grad=None):
+        """probe, Adam, average and `it` for the gradient of k (micro-)batches.  `totals`: (tensor, stride, offset) of the k `total`
+        losses, read only with a transaction.  `grad`: the accumulator, all-reduced here, or None: flat.g, which `comm` reduced"""
+        if self.txn is not None:
+            self._probe(totals[0], k, totals[1], totals[2])
+        if grad is not None:
+            allreduce_mean_(grad, self.world)
+        self.opt.step(grad_scale=1.0 / (k * self.world), grad=grad)
+        if self.ema is not None:
+            self.ema.update(self.opt)         # right behind Adam on the same stream; reads the guard's skip decision there
+        self.it += 1
+
+    def step(self, pc, img, calib, A, gt, micro_batches=None):
+        """one optimizer step on one batch, through the step core (the comment above `_begin` argues its order).  `micro_batches=k`:
+        the batch is cut into k equal chunks along dimension 0 whose gradients are accumulated (step_accumulated): the activation
+        memory of B / k samples, the update of B."""
+        if micro_batches is not None:
+            return self.step_accumulated(split_micro_batches(pc, img, calib, A, gt, micro_batches))
+        self._begin('step')
+        losses, gt, pred = self._forward_loss(pc, img, calib, A, gt)
         self.flat.zero_grad()
         self.comm.start_step()
         losses['total'].backward()            # bucket all-reduces start from the parameter hooks during this call
         # the point branch runs on a side stream (nets/efghbackbone.py) and so does its backward; autograd joins the streams of the
         # AccumulateGrad nodes it ran, but gradients written directly into the flat buffer have no such node: join explicitly
-        for s in ops.side_streams():
-            torch.cuda.current_stream().wait_stream(s)
+        ops.join_side_streams(self.flat.g)
         self.comm.finish()
-        if self.txn is not None:
-            self._probe(losses['total'], 1, 1)
-        self.opt.step(grad_scale=1.0 / self.world)
-        if self.ema is not None:
-            self.ema.update(self.opt)         # right behind Adam on the same stream; reads the guard's skip decision there
-        self.it += 1
+        self._apply(1, (losses['total'], 1, 0))
         return losses, pred
 
     def step_accumulated(self, micro_batches, exact_depth_mean=True):
         """ONE optimizer step on the gradient accumulated over k >= 1 micro-batches, a sequence of (pc, img, calib, A, gt) tuples
-        of equal batch size: per micro-batch forward, loss and backward into the zeroed flat gradient exactly as `step` runs them,
-        then GradAccumulator.drain(); each micro-batch's graph is gone before the next forward, so the activation memory is that
-        of ONE micro-batch.  After the last drain the sum is all-reduced once (world > 1; not overlapped with backward - the
-        bucket listeners are paused meanwhile) and the optimizer kernels read it with grad_scale = 1 / (k * world).
+        of equal batch size, through the step core of `step` (ordering: the comment above `_begin`): per micro-batch forward, loss
+        and backward into the zeroed flat gradient, then GradAccumulator.drain(); each micro-batch's graph is gone before the next
+        forward, so the activation memory is that of ONE micro-batch.  After the last drain the sum is all-reduced once (world > 1;
+        not overlapped with backward - the bucket listeners are paused meanwhile) and read with grad_scale = 1 / (k * world).
 
         The meaning is that of k data-parallel ranks (`torch.nn.DataParallel` replicas): one loss over the global batch, BatchNorm
         statistics per micro-batch.  Every term of efghloss is a batch mean except g_depth, a mean over the valid pixels of the
@@ -841,41 +861,22 @@ class Trainer:
         or BatchNorm statistic in ANY micro-batch - also undoes what ALL k micro-batches did to the running statistics and counters.
         -> (losses, preds): the criterion's `loss_name` entries as detached device scalars of the global batch (the mean over the
         micro-batches of their weighted terms), and the list of the k prediction dicts (detached)."""
-        self._not_in_ema_scope('step_accumulated')
         mbs = [tuple(mb) for mb in micro_batches]
         if not mbs or any(len(mb) != 5 for mb in mbs):
             raise _C.EfghError('step_accumulated takes a sequence of k >= 1 tuples (pc, img, calib, A, gt)')
         sizes = [int(mb[0].shape[0]) for mb in mbs]
         if len(set(sizes)) != 1:
             raise _C.EfghError('step_accumulated: the micro-batches must have equal batch sizes, got %s' % sizes)
-        self._check_frozen()
         k = len(mbs)
-        self.opt.lr = adjust_learning_rate(self.base_lr, self.it)
-        weights = self.depth_weights(mbs) if exact_depth_mean else None
-        if self.accum is None:
-            self.accum = GradAccumulator(self.flat)
-        acc = self.accum
+        weights = self._begin('step_accumulated', mbs if exact_depth_mean else None)   # ONE snapshot for the k micro-batches
+        acc = self.accum = self.accum or GradAccumulator(self.flat)
         acc.reset()
-        self.model.train()
         names = list(getattr(self.criterion, 'loss_name', None) or [])
         rows, preds, totals = [], [], []
-        if self.txn is not None:
-            self.txn.snapshot()                       # ONE snapshot for the k micro-batches: the state before the first forward
         paused, self.comm.paused = self.comm.paused, True
         try:
-            for i, (pc, img, calib, A, gt) in enumerate(mbs):
-                ops.w2v_clear()
-                self.flat.uses = [0] * len(self.flat.params)
-                self.flat.collect_ticks = True
-                try:
-                    pred = self.model(pc, img, calib, A)
-                finally:
-                    self.flat.flush_ticks()
-                ops.TLS.depth_weight = weights[i] if weights is not None else 1.0
-                try:
-                    losses = self.criterion.compute_loss(pc, img, calib, A, gt, pred)[0]
-                finally:
-                    ops.TLS.depth_weight = None
+            for i, mb in enumerate(mbs):
+                losses, pred = self._forward_loss(*mb, depth_weight=weights[i] if weights is not None else 1.0)[::2]
                 if i == 0:
                     self.flat.zero_grad()             # (later micro-batches find the buffer zeroed and re-armed by drain)
                 losses['total'].backward()
@@ -889,19 +890,12 @@ class Trainer:
         finally:
             self.comm.paused = paused
         stacked = rows[0] if k == 1 else torch.stack(rows)
+        # ONE probe after the last drain: a running statistic that went inf / NaN in an earlier micro-batch stays so under
+        # (1 - momentum) * running + momentum * batch, so the end state shows it; the k totals are read where they already are
+        where = None
         if self.txn is not None:
-            # ONE probe after the last drain (which joined the side streams): a running statistic that went inf / NaN in an earlier
-            # micro-batch stays so under (1 - momentum) * running + momentum * batch, so the end state shows it; the k totals are
-            # read where they already are (column `total` of the stacked loss rows)
-            if 'total' in names:
-                self._probe(stacked, k, len(names), names.index('total'))
-            else:
-                self._probe(torch.stack(totals), k, 1)
-        allreduce_mean_(acc.acc, self.world)
-        self.opt.step(grad_scale=1.0 / (k * self.world), grad=acc.acc)
-        if self.ema is not None:
-            self.ema.update(self.opt)         # once per optimizer step, not per micro-batch
+            where = (stacked, len(names), names.index('total')) if 'total' in names else (torch.stack(totals), 1, 0)
+        self._apply(k, where, grad=acc.acc)
         acc.reset()
-        self.it += 1
         mean = stacked if k == 1 else stacked.sum(0) / k
         return {n: mean[j] for j, n in enumerate(names)}, preds

@@ -12,17 +12,13 @@ from efgh_amd import _C, ops, synthetic as syn
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import ema_contract as contract  # noqa: E402
+from train_harness import (NAN, RAW, SpoilOnCall as _SpoilOnCall, bits as _bits, census, eval_forward, mb as _mb, step as _step,  # noqa: E402,F401
+                           trainer, waits_for_nothing, world)
 
 pytestmark = pytest.mark.gpu
-RAW, NPTS = (128, 256), 2048
-INF, NAN = float('inf'), float('nan')
 SIZES = [1, 2, 3, 4, 5, 255, 256, 257, 1023, 1024, 1025, 1000003]
 SETTINGS = [(0.999, 1), (0.999, 5), (0.999, 10 ** 5), (0.5, 10 ** 3), (0.9999, 10 ** 6)]
 GUARD = 8
-
-
-def _bits(t):
-    return t.detach().clone().view(torch.int32)
 
 
 def _boxed(x):
@@ -200,62 +196,9 @@ def test_swap_exchanges_bits(n):
     assert _guard_ok(bufa, n) and _guard_ok(bufb, n)
 
 
-# ---- Trainer, small configuration of tests/test_gpu_train.py ----
-class _InfOnCall:
-    """criterion whose `total` is multiplied by inf on the given calls (1-based): the forward stays finite, the gradient does not
-    (tests/test_gpu_grad_guard.py)"""
-
-    def __init__(self, inner, bad_calls):
-        self.inner, self.bad, self.calls = inner, set(bad_calls), 0
-        self.loss_name = getattr(inner, 'loss_name', None)
-
-    def compute_loss(self, *a):
-        losses, gt = self.inner.compute_loss(*a)
-        self.calls += 1
-        if self.calls in self.bad:
-            losses = dict(losses)
-            losses['total'] = losses['total'] * INF
-        return losses, gt
-
-
-class _SpoilOnCall:
-    """criterion that writes +inf into one running statistic on the given call (1-based), after the forward: loss and gradient stay
-    finite and only the transaction's probe sees it (tests/test_gpu_txn.py)"""
-
-    def __init__(self, inner, model, key, call):
-        self.inner, self.model, self.key, self.call, self.calls = inner, model, key, call, 0
-
-    def compute_loss(self, *a):
-        self.calls += 1
-        if self.calls == self.call:
-            with torch.no_grad():
-                self.model.state_dict()[self.key].view(-1)[0] = INF
-        return self.inner.compute_loss(*a)
-
-
-@pytest.fixture(scope='module')
-def world(manifest):
-    def batch(seed):
-        b = syn.make_batch(RAW, NPTS, 2, first_seed=seed)
-        return ([torch.from_numpy(b[k]).cuda() for k in ('pc', 'img', 'calib', 'A')],
-                {k: torch.from_numpy(v) for k, v in b['gt'].items()})
-    return {'sd': syn.synthetic_state_dict(manifest['state_dict'], 1), 'batches': [batch(0), batch(2), batch(4)]}
-
-
+# ---- Trainer, small configuration of tests/test_gpu_train.py (tests/train_harness.py) ----
 def _trainer(world, bad_calls=(), **kw):
-    from efgh_amd.losses import EFGHCriterion
-    from efgh_amd.nets import EFGHBackbone
-    from efgh_amd.train import Trainer
-    args = syn.default_args(RAW, 'cuda')
-    m = EFGHBackbone(args)
-    m.load_state_dict(world['sd'])
-    crit = EFGHCriterion(args)
-    return Trainer(m.cuda(), _InfOnCall(crit, bad_calls) if bad_calls else crit, lr=1e-3, **kw)
-
-
-def _step(tr, world, i):
-    inp, gt = world['batches'][i]
-    return tr.step(*inp, dict(gt))
+    return trainer(world, bad_calls, forward_names=True, **kw)
 
 
 def _np(t):
@@ -310,8 +253,6 @@ def test_every_step_follows_the_recipe(ema_run):
 
 
 def test_update_adds_no_aten_op_and_no_host_wait(world, plain_run, ema_run):
-    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..', 'tools'))
-    from glue_census import census
     # (placed ahead of the tests that take the averaging trainer through accumulated steps, eval forwards and checkpoints: here both
     # trainers have the same history, three plain steps, so the two counts compare like with like)
     plain, avg = plain_run['tr'], ema_run['tr']
@@ -322,14 +263,7 @@ def test_update_adds_no_aten_op_and_no_host_wait(world, plain_run, ema_run):
     print('aten ops per step: %d without the average, %d with it; more with it: %s' % (n_plain, n_avg, dict(c_avg - c_plain)))
     assert n_avg <= n_plain, (n_avg, n_plain, dict(c_avg - c_plain))
     assert sum(census(lambda: avg.ema.update(avg.opt)).values()) == 0
-    try:
-        torch.cuda.set_sync_debug_mode('error')
-    except (RuntimeError, AttributeError):         # this build cannot flag synchronising calls: nothing more to check
-        return
-    try:
-        avg.ema.update(avg.opt)
-    finally:
-        torch.cuda.set_sync_debug_mode('default')
+    waits_for_nothing(lambda: avg.ema.update(avg.opt))
 
 
 @pytest.mark.parametrize('route', ['gradient', 'forward_veto'])
@@ -361,17 +295,10 @@ def test_an_accumulated_step_moves_the_average_once(world, ema_run):
     tr = ema_run['tr']
     t0 = tr.opt.t
     prev = _np(tr.ema.buf)
-    tr.step_accumulated([tuple(world['batches'][i][0]) + (dict(world['batches'][i][1]),) for i in range(3)])
+    tr.step_accumulated([_mb(world, i) for i in range(3)])
     assert tr.opt.t == t0 + 1
     _within(_np(tr.ema.buf), prev, _np(tr.flat.w), contract.decay_at(0.999, True, t0 + 1), 'accumulated step, t = %d' % (t0 + 1))
     assert float(np.abs(_np(tr.ema.buf) - prev).max()) > 0
-
-
-def _eval_forward(model, world):
-    model.eval()
-    with torch.no_grad():
-        out = model(*world['batches'][2][0])
-    return {k: v.clone() for k, v in out.items() if torch.is_tensor(v)}
 
 
 def _same_outputs(a, b):
@@ -382,7 +309,7 @@ def _same_outputs(a, b):
 def test_the_scope_puts_the_averaged_weights_under_the_model(world, ema_run):
     from efgh_amd.nets import EFGHBackbone
     tr = ema_run['tr']
-    live = _eval_forward(tr.model, world)                                        # (packs and folds the LIVE weights)
+    live = eval_forward(tr.model, world)                                        # (packs and folds the LIVE weights)
     w, e = _bits(tr.flat.w), _bits(tr.ema.buf)
     sd = tr.ema_state_dict()
     now = tr.model.state_dict()
@@ -397,26 +324,26 @@ def test_the_scope_puts_the_averaged_weights_under_the_model(world, ema_run):
     assert torch.equal(torch.cat([sd[k].reshape(-1) for k, p in tr.model.named_parameters() if p.requires_grad]), tr.ema.buf)
     fresh = EFGHBackbone(syn.default_args(RAW, 'cuda'))
     fresh.load_state_dict(sd, strict=True)
-    want = _eval_forward(fresh.cuda(), world)
+    want = eval_forward(fresh.cuda(), world)
     assert not _same_outputs(live, want)                                         # the average is a different model
     with tr.ema_weights():
         assert torch.equal(_bits(tr.flat.w), e) and torch.equal(_bits(tr.ema.buf), w)
-        inside = _eval_forward(tr.model, world)                                  # a missed epoch bump would leave stale packed weights
+        inside = eval_forward(tr.model, world)                                  # a missed epoch bump would leave stale packed weights
         with pytest.raises(_C.EfghError):
             _step(tr, world, 0)
         with pytest.raises(_C.EfghError):
-            tr.step_accumulated([tuple(world['batches'][0][0]) + (dict(world['batches'][0][1]),)])
+            tr.step_accumulated([_mb(world, 0)])
         with pytest.raises(_C.EfghError):
             with tr.ema_weights():
                 pass
     assert _same_outputs(inside, want)
     assert torch.equal(_bits(tr.flat.w), w) and torch.equal(_bits(tr.ema.buf), e)
-    assert _same_outputs(_eval_forward(tr.model, world), live)
+    assert _same_outputs(eval_forward(tr.model, world), live)
     with pytest.raises(KeyError):                                                # an exception inside the scope still swaps back
         with tr.ema_weights():
             raise KeyError('x')
     assert torch.equal(_bits(tr.flat.w), w) and torch.equal(_bits(tr.ema.buf), e)
-    assert _same_outputs(_eval_forward(tr.model, world), live)
+    assert _same_outputs(eval_forward(tr.model, world), live)
     tr.model.train()
 
 

@@ -14,16 +14,11 @@ from efgh_amd import _C, ops, synthetic as syn
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import grad_accum_contract as contract  # noqa: E402
+from train_harness import INF, RAW, batch, bits as _bits, census, make_world, mb as _mb, model as _model, trainer as _trainer, waits_for_nothing  # noqa: E402
 
 pytestmark = pytest.mark.gpu
-RAW, NPTS = (128, 256), 2048
-INF = float('inf')
 SIZES = [1, 2, 3, 4, 5, 255, 256, 257, 1023, 1024, 1025, 1000003]        # the float4 and tail edges
 SPECIALS = [0.0, -0.0, np.inf, -np.inf, 1e-45, -1e-40, 1.1754942e-38]    # +-0, +-inf, denormals
-
-
-def _bits(t):
-    return t.detach().clone().view(torch.int32)
 
 
 # ---- efgh_grad_drain ----
@@ -127,67 +122,34 @@ def test_valid_count_is_exact_and_is_the_loss_kernels_count(hw, B):
             assert 0 < want < B * H * W
 
 
-# ---- Trainer, small configuration of tests/test_gpu_train.py ----
-class _InfOnCall:
-    """criterion whose `total` is multiplied by inf on the given calls (1-based): the forward stays finite, the gradient does not
-    (the wrapper of tests/test_gpu_grad_guard.py)"""
-
-    def __init__(self, inner, bad_calls):
-        self.inner, self.bad, self.calls = inner, set(bad_calls), 0
-
-    def compute_loss(self, *a):
-        losses, gt = self.inner.compute_loss(*a)
-        self.calls += 1
-        if self.calls in self.bad:
-            losses = dict(losses)
-            losses['total'] = losses['total'] * INF
-        return losses, gt
-
-
-def _batch(seed, size):
-    b = syn.make_batch(RAW, NPTS, size, first_seed=seed)
-    return tuple(torch.from_numpy(b[k]).cuda() for k in ('pc', 'img', 'calib', 'A')) + \
-        ({k: torch.from_numpy(v) for k, v in b['gt'].items()},)
-
-
+# ---- Trainer, small configuration of tests/test_gpu_train.py (tests/train_harness.py) ----
 @pytest.fixture(scope='module')
 def world(manifest):
-    return {'sd': syn.synthetic_state_dict(manifest['state_dict'], 1), 'batches': [_batch(0, 2), _batch(2, 2), _batch(4, 2)],
-            'singles': [_batch(i, 1) for i in range(3)]}
-
-
-def _model(world):
-    from efgh_amd.nets import EFGHBackbone
-    m = EFGHBackbone(syn.default_args(RAW, 'cuda'))
-    m.load_state_dict(world['sd'])
-    return m.cuda()
-
-
-def _trainer(world, bad_calls=(), lr=1e-3, **kw):
-    from efgh_amd.losses import EFGHCriterion
-    from efgh_amd.train import Trainer
-    crit = EFGHCriterion(syn.default_args(RAW, 'cuda'))
-    return Trainer(_model(world), _InfOnCall(crit, bad_calls) if bad_calls else crit, lr=lr, **kw)
-
-
-def _mb(world, i):
-    inp = world['batches'][i]
-    return inp[:4] + (dict(inp[4]),)
+    return dict(make_world(manifest), singles=[batch(i, 1) for i in range(3)])
 
 
 def _state(tr):
-    return [_bits(t) for t in (tr.flat.w, tr.opt.m, tr.opt.v)]
+    """the bits of weights and moments - and of the average, the BatchNorm statistics and the counters where the options keep them"""
+    extra = ([tr.ema.buf] if tr.ema is not None else []) + ([tr.txn.live, tr.flat.nbt] if tr.txn is not None else [])
+    return [_bits(t) if t.dtype == torch.float32 else t.clone() for t in [tr.flat.w, tr.opt.m, tr.opt.v] + extra]
 
 
 def _same(a, b):
     return all(torch.equal(x, y) for x, y in zip(a, b))
 
 
-@pytest.mark.parametrize('route', ['plain', 'skip_nonfinite', 'measure_only'])
+ROUTES = {'plain': {}, 'skip_nonfinite': {'skip_nonfinite': True}, 'measure_only': {'max_grad_norm': INF},
+          'all_options': {'max_grad_norm': 1.0, 'skip_nonfinite': True, 'transactional': True, 'ema_decay': 0.999}}
+
+
+@pytest.mark.parametrize('route', list(ROUTES))
 def test_one_micro_batch_is_a_plain_step(world, route):
-    kw = {'plain': {}, 'skip_nonfinite': {'skip_nonfinite': True}, 'measure_only': {'max_grad_norm': INF}}[route]
+    """what holds the two entry points of the step core together: the same kernels on the same bits, so equality is exact - with
+    every option on (all_options) also for the average, the BatchNorm statistics and counters, and the guard's whole report"""
+    kw = ROUTES[route]
     a, b = _trainer(world, **kw), _trainer(world, **kw)
     assert _same(_state(a), _state(b))
+    assert len(_state(a)) == (6 if route == 'all_options' else 3)
     w0 = a.flat.w.clone()
     for i in (0, 2):
         la, _ = a.step(*_mb(world, i))
@@ -199,7 +161,12 @@ def test_one_micro_batch_is_a_plain_step(world, route):
     assert float((a.flat.w - w0).abs().max()) > 0
     if route != 'plain':
         sa, sb = a.guard_stats(), b.guard_stats()
-        assert sa == sb and sa['applied'] == 2 and sa['coef'] == 1.0
+        assert sa == sb and sa['applied'] == 2
+        if route == 'all_options':                                 # a finite clip: the coefficient is below 1 on this net
+            assert sa['coef'] < 1.0 and sa['coef'] == sb['coef']
+            assert (sa['rolled_back'], sa['forward_nonfinite']) == (0, 0) and float((a.ema.buf - a.flat.w).abs().max()) > 0
+        else:
+            assert sa['coef'] == 1.0
 
 
 def _micro_gradient(tr, mb):
@@ -248,7 +215,7 @@ def test_three_micro_batches_equal_dataparallel_on_the_real_net(world):
     an exact 1/2 on both sides)."""
     from efgh_amd.losses import EFGHCriterion
     k = 3
-    mbs = lambda: [s[:4] + (dict(s[4]),) for s in world['singles']]
+    mbs = lambda: [tuple(inp) + (dict(gt),) for inp, gt in world['singles']]
     tr = _trainer(world, lr=0.0)
     w0 = _bits(tr.flat.w)
     weights = tr.depth_weights(mbs()).cpu().numpy()
@@ -260,12 +227,12 @@ def test_three_micro_batches_equal_dataparallel_on_the_real_net(world):
         assert torch.equal(_bits(tr.flat.w), w0) and len(preds) == k
         got[exact] = (tr.accum.acc.double() / k, {n: float(v) for n, v in losses.items()})
     # the reference
-    m = _model(world).train()
+    m = _model(world['sd']).train()
     crit = EFGHCriterion(syn.default_args(RAW, 'cuda'))
-    ps = [m(*s[:4]) for s in world['singles']]
+    ps = [m(*inp) for inp, _ in world['singles']]
     pred = {n: (torch.cat([p[n] for p in ps], 0) if torch.is_tensor(ps[0][n]) else ps[0][n]) for n in ps[0]}
-    inp = [torch.cat([s[j] for s in world['singles']], 0) for j in range(4)]
-    gt = {n: torch.cat([s[4][n] for s in world['singles']], 0) for n in world['singles'][0][4]}
+    inp = [torch.cat([s[0][j] for s in world['singles']], 0) for j in range(4)]
+    gt = {n: torch.cat([s[1][n] for s in world['singles']], 0) for n in world['singles'][0][1]}
     L, _ = crit.compute_loss(*inp, gt, pred)
     L['total'].backward()
     torch.cuda.synchronize()
@@ -335,8 +302,8 @@ def test_bookkeeping_and_the_micro_batches_argument(world):
     step, three BatchNorm ticks; then a plain step() - against a Trainer that took the same two updates through
     step_accumulated([..]) on the explicit micro-batches and step_accumulated([b])"""
     a, b = _trainer(world), _trainer(world)
-    cat = [torch.cat([world['batches'][i][j] for i in range(3)], 0) for j in range(4)]
-    gt = {n: torch.cat([world['batches'][i][4][n] for i in range(3)], 0) for n in world['batches'][0][4]}
+    cat = [torch.cat([world['batches'][i][0][j] for i in range(3)], 0) for j in range(4)]
+    gt = {n: torch.cat([world['batches'][i][1][n] for i in range(3)], 0) for n in world['batches'][0][1]}
     nbt0 = a.flat.nbt.clone()
     assert nbt0.numel() > 50
     losses, preds = a.step(*cat, gt, micro_batches=3)
@@ -397,8 +364,6 @@ def test_activation_memory_is_that_of_one_micro_batch(world):
 
 
 def test_no_host_sync_and_no_aten_op_in_the_new_pieces(world):
-    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..', 'tools'))
-    from glue_census import census
     tr = _trainer(world)
     mbs = [mb[:4] + ({n: v.cuda() for n, v in mb[4].items()},) for mb in (_mb(world, i) for i in range(3))]
     tr.step_accumulated(mbs)
@@ -408,15 +373,7 @@ def test_no_host_sync_and_no_aten_op_in_the_new_pieces(world):
     want = contract.depth_weights([int(((ops.depth_image(mb[0], mb[4]['cam_T_velo'].float(), *RAW)[0][..., 3] > 0)
                                         & (mb[4]['img_mask'].view(-1, *RAW) > 0)).sum()) for mb in mbs])
     assert np.array_equal(tr.depth_weights(mbs).cpu().numpy(), want)      # the weight rule of the contract, bit for bit
-    try:
-        torch.cuda.set_sync_debug_mode('error')
-    except (RuntimeError, AttributeError):         # this build cannot flag synchronising calls: nothing more to check
-        return
-    try:
-        tr.accum.drain()
-        tr.depth_weights(mbs)
-    finally:
-        torch.cuda.set_sync_debug_mode('default')
+    waits_for_nothing(lambda: (tr.accum.drain(), tr.depth_weights(mbs)))
 
 
 def test_example_loop_accumulates():

@@ -13,11 +13,10 @@ from efgh_amd import _C, synthetic as syn
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import grad_guard_contract as contract  # noqa: E402
+from train_harness import INF, RAW, bits as _bits, census, step as _step, trainer as _trainer, waits_for_nothing, world  # noqa: E402,F401
 
 pytestmark = pytest.mark.gpu
-RAW, NPTS = (128, 256), 2048
 L = _C.GUARD_RUN
-INF = float('inf')
 SIZES = [1, 2, 3, 4, 5, 255, 256, 257, L - 1, L, L + 1, 3 * L + 5, 1000003]
 
 
@@ -191,10 +190,6 @@ def _flat3():
     return flat
 
 
-def _bits(t):
-    return t.detach().clone().view(torch.int32)
-
-
 def _yardstick(w, w64):
     """the project's FusedAdam-vs-torch bound (tests/test_gpu_train.py): |w - w64| <= 2e-6 + 1e-5 max|w64|"""
     d = float(np.abs(w.astype(np.float64) - w64).max())
@@ -264,47 +259,7 @@ def test_nonfinite_gradient_propagates_as_in_torch_without_skipping():
     assert stats['nonfinite'] == 1 and stats['applied'] == 1 and stats['skipped'] == 0 and math.isnan(stats['coef'])
 
 
-# ---- Trainer, small configuration of tests/test_gpu_train.py ----
-class _InfOnCall:
-    """criterion whose `total` is multiplied by inf on the given calls (1-based): the forward stays finite, the gradient does not"""
-
-    def __init__(self, inner, bad_calls):
-        self.inner, self.bad, self.calls = inner, set(bad_calls), 0
-
-    def compute_loss(self, *a):
-        losses, gt = self.inner.compute_loss(*a)
-        self.calls += 1
-        if self.calls in self.bad:
-            losses = dict(losses)
-            losses['total'] = losses['total'] * INF
-        return losses, gt
-
-
-@pytest.fixture(scope='module')
-def world(manifest):
-    def batch(seed):
-        b = syn.make_batch(RAW, NPTS, 2, first_seed=seed)
-        return ([torch.from_numpy(b[k]).cuda() for k in ('pc', 'img', 'calib', 'A')],
-                {k: torch.from_numpy(v) for k, v in b['gt'].items()})
-    return {'sd': syn.synthetic_state_dict(manifest['state_dict'], 1), 'batches': [batch(0), batch(2), batch(4)]}
-
-
-def _trainer(world, bad_calls=(), **kw):
-    from efgh_amd.losses import EFGHCriterion
-    from efgh_amd.nets import EFGHBackbone
-    from efgh_amd.train import Trainer
-    args = syn.default_args(RAW, 'cuda')
-    m = EFGHBackbone(args)
-    m.load_state_dict(world['sd'])
-    crit = EFGHCriterion(args)
-    return Trainer(m.cuda(), _InfOnCall(crit, bad_calls) if bad_calls else crit, lr=1e-3, **kw)
-
-
-def _step(tr, world, i):
-    inp, gt = world['batches'][i]
-    return tr.step(*inp, dict(gt))
-
-
+# ---- Trainer, small configuration of tests/test_gpu_train.py (tests/train_harness.py) ----
 @pytest.fixture(scope='module')
 def default_run(world):
     """a Trainer with defaults after batches 0 and 2"""
@@ -427,8 +382,6 @@ def test_checkpoint_carries_the_applied_step_count(world, skip_run):
 
 
 def test_guarded_step_adds_no_aten_ops_and_no_host_sync(world, default_run, measured_run):
-    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..', 'tools'))
-    from glue_census import census
     plain, guarded = default_run['tr'], measured_run['tr']
     for tr in (plain, guarded):
         _step(tr, world, 0)
@@ -437,11 +390,4 @@ def test_guarded_step_adds_no_aten_ops_and_no_host_sync(world, default_run, meas
     assert n_guarded <= n_plain, (n_guarded, n_plain)
     # the optimizer step alone: no aten op at all, and nothing that waits for the device
     assert sum(census(lambda: guarded.opt.step()).values()) == 0
-    try:
-        torch.cuda.set_sync_debug_mode('error')
-    except (RuntimeError, AttributeError):         # this build cannot flag synchronising calls: nothing more to check
-        return
-    try:
-        guarded.opt.step()
-    finally:
-        torch.cuda.set_sync_debug_mode('default')
+    waits_for_nothing(guarded.opt.step)

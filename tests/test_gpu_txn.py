@@ -13,10 +13,10 @@ from efgh_amd import _C, synthetic as syn
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import txn_contract as contract  # noqa: E402
+from train_harness import (INF, NAN, RAW, SpoilOnCall as _SpoilOnCall, batch, census, eval_forward, make_world, step as _step,  # noqa: E402
+                           trainer as _trainer, waits_for_nothing)
 
 pytestmark = pytest.mark.gpu
-RAW, NPTS = (128, 256), 2048
-INF, NAN = float('inf'), float('nan')
 GS, TS = ctypes.sizeof(_C.GuardState), ctypes.sizeof(_C.TxnState)
 
 
@@ -233,48 +233,13 @@ def test_veto_rewrites_the_guard_block_as_a_skip_would():
 
 
 # ---------------------------------------------------------------- Trainer, small configuration of tests/test_gpu_grad_guard.py
-class _InfOnCall:
-    """criterion whose `total` is multiplied by inf on the given calls (1-based): the forward stays finite, the gradient does not"""
-
-    def __init__(self, inner, bad_calls):
-        self.inner, self.bad, self.calls = inner, set(bad_calls), 0
-
-    def compute_loss(self, *a):
-        losses, gt = self.inner.compute_loss(*a)
-        self.calls += 1
-        if self.calls in self.bad:
-            losses = dict(losses)
-            losses['total'] = losses['total'] * INF
-        return losses, gt
-
-
 @pytest.fixture(scope='module')
 def world(manifest):
-    def batch(seed):
-        b = syn.make_batch(RAW, NPTS, 2, first_seed=seed)
-        return ([torch.from_numpy(b[k]).cuda() for k in ('pc', 'img', 'calib', 'A')],
-                {k: torch.from_numpy(v) for k, v in b['gt'].items()})
-    batches = [batch(0), batch(2), batch(4)]
+    w = make_world(manifest)
     inp, gt = batch(2)
-    inp[1] = inp[1].clone()
     inp[1][1, 0, 40, 100] = NAN                              # ONE NaN pixel in the second image
-    return {'sd': syn.synthetic_state_dict(manifest['state_dict'], 1), 'batches': batches, 'nan': (inp, gt)}
-
-
-def _trainer(world, bad_calls=(), **kw):
-    from efgh_amd.losses import EFGHCriterion
-    from efgh_amd.nets import EFGHBackbone
-    from efgh_amd.train import Trainer
-    args = syn.default_args(RAW, 'cuda')
-    m = EFGHBackbone(args)
-    m.load_state_dict(world['sd'])
-    crit = EFGHCriterion(args)
-    return Trainer(m.cuda(), _InfOnCall(crit, bad_calls) if bad_calls else crit, lr=1e-3, **kw)
-
-
-def _step(tr, world, i, **kw):
-    inp, gt = world['nan'] if i == 'nan' else world['batches'][i]
-    return tr.step(*inp, dict(gt), **kw)
+    w['nan'] = (inp, gt)
+    return w
 
 
 def _entries(tr):
@@ -349,13 +314,6 @@ def test_without_the_option_the_skipped_step_leaves_its_mark(world):
     assert any(k.endswith('running_mean') for k in diff) and any(k.endswith('running_var') for k in diff)
 
 
-def _eval_forward(tr, world):
-    tr.model.eval()
-    with torch.no_grad():
-        out = tr.model(*world['batches'][2][0])
-    return {k: v.clone() for k, v in out.items() if torch.is_tensor(v)}
-
-
 def test_a_nonfinite_forward_is_seen_and_undone(world, clean_runs):
     """One NaN pixel in the second image of a batch.  Measured on an MI355X when this test was written: 16 205 running statistics
     became non-finite, the first in `H.vgg.features.1.running_mean`; the gradient came out non-finite as well (37 215 058 elements),
@@ -364,7 +322,7 @@ def test_a_nonfinite_forward_is_seen_and_undone(world, clean_runs):
     tr = _trainer(world, skip_nonfinite=True, transactional=True)
     _step(tr, world, 0)
     before = _entries(tr)
-    e0, e1 = _eval_forward(tr, world), _eval_forward(tr, world)
+    e0, e1 = eval_forward(tr.model, world), eval_forward(tr.model, world)
     assert _differing(e0, e1) == []                                          # (the eval forward repeats itself bit for bit)
     _step(tr, world, 'nan')
     s = tr.guard_stats()
@@ -374,7 +332,7 @@ def test_a_nonfinite_forward_is_seen_and_undone(world, clean_runs):
     assert (s['skipped'], s['applied'], s['rolled_back']) == (1, 1, 1)        # skipped, whether or not the gradient came out finite
     assert s['vetoed'] == (1 if s['nonfinite'] == 0 else 0)
     assert _differing(before, _entries(tr)) == []
-    assert _differing(e0, _eval_forward(tr, world)) == []                    # the folded eval affine was rebuilt from restored values
+    assert _differing(e0, eval_forward(tr.model, world)) == []               # the folded eval affine was rebuilt from restored values
     _step(tr, world, 2)
     assert tr.guard_stats()['applied'] == 2 and tr.guard_stats()['forward_nonfinite'] == 0
     # against the run that never saw the bad batch: the yardstick of test_trainer_skips_a_nonfinite_step, per parameter and buffer
@@ -390,21 +348,6 @@ def test_a_nonfinite_forward_is_seen_and_undone(world, clean_runs):
     print('after the following clean step: %d of %d entries differ in bits from the clean run, worst |d| / bound = %.3g'
           % (len(_differing(mine, clean)), len(clean), worst))
     assert bool(torch.isfinite(tr.txn.live).all())
-
-
-class _SpoilOnCall:
-    """criterion that writes +inf into one running statistic on the given call (1-based), after the forward: loss and gradient stay
-    finite - the case the deferred activations can produce, which only the probe sees"""
-
-    def __init__(self, inner, model, key, call):
-        self.inner, self.model, self.key, self.call, self.calls = inner, model, key, call, 0
-
-    def compute_loss(self, *a):
-        self.calls += 1
-        if self.calls == self.call:
-            with torch.no_grad():
-                self.model.state_dict()[self.key].view(-1)[0] = INF
-        return self.inner.compute_loss(*a)
 
 
 def test_a_finite_gradient_is_vetoed_by_a_spoiled_buffer(world):
@@ -429,8 +372,7 @@ def test_a_finite_gradient_is_vetoed_by_a_spoiled_buffer(world):
 def test_accumulated_step_rolls_back_every_micro_batch(world):
     tr = _trainer(world, skip_nonfinite=True, transactional=True)
     before, c0 = _entries(tr), _counters(tr)
-    inp, gt = world['nan']                                                   # the NaN pixel is in the second micro-batch
-    tr.step(*inp, dict(gt), micro_batches=2)
+    _step(tr, world, 'nan', micro_batches=2)                                 # the NaN pixel is in the second micro-batch
     s = tr.guard_stats()
     assert s['forward_nonfinite'] > 0 and (s['skipped'], s['applied'], s['rolled_back']) == (1, 0, 1)
     assert _differing(before, _entries(tr)) == []
@@ -453,8 +395,6 @@ def test_no_side_effects_when_nothing_is_wrong(clean_runs):
 
 
 def test_transactional_step_adds_no_aten_ops_and_no_host_sync(world, clean_runs):
-    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..', 'tools'))
-    from glue_census import census
     guarded, txn = clean_runs['guard']['tr'], clean_runs['txn']['tr']
     n_guarded = sum(census(lambda: _step(guarded, world, 0)).values())
     n_txn = sum(census(lambda: _step(txn, world, 0)).values())
@@ -467,14 +407,7 @@ def test_transactional_step_adds_no_aten_ops_and_no_host_sync(world, clean_runs)
         t.probe(loss, 1, 1)
         t.resolve(txn.opt.state, txn.opt.betas)
     assert sum(census(three).values()) == 0
-    try:
-        torch.cuda.set_sync_debug_mode('error')
-    except (RuntimeError, AttributeError):         # this build cannot flag synchronising calls: nothing more to check
-        return
-    try:
-        three()
-    finally:
-        torch.cuda.set_sync_debug_mode('default')
+    waits_for_nothing(three)
 
 
 def test_checkpoint_after_a_skipped_step(world, skip_run):

@@ -8,18 +8,14 @@
      (`--no-step` leaves this part out).
 
     python tools/bench_ema.py [--out profiles/ema.txt]"""
-import argparse
 import ctypes
-import os
 import statistics
 import sys
-import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-import torch  # noqa: E402
+import cost_scaffold as cs
+import torch
 
-from efgh_amd import _C, ops, synthetic as syn  # noqa: E402
+from efgh_amd import _C, ops
 
 N_FULL = 47810443
 
@@ -43,30 +39,12 @@ def kernels(a, lines):
              ('efgh_ema_update, state block', lambda: ops.ema_update(ema, w, 0.999, True, 0, state), 12 * n),
              ('efgh_ema_swap', lambda: ops.ema_swap(ema, other), 16 * n)]
 
-    def window(fn):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(a.calls):
-            fn()
-        e1.record()
-        torch.cuda.synchronize()
-        return e0.elapsed_time(e1) * 1e3 / a.calls            # us per call
-
-    for _, fn, _ in names:
-        fn()
-    torch.cuda.synchronize()
-    times = {k: [] for k, _, _ in names}
-    for _ in range(a.rounds):
-        for k, fn, _ in names:
-            times[k].append(window(fn))
+    times = cs.alternate(names, a.rounds, a.calls)
     lines += ['weight average at n = %d (%.0f MB per buffer)' % (n, 4 * n / 1e6),
               'one run on one MI355X; %d rounds, the forms alternating; a window = %d back-to-back calls (device events, us per call)'
               % (a.rounds, a.calls),
               '%-30s %10s %10s %10s %10s %10s' % ('', 'median us', 'min us', 'max us', 'MB moved', 'TB/s')]
-    for k, _, nbytes in names:
-        t = times[k]
-        med = statistics.median(t)
-        lines.append('%-30s %10.2f %10.2f %10.2f %10.0f %10.2f' % (k, med, min(t), max(t), nbytes / 1e6, nbytes / med / 1e6))
+    lines += cs.table(names, times, '%-30s %10.2f %10.2f %10.2f %10.0f %10.2f', lambda nbytes, med: (nbytes / 1e6, nbytes / med / 1e6))
     med = {k: statistics.median(t) for k, t in times.items()}
     worst = max(med['efgh_ema_update, host step'], med['efgh_ema_update, state block'])
     ok = worst < med['efgh_adam_step']
@@ -76,34 +54,7 @@ def kernels(a, lines):
 
 
 def steps(a, lines):
-    from efgh_amd.losses import EFGHCriterion
-    from efgh_amd.nets import EFGHBackbone
-    from efgh_amd.train import Trainer
-    raw, npts, B = (768, 2560), 131072, 8
-    dev = torch.device('cuda', 0)
-    args = syn.default_args(raw, 'cuda')
-    batch = syn.make_batch(raw, npts, B, first_seed=0)
-    inp = [torch.from_numpy(batch[k]).to(dev) for k in ('pc', 'img', 'calib', 'A')]
-    gt = {k: torch.from_numpy(v).to(dev) for k, v in batch['gt'].items()}
-    forms = []
-    for name, kw in (('Trainer()', {}), ('Trainer(ema_decay=0.999)', {'ema_decay': 0.999})):
-        torch.manual_seed(0)
-        forms.append((name, Trainer(EFGHBackbone(args).to(dev), EFGHCriterion(args), lr=1e-4, **kw)))
-    for _, tr in forms:
-        for _ in range(a.warmup):
-            tr.step(*inp, gt)
-    times = {name: [] for name, _ in forms}
-    for _ in range(a.step_rounds):
-        for name, tr in forms:
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            for _ in range(a.steps):
-                tr.step(*inp, gt)
-            torch.cuda.synchronize()
-            times[name].append((time.perf_counter() - t0) * 1e3 / a.steps)
-    lines.append('config S (%dx%d raw, %d points, batch %d), Trainer.step; %d rounds of %d steps per form after %d warm-up steps, the two '
-                 'forms alternating; wall clock around a device synchronisation, ms per step'
-                 % (raw[0], raw[1], npts, B, a.step_rounds, a.steps, a.warmup))
+    forms, times = cs.compare_trainers(a, lines, [('Trainer()', {}), ('Trainer(ema_decay=0.999)', {'ema_decay': 0.999})])
     for name, tr in forms:
         t = times[name]
         lines.append('%-28s median %8.2f  min %8.2f  max %8.2f   (n = %d, %s)'
@@ -115,25 +66,8 @@ def steps(a, lines):
 
 
 def main(argv=None):
-    ap = argparse.ArgumentParser()
-    ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'ema.txt'))
-    ap.add_argument('--n', type=int, default=N_FULL)
-    ap.add_argument('--rounds', type=int, default=9)
-    ap.add_argument('--calls', type=int, default=20, help='calls per timed window')
-    ap.add_argument('--steps', type=int, default=5)
-    ap.add_argument('--step-rounds', type=int, default=3)
-    ap.add_argument('--warmup', type=int, default=2)
-    ap.add_argument('--no-step', action='store_true', help='kernels only')
-    a = ap.parse_args(argv)
-    lines = []
-    ok = kernels(a, lines)
-    if not a.no_step:
-        torch.cuda.empty_cache()
-        steps(a, lines)
-    text = '\n'.join(lines) + '\n'
-    print(text, end='')
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    open(a.out, 'w').write(text)
+    ok = cs.main(argv, 'ema.txt', kernels, steps, (20, 'calls per timed window'),
+                 extra=[('--n', {'type': int, 'default': N_FULL}), ('--step-rounds', {'type': int, 'default': 3})])
     return 0 if ok else 1
 
 

@@ -9,17 +9,13 @@
     python tools/bench_grad_accum.py [--out profiles/grad_accum.txt]
 
 Bytes: the drain moves 12 n with `first` (read g; write acc, g) and 16 n otherwise; k_adam moves 28 n."""
-import argparse
-import os
 import statistics
-import sys
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-import torch  # noqa: E402
+import cost_scaffold as cs
+import torch
 
-from efgh_amd import _C, ops, synthetic as syn  # noqa: E402
+from efgh_amd import _C, ops
 
 N = 47810443
 
@@ -40,71 +36,45 @@ def kernels(a, lines):
         s['acc'].add_(s['g'])
         s['g'].zero_()
 
-    def window(fn):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for i in range(a.calls):
-            fn(sets[i % a.sets])
-        e1.record()
-        torch.cuda.synchronize()
-        return e0.elapsed_time(e1) * 1e3 / a.calls            # us per call
+    def rotating(fn, over):                                   # every call works on the next buffer set
+        i = [0]
 
-    names = [('efgh_grad_drain first', lambda s: ops.grad_drain(s['acc'], s['g'], True), 12 * n),
-             ('efgh_grad_drain', lambda s: ops.grad_drain(s['acc'], s['g'], False), 16 * n),
-             ('acc.add_(g) + g.zero_()', torch_pair, 16 * n),
-             ('efgh_adam_step', adam, 28 * n)]
-    for s in sets:
-        for _, fn, _ in names:
-            fn(s)
-    torch.cuda.synchronize()
-    times = {k: [] for k, _, _ in names}
-    for _ in range(a.rounds):
-        for k, fn, _ in names:
-            times[k].append(window(fn))
+        def call():
+            fn(over[i[0] % len(over)])
+            i[0] += 1
+        return call
+
+    names = [('efgh_grad_drain first', rotating(lambda s: ops.grad_drain(s['acc'], s['g'], True), sets), 12 * n),
+             ('efgh_grad_drain', rotating(lambda s: ops.grad_drain(s['acc'], s['g'], False), sets), 16 * n),
+             ('acc.add_(g) + g.zero_()', rotating(torch_pair, sets), 16 * n),
+             ('efgh_adam_step', rotating(adam, sets), 28 * n)]
+    times = cs.alternate(names, a.rounds, a.calls, warm=a.sets)
     lines += ['gradient accumulation at n = %d' % n,
               'one run on one MI355X; %d rounds, the four alternating; a window = %d back-to-back calls over %d buffer sets (device '
               'events, us per call)' % (a.rounds, a.calls, a.sets),
               '%-26s %10s %10s %10s %10s' % ('', 'median us', 'min us', 'max us', 'GB/s (median)')]
-    med = {}
-    for k, _, nbytes in names:
-        t = times[k]
-        med[k] = statistics.median(t)
-        lines.append('%-26s %10.1f %10.1f %10.1f %10.0f' % (k, med[k], min(t), max(t), nbytes / med[k] / 1e3))
+    lines += cs.table(names, times, '%-26s %10.1f %10.1f %10.1f %10.0f', lambda nbytes, med: (nbytes / med / 1e3,))
+    med = {k: statistics.median(t) for k, t in times.items()}
     lines.append('efgh_grad_drain / efgh_adam_step = %.3f (byte ratio 16n / 28n = 0.571); / the torch pair = %.3f'
                  % (med['efgh_grad_drain'] / med['efgh_adam_step'], med['efgh_grad_drain'] / med['acc.add_(g) + g.zero_()']))
-    del sets
+    del sets, names
     # the valid count at the full raw size, batch 8
     B, H, W = 8, 768, 2560
     imgs = [torch.rand(B, H, W, 4, device=dev) - 0.5 for _ in range(a.sets)]
     masks = [(torch.rand(B, 1, H, W, device=dev) > 0.1).to(torch.uint8) for _ in range(a.sets)]
     count = torch.zeros(1, dtype=torch.int64, device=dev)
-    ts = []
-    for r in range(a.rounds + 1):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for i in range(a.calls):
-            ops.gimg_valid_count(imgs[i % a.sets], masks[i % a.sets], count)
-        e1.record()
-        torch.cuda.synchronize()
-        if r:
-            ts.append(e0.elapsed_time(e1) * 1e3 / a.calls)
+    valid_count = rotating(lambda s: ops.gimg_valid_count(s[0], s[1], count), list(zip(imgs, masks)))
+    ts = [cs.window(valid_count, a.calls) for _ in range(a.rounds + 1)][1:]          # (the first window warms up)
     nbytes = B * H * W * 17                                    # (the 16-byte pixel's sector is fetched for its one depth word)
     lines.append('efgh_gimg_valid_count %dx%dx%d: median %.1f us (min %.1f, max %.1f), %.0f GB/s of the %d bytes it touches'
                  % (H, W, B, statistics.median(ts), min(ts), max(ts), nbytes / statistics.median(ts) / 1e3, nbytes))
 
 
 def steps(a, lines):
-    from efgh_amd.losses import EFGHCriterion
-    from efgh_amd.nets import EFGHBackbone
-    from efgh_amd.train import Trainer, split_micro_batches
-    raw, npts, B = (768, 2560), 131072, 8
-    dev = torch.device('cuda', 0)
-    args = syn.default_args(raw, 'cuda')
-    torch.manual_seed(0)
-    tr = Trainer(EFGHBackbone(args).to(dev), EFGHCriterion(args), lr=1e-4)
-    batch = syn.make_batch(raw, npts, B, first_seed=0)
-    inp = [torch.from_numpy(batch[k]).to(dev) for k in ('pc', 'img', 'calib', 'A')]
-    gt = {k: torch.from_numpy(v).to(dev) for k, v in batch['gt'].items()}
+    from efgh_amd.train import split_micro_batches
+    raw, npts = cs.RAW, cs.NPTS
+    args, inp, gt = cs.config_s()
+    tr = cs.trainer(args)
     mbs = split_micro_batches(*inp, gt, 2)
     forms = [('step, batch 8', lambda: tr.step(*inp, gt)),
              ('step_accumulated, 2 micro-batches of 4', lambda: tr.step_accumulated(mbs)),
@@ -126,24 +96,8 @@ def steps(a, lines):
 
 
 def main(argv=None):
-    ap = argparse.ArgumentParser()
-    ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'grad_accum.txt'))
-    ap.add_argument('--rounds', type=int, default=9)
-    ap.add_argument('--calls', type=int, default=12, help='calls per timed window (a multiple of --sets)')
-    ap.add_argument('--sets', type=int, default=3)
-    ap.add_argument('--steps', type=int, default=5)
-    ap.add_argument('--warmup', type=int, default=2)
-    ap.add_argument('--no-step', action='store_true', help='kernels only')
-    a = ap.parse_args(argv)
-    lines = []
-    kernels(a, lines)
-    if not a.no_step:
-        torch.cuda.empty_cache()
-        steps(a, lines)
-    text = '\n'.join(lines) + '\n'
-    print(text, end='')
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    open(a.out, 'w').write(text)
+    cs.main(argv, 'grad_accum.txt', kernels, steps, (12, 'calls per timed window (a multiple of --sets)'),
+            extra=[('--sets', {'type': int, 'default': 3})])
 
 
 if __name__ == '__main__':
