@@ -64,6 +64,17 @@ class TxnState(ctypes.Structure):
                 ('first_bad', c_int32), ('vetoed', c_int32)]
 
 
+ADAM_MAX_GROUPS = 16     # EFGH_ADAM_MAX_GROUPS
+ADAM_MAX_SEGMENTS = 4096 # EFGH_ADAM_MAX_SEGMENTS
+
+
+class AdamGroups(ctypes.Structure):
+    """mirror of efgh_adam_groups (include/efgh_hip.h): the per-group values of efgh_adam_step_groups, a HOST struct"""
+    _fields_ = [('n_groups', c_int32), ('step', c_int32), ('beta1', c_float), ('beta2', c_float), ('eps', c_float),
+                ('grad_scale', c_float), ('lr', c_float * ADAM_MAX_GROUPS), ('weight_decay', c_float * ADAM_MAX_GROUPS),
+                ('decay', c_float * ADAM_MAX_GROUPS), ('decoupled', c_int32 * ADAM_MAX_GROUPS)]
+
+
 WROTE_OUT = 1            # EFGH_WROTE_OUT
 
 
@@ -133,6 +144,9 @@ def lib():
                                           c_float, c_void_p]
         _lib.efgh_ema_update.argtypes = [c_void_p, c_void_p, c_int64, c_float, c_int32, c_int64, c_void_p, c_void_p]
         _lib.efgh_ema_swap.argtypes = [c_void_p, c_void_p, c_int64, c_void_p]
+        _lib.efgh_adam_step_groups.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int32,
+                                               ctypes.POINTER(c_int64), ctypes.POINTER(ctypes.c_uint8),
+                                               ctypes.POINTER(AdamGroups), c_void_p, c_int32, c_void_p]
     return _lib
 
 

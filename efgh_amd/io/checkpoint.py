@@ -64,32 +64,84 @@ def load_pretrained(model, ckpt, convert_dict=None, grad_false_keys=None):
     return res
 
 
+def _torch_group(lr, betas, eps, wd, params):
+    return {'lr': lr, 'betas': tuple(betas), 'eps': eps,
+            'weight_decay': wd, 'amsgrad': False, 'maximize': False, 'foreach': None, 'capturable': False,
+            'differentiable': False, 'fused': None, 'params': params}
+
+
+def adam_numbering(opt):
+    """flat parameter indices in torch's state_dict numbering: group by group, in each group's own order (the identity without
+    parameter groups, and whenever every group is one contiguous run of the flat order)"""
+    if getattr(opt, 'param_groups', None) is None:
+        return list(range(len(opt.flat.params)))
+    return [i for g in opt.param_groups for i in g['params']]
+
+
 def adam_state_dict(opt, lr=None):
-    """`torch.optim.Adam.state_dict()`-compatible view of a train.FusedAdam (one entry per parameter)."""
+    """`torch.optim.Adam.state_dict()`-compatible view of a train.FusedAdam (one entry per parameter).  With parameter groups: one
+    entry of `param_groups` per group, `params` numbered group by group as torch numbers them, every group with its own lr /
+    weight_decay and `decoupled_weight_decay` (torch.optim.Adam's key for AdamW's decay)."""
     flat = opt.flat
     state = {}
     t = opt.t           # read ONCE: with the gradient guard's skip_nonfinite the count of APPLIED steps lives on the device
-    for i, (p, (off, k)) in enumerate(zip(flat.params, flat.offsets)):
+    order = adam_numbering(opt)
+    for j, i in enumerate(order):
+        p, (off, k) = flat.params[i], flat.offsets[i]
         if t > 0:
-            state[i] = {'step': torch.tensor(float(t)),
+            state[j] = {'step': torch.tensor(float(t)),
                         'exp_avg': opt.m[off:off + k].view(p.shape).detach().clone(),
                         'exp_avg_sq': opt.v[off:off + k].view(p.shape).detach().clone()}
-    group = {'lr': opt.lr if lr is None else lr, 'betas': tuple(opt.betas), 'eps': opt.eps,
-             'weight_decay': opt.wd, 'amsgrad': False, 'maximize': False, 'foreach': None, 'capturable': False,
-             'differentiable': False, 'fused': None, 'params': list(range(len(flat.params)))}
-    return {'state': state, 'param_groups': [group]}
+    if getattr(opt, 'param_groups', None) is None:
+        return {'state': state, 'param_groups': [_torch_group(opt.lr if lr is None else lr, opt.betas, opt.eps, opt.wd, order)]}
+    groups, j = [], 0
+    for g in opt.param_groups:
+        group = _torch_group(g['lr'], opt.betas, opt.eps, g['weight_decay'], list(range(j, j + len(g['params']))))
+        group['decoupled_weight_decay'] = bool(g['decoupled'])
+        groups.append(group)
+        j += len(g['params'])
+    return {'state': state, 'param_groups': groups}
 
 
 def load_adam_state(opt, sd):
-    """inverse of adam_state_dict: accepts the reference's optimizer state (main.py:190-198)"""
+    """inverse of adam_state_dict: accepts the reference's optimizer state (main.py:190-198) or any torch.optim.Adam / AdamW
+    state_dict built over the same groups.  Every group's lr / weight_decay is taken over; betas and eps, shared by design, from
+    the first; the coupled / decoupled choice must be the optimizer's own.  EfghError naming the mismatch when the number of
+    groups, a group's size or its decoupled choice differs."""
     flat = opt.flat
-    g = sd['param_groups'][0]
-    opt.lr, opt.betas, opt.eps, opt.wd = g['lr'], tuple(g['betas']), g['eps'], g.get('weight_decay', 0.0)
+    mine = opt.param_groups if getattr(opt, 'param_groups', None) is not None else [{'params': list(range(len(flat.params)))}]
+    theirs = sd['param_groups']
+    if len(theirs) != len(mine):
+        raise EfghError('the optimizer state has %d parameter group(s), this optimizer %d' % (len(theirs), len(mine)))
+    for k, (a, b) in enumerate(zip(theirs, mine)):
+        if len(a['params']) != len(b['params']):
+            raise EfghError('parameter group %d of the optimizer state holds %d parameters, this optimizer\'s %d'
+                            % (k, len(a['params']), len(b['params'])))
+    order = adam_numbering(opt)
+    ids = [j for a in theirs for j in a['params']]
+    grouped = getattr(opt, 'param_groups', None) is not None
+    for k, (a, b) in enumerate(zip(theirs, mine)):
+        # torch.optim.Adam's key for AdamW's decay (absent in older files: coupled); an ungrouped FusedAdam is coupled
+        saved, own = bool(a.get('decoupled_weight_decay', False)), bool(b.get('decoupled', False))
+        if saved != own and (saved or grouped):
+            raise EfghError('parameter group %d of the optimizer state has %s weight decay, this optimizer\'s group %s: build the '
+                            'optimizer with the same choice' % (k, 'decoupled (AdamW)' if saved else 'coupled (Adam)',
+                                                                 'decoupled (AdamW)' if own else 'coupled (Adam)'))
+    g = theirs[0]
+    opt.betas, opt.eps = tuple(g['betas']), g['eps']
+    if getattr(opt, 'param_groups', None) is None:
+        opt.lr, opt.wd = g['lr'], g.get('weight_decay', 0.0)
+    else:
+        for a, b in zip(theirs, mine):
+            if tuple(a['betas']) != opt.betas or a['eps'] != opt.eps:
+                raise EfghError('the optimizer state\'s groups differ in betas / eps: they are shared by all groups here')
+            b['lr'], b['weight_decay'] = float(a['lr']), float(a.get('weight_decay', 0.0))
     steps = []
-    for i, (p, (off, k)) in enumerate(zip(flat.params, flat.offsets)):
-        st = sd['state'].get(i)
+    for j, i in zip(ids, order):
+        st = sd['state'].get(j)
         if st is None:
             continue
+        off, k = flat.offsets[i]
         opt.m[off:off + k].copy_(st['exp_avg'].reshape(-1))
         opt.v[off:off + k].copy_(st['exp_avg_sq'].reshape(-1))
         steps.append(int(st['step']))

@@ -9,6 +9,13 @@
 would do with one line.  Under 'high' the 36 Winograd-domain planes of the 2-D F(4x4,3x3) layers run on the split-bf16 kernels
 (ops.planes_split_active); without the flag torch's default ('highest': exact fp32) stays.
 
+`--fused-optimizer [--max-grad-norm X] [--skip-nonfinite]` rebinds `torch.optim.Adam` and `torch.optim.AdamW` to
+`efgh_amd.optim.Adam` / `AdamW` for the duration of the run (the `--gpus N` children included): the optimizer the script builds
+(main.py:181-183) then keeps parameters and gradients in one flat buffer each, takes the layer backwards' gradients without
+autograd's per-parameter accumulation and steps with one launch - the fused step of `efgh_amd.train.Trainer` under the unmodified
+loop.  The two guard options become constructor defaults (global-norm clipping, skipping of non-finite steps, decided on the
+device).  Without the flag nothing is rebound.  The transactional step and the weight average stay Trainer-only.
+
 The reference binds its model and criterion by module name (`import nets`, `import losses`, main.py:14-15;
 `nets.__dict__[arch + 'Backbone']`, `losses.__dict__[arch + 'Criterion']`, main.py:126,129).  This launcher installs
 `efgh_amd.nets` / `efgh_amd.losses` under those two names in `sys.modules`, puts the script's directory at the front of
@@ -136,6 +143,16 @@ def _process_data_parallel_class():
             return self.module(*args, **kwargs)
 
         def _average_gradients(self, optimizer, args, kwargs):
+            from . import optim as fused_optim
+            if isinstance(optimizer, fused_optim.Adam):
+                # the gradients live in ONE flat buffer: sum it over the ranks in buckets where it is (no flattening, no copy
+                # back); the 1 / world factor is folded into the optimizer's launch
+                from . import ops
+                from .train import allreduce_mean_
+                ops.join_side_streams(optimizer.flat.g)
+                allreduce_mean_(optimizer.flat.g, self.world, self.BUCKET)
+                optimizer.grad_scale = 1.0 / self.world
+                return
             mine = {id(p) for p in self.module.parameters()}
             ps = [p for g in optimizer.param_groups for p in g['params'] if id(p) in mine and p.grad is not None]
             if not ps:
@@ -365,6 +382,56 @@ def apply_fp32_precision(precision):
         torch.set_float32_matmul_precision(precision)
 
 
+def take_optimizer_flags(argv):
+    """takes `--fused-optimizer [--max-grad-norm X] [--skip-nonfinite]` out of the launcher's own options (everything in front of
+    the script) -> ({'fused': bool, 'max_grad_norm': float | None, 'skip_nonfinite': bool}, the remaining arguments for parse())"""
+    opts = {'fused': False, 'max_grad_norm': None, 'skip_nonfinite': False}
+    rest, i = [], 0
+    while i < len(argv):
+        a = argv[i]
+        if a == '--fused-optimizer':
+            opts['fused'] = True
+        elif a == '--skip-nonfinite':
+            opts['skip_nonfinite'] = True
+        elif a == '--max-grad-norm' or a.startswith('--max-grad-norm='):
+            if '=' in a:
+                value = a.split('=', 1)[1]
+            elif i + 1 < len(argv):
+                i += 1
+                value = argv[i]
+            else:
+                raise SystemExit('efgh_amd.run: --max-grad-norm needs a value')
+            try:
+                opts['max_grad_norm'] = float(value)
+            except ValueError:
+                raise SystemExit('efgh_amd.run: --max-grad-norm %s: expected a number > 0' % value)
+            if not opts['max_grad_norm'] > 0.0:
+                raise SystemExit('efgh_amd.run: --max-grad-norm %s: expected a number > 0' % value)
+        elif a in ('--device', '--gpus', '--fp32-precision') and i + 1 < len(argv):
+            rest += argv[i:i + 2]
+            i += 1
+        elif a.startswith('-'):
+            rest.append(a)
+        else:                                      # the script: everything from here on is its own
+            rest += argv[i:]
+            break
+        i += 1
+    if (opts['max_grad_norm'] is not None or opts['skip_nonfinite']) and not opts['fused']:
+        raise SystemExit('efgh_amd.run: --max-grad-norm / --skip-nonfinite are options of --fused-optimizer')
+    return opts, rest
+
+
+def install_fused_optimizer(max_grad_norm=None, skip_nonfinite=False):
+    """`torch.optim.Adam` / `torch.optim.AdamW` are efgh_amd.optim's classes from here on (with the guard options as constructor
+    defaults) -> the two classes"""
+    import torch
+    from . import optim as fused_optim
+    adam, adamw = fused_optim.bind_defaults(max_grad_norm, skip_nonfinite)
+    torch.optim.Adam = adam
+    torch.optim.AdamW = adamw
+    return adam, adamw
+
+
 def parse(argv):
     """-> (device, pin, gpus, script, script arguments, fp32 precision or None)"""
     device, pin, gpus, precision = 0, True, 1, None
@@ -399,13 +466,14 @@ def parse(argv):
             break
     if i >= len(argv):
         raise SystemExit('usage: python -m efgh_amd.run [--gpus N | --device I | --all-devices] [--fp32-precision {highest,high}] '
-                         '<script.py> [script arguments...]')
+                         '[--fused-optimizer [--max-grad-norm X] [--skip-nonfinite]] <script.py> [script arguments...]')
     return device, pin, gpus, argv[i], argv[i + 1:], precision
 
 
 def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
-    device, pin, gpus, script, rest, precision = parse(argv)
+    optimizer, own = take_optimizer_flags(argv)
+    device, pin, gpus, script, rest, precision = parse(own)
     if not os.path.isfile(script):
         raise SystemExit('efgh_amd.run: no such script: %s' % script)
     child = os.environ.get('EFGH_RUN_CHILD') == '1' and 'RANK' in os.environ
@@ -421,12 +489,19 @@ def main(argv=None):
     install_aliases()
     install_loop_rebinds()
     apply_fp32_precision(precision)
+    stock = None
+    if optimizer['fused']:
+        import torch
+        stock = (torch.optim.Adam, torch.optim.AdamW)
+        install_fused_optimizer(optimizer['max_grad_norm'], optimizer['skip_nonfinite'])
     script = os.path.abspath(script)
     sys.argv = [script] + list(rest)
     sys.path.insert(0, os.path.dirname(script))
     try:
         runpy.run_path(script, run_name='__main__')
     finally:
+        if stock is not None:
+            torch.optim.Adam, torch.optim.AdamW = stock
         if child:
             import torch.distributed as dist
             if dist.is_initialized():

@@ -22,6 +22,32 @@ class FlatParams:
         self.frozen = tuple(bool(p.requires_grad) for p in model.parameters())      # checked by Trainer.step
         self.all_params = list(model.parameters())
         ps = [p for p in model.parameters() if p.requires_grad]
+        bns = [m for m in model.modules() if isinstance(m, torch.nn.modules.batchnorm._BatchNorm)
+               and m.num_batches_tracked is not None]
+        self._home(ps, bns)
+
+    @classmethod
+    def from_params(cls, params):
+        """the same flat buffers over a plain list of parameters, in that order (optim.Adam: there is no model, so BatchNorm's
+        counters stay in their modules and `frozen` / `all_params` describe the list alone)"""
+        ps = list(params)
+        if not ps:
+            raise _C.EfghError('FlatParams.from_params: no parameters')
+        seen = set()
+        for i, p in enumerate(ps):
+            if not torch.is_tensor(p) or p.dtype != torch.float32 or p.device != ps[0].device or not p.requires_grad \
+                    or not p.is_leaf:
+                raise _C.EfghError('FlatParams.from_params: parameter %d must be a float32 leaf tensor that requires a gradient, on '
+                                   '%s (filter frozen parameters out as main.py:178-180 does)' % (i, ps[0].device))
+            if id(p) in seen:
+                raise _C.EfghError('FlatParams.from_params: parameter %d appears twice' % i)
+            seen.add(id(p))
+        self = cls.__new__(cls)
+        self.frozen, self.all_params = tuple(True for _ in ps), list(ps)
+        self._home(ps, [])
+        return self
+
+    def _home(self, ps, bns):
         dev, n = ps[0].device, sum(p.numel() for p in ps)
         self.n = n
         self.w = torch.cat([p.data.reshape(-1).float() for p in ps])          # (one launch, not one copy per parameter)
@@ -43,8 +69,6 @@ class FlatParams:
         self.direct = True
         # BatchNorm's `num_batches_tracked` counters re-homed as views of ONE int64 vector: a training forward notes which layers
         # ran (GemmLayerFn.forward -> tick) and Trainer.step adds the whole step's counts with one launch instead of one per layer
-        bns = [m for m in model.modules() if isinstance(m, torch.nn.modules.batchnorm._BatchNorm)
-               and m.num_batches_tracked is not None]
         self.nbt = torch.stack([m.num_batches_tracked.to(dev) for m in bns]).clone() if bns else None
         self.ticks, self.collect_ticks = [0] * len(bns), False
         self._bns = bns
@@ -466,6 +490,85 @@ def name_segments(names, sizes, limit=_C.GUARD_MAX_SEGMENTS):
     return [tuple(s) for s in segs]
 
 
+def adam_segment_table(sizes, group_of, limit=_C.ADAM_MAX_SEGMENTS):
+    """segment table of efgh_adam_step_groups for parameters of `sizes` elements laid out one after the other, parameter i in group
+    group_of[i]: (ends, group ids) with adjacent parameters of one group merged and empty parameters dropped - ends strictly
+    ascending, the last one the total size"""
+    ends, gids, off = [], [], 0
+    for k, gi in zip(sizes, group_of):
+        off += int(k)
+        if k <= 0:
+            continue
+        if gids and gids[-1] == gi:
+            ends[-1] = off
+        else:
+            ends.append(off)
+            gids.append(int(gi))
+    if not ends or len(ends) > limit:
+        raise _C.EfghError('parameter groups cut the flat buffer into %d segments; 1..%d are supported (order the parameters so '
+                           'that those of one group lie together)' % (len(ends), limit))
+    return ends, gids
+
+
+def _group_name(k, group):
+    return 'group %d%s' % (k, ' (%s)' % group['name'] if isinstance(group, dict) and group.get('name') else '')
+
+
+def check_group_value(what, name, value):
+    """a group's `lr` / `weight_decay`: anything float() converts (a Python or numpy number, a one-element tensor; no bool) that is
+    finite and >= 0 -> float"""
+    try:
+        v = float(value) if not isinstance(value, bool) else None
+    except (TypeError, ValueError):
+        v = None
+    if v is None or not 0.0 <= v < float('inf'):
+        raise _C.EfghError('%s: %s must be a finite real number >= 0, got %r' % (name, what, value))
+    return v
+
+
+def normalize_adam_groups(nparams, groups, lr, weight_decay, betas, eps, decoupled=False):
+    """FusedAdam's `groups` -> (param_groups, group_of): plain dicts {'name', 'params', 'lr', 'weight_decay', 'decoupled'} with the
+    constructor's values filled in, and the group of every parameter index.  EfghError naming the group for anything refused."""
+    groups = list(groups)
+    if not 1 <= len(groups) <= _C.ADAM_MAX_GROUPS:
+        raise _C.EfghError('%d parameter groups: 1..%d are supported (group %d is one too many)'
+                           % (len(groups), _C.ADAM_MAX_GROUPS, _C.ADAM_MAX_GROUPS) if groups else 'no parameter groups')
+    group_of, out = [None] * nparams, []
+    for k, gr in enumerate(groups):
+        name = _group_name(k, gr)
+        if not isinstance(gr, dict) or 'params' not in gr:
+            raise _C.EfghError("%s: expected a dict with 'params' (indices into flat.params)" % name)
+        unknown = set(gr) - {'name', 'params', 'lr', 'weight_decay', 'decoupled', 'betas', 'eps', 'amsgrad', 'maximize'}
+        if unknown:
+            raise _C.EfghError('%s: unknown keys %s' % (name, sorted(unknown)))
+        for flag in ('amsgrad', 'maximize'):
+            if gr.get(flag):
+                raise _C.EfghError('%s: %s is not supported by the fused step' % (name, flag))
+        if 'betas' in gr and tuple(float(b) for b in gr['betas']) != tuple(float(b) for b in betas):
+            raise _C.EfghError('%s: betas %r differ from the optimizer\'s %r (betas are shared by all groups)'
+                               % (name, tuple(gr['betas']), tuple(betas)))
+        if 'eps' in gr and float(gr['eps']) != float(eps):
+            raise _C.EfghError('%s: eps %r differs from the optimizer\'s %r (eps is shared by all groups)' % (name, gr['eps'], eps))
+        idx = list(gr['params'])
+        if not idx:
+            raise _C.EfghError('%s is empty' % name)
+        for i in idx:
+            if isinstance(i, bool) or not isinstance(i, int) or not 0 <= i < nparams:
+                raise _C.EfghError('%s: %r is not an index into the %d flat parameters' % (name, i, nparams))
+            if group_of[i] is not None:
+                raise _C.EfghError('%s: parameter %d is in %s already' % (name, i, _group_name(group_of[i], groups[group_of[i]])))
+            group_of[i] = k
+        out.append({'name': gr.get('name'), 'params': idx,
+                    'lr': check_group_value('lr', name, gr.get('lr', lr)),
+                    'weight_decay': check_group_value('weight_decay', name, gr.get('weight_decay', weight_decay)),
+                    'decoupled': bool(gr.get('decoupled', decoupled))})
+    missing = [i for i, k in enumerate(group_of) if k is None]
+    if missing:
+        raise _C.EfghError('parameter %d is in no group (%d parameters are not: every parameter belongs to exactly one)'
+                           % (missing[0], len(missing)))
+    return out, group_of
+
+
 class FusedAdam:
     """torch.optim.Adam(lr, betas=(0.9,0.999), eps=1e-8, weight_decay) on a FlatParams, one HIP launch.
 
@@ -480,10 +583,27 @@ class FusedAdam:
     A guarded step is three launches (measure, decide, Adam): the norm, the clip coefficient and the skip decision stay in a
     device-resident state block, nothing is read back.  In a data-parallel run the measure pass sees the all-reduced (summed)
     gradient, which is bit-identical on every rank, so every rank takes the same decision.  `guard_stats()` reads the block.
-    With skip_nonfinite the step count `t` lives on the device too (reading `opt.t` costs one device read)."""
+    With skip_nonfinite the step count `t` lives on the device too (reading `opt.t` costs one device read).
+
+    Parameter groups (`groups=None`, the default: none of the following exists and the launches are those above):
+      groups          [{'params': [indices into flat.params], 'lr':, 'weight_decay':, 'decoupled':, 'name':}, ...], at most 16; every
+                      key besides `params` is optional and defaults to the constructor's value; every parameter is in exactly one
+                      group.  `decoupled` selects torch.optim.AdamW's decay (w *= 1 - lr * weight_decay) for the group.
+    With groups the Adam launch of `step` is efgh_adam_step_groups (one launch still; the measure, decide and resolve launches of a
+    guarded step are unchanged, and clipping is by the global norm over all groups, as clip_grad_norm_ over all parameters is).
+    `opt.param_groups` holds one plain dict per group whose `lr` / `weight_decay` are read at every step: writing
+    `param_group['lr']` between steps takes effect at the next launch, nothing is uploaded.  betas and eps are shared by all
+    groups BY DESIGN (one pair of moment buffers, one bias correction per step, one step count): a group that asks for its own is
+    refused, as are amsgrad and maximize.  The segment table (runs of consecutive parameters of one group) goes to the device once,
+    here.
+    Which bits a grouped step leaves depends on that table: every SEGMENT holds the bits of the ungrouped kernel run on it alone,
+    and that kernel rounds m and v twice (a product and a sum, not a fused multiply-add) in its last `length & 3` elements.  So
+    the last `length & 3` elements of every segment take that form, wherever the segment lies - up to 3 elements per segment may
+    differ in the last bit of m and v from an ungrouped FusedAdam over the whole buffer, which treats only ITS last `n & 3`
+    elements so.  (From zero moments the two forms coincide: b * 0 is exact.)"""
 
     def __init__(self, flat, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_grad_norm=None,
-                 skip_nonfinite=False, segments=None, txn=None):
+                 skip_nonfinite=False, segments=None, txn=None, groups=None):
         self.max_grad_norm = check_max_grad_norm(max_grad_norm)
         self.skip_nonfinite = bool(skip_nonfinite)
         if txn is not None and not self.skip_nonfinite:
@@ -495,6 +615,16 @@ class FusedAdam:
         self.v = torch.zeros_like(flat.w)
         self._t = 0
         self.segments = self.state = self.workspace = None
+        self.param_groups = None
+        if groups is not None:
+            self.param_groups, self.group_of = normalize_adam_groups(len(flat.params), groups, lr, weight_decay, betas, eps)
+            ends, gids = adam_segment_table([k for _, k in flat.offsets], self.group_of)
+            self.seg_table = (ends, gids)
+            self._seg_ends_host = (_C.c_int64 * len(ends))(*ends)
+            self._seg_gids_host = (_C.ctypes.c_uint8 * len(gids))(*gids)
+            self._seg_ends = torch.tensor(ends, dtype=torch.int64).to(flat.w.device)
+            self._seg_gids = torch.tensor(gids, dtype=torch.uint8).to(flat.w.device)
+            self._hp = _C.AdamGroups()
         if self.guarded:
             segs = [(str(a), int(b), int(c)) for a, b, c in segments] if segments is not None else [('all', 0, flat.n)]
             ends = [0] + [c for _, _, c in segs]
@@ -563,11 +693,30 @@ class FusedAdam:
             return self._step_guarded(grad_scale, g)
         self.t += 1
         f = self.flat
+        if self.param_groups is not None:
+            self._launch_groups(g, grad_scale, None)
+            ops.bump_epoch(self.flat.epoch)
+            return
         _C.check(_C.lib().efgh_adam_step(_C.ptr(f.w), _C.ptr(g), _C.ptr(self.m), _C.ptr(self.v), _C.c_int64(f.n),
                                          _C.c_float(self.lr), _C.c_float(self.betas[0]), _C.c_float(self.betas[1]),
                                          _C.c_float(self.eps), _C.c_float(self.wd), _C.c_int32(self.t),
                                          _C.c_float(grad_scale), _C.stream_ptr()))
         ops.bump_epoch(self.flat.epoch)            # packed-weight / folded-BN caches are stale now
+
+    def _launch_groups(self, g, grad_scale, state, grid=0):
+        """efgh_adam_step_groups with the groups' values as they are NOW (a host struct passed by value: no upload)"""
+        f, hp = self.flat, self._hp
+        hp.n_groups, hp.step, hp.grad_scale = len(self.param_groups), self._t, grad_scale
+        hp.beta1, hp.beta2, hp.eps = self.betas[0], self.betas[1], self.eps
+        for k, gr in enumerate(self.param_groups):
+            lr = check_group_value('lr', _group_name(k, gr), gr['lr'])
+            wd = check_group_value('weight_decay', _group_name(k, gr), gr['weight_decay'])
+            hp.lr[k], hp.weight_decay[k], hp.decoupled[k] = lr, wd, 1 if gr['decoupled'] else 0
+            hp.decay[k] = 1.0 - lr * wd             # (float64 product and difference, rounded once by the assignment)
+        _C.check(_C.lib().efgh_adam_step_groups(f.w.data_ptr(), g.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), f.n,
+                                                self._seg_ends.data_ptr(), self._seg_gids.data_ptr(), len(self._seg_ends_host),
+                                                self._seg_ends_host, self._seg_gids_host, _C.ctypes.byref(hp),
+                                                state.data_ptr() if state is not None else None, grid, _C.stream_ptr()))
 
     def _check_grad(self, grad):
         w = self.flat.w
@@ -588,9 +737,39 @@ class FusedAdam:
                                              self.workspace.data_ptr(), self.state.data_ptr(), 0, stream))
         if self.txn is not None:                   # veto / restore: after decide, before Adam reads state->skip, same stream
             self.txn.resolve(self.state, self.betas)
+        if self.param_groups is not None:
+            self._launch_groups(g, grad_scale, self.state)
+            ops.bump_epoch(self.flat.epoch)
+            return
         _C.check(lib.efgh_adam_step_guarded(f.w.data_ptr(), g.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), f.n, self.lr,
                                             self.betas[0], self.betas[1], self.eps, self.wd, self.state.data_ptr(), stream))
         ops.bump_epoch(self.flat.epoch)            # (also after a skipped step: the host does not know, a repack is harmless)
+
+
+def named_param_groups(names, specs):
+    """Trainer's `param_groups` -> FusedAdam's `groups` over the trainable parameters `names` (in flat order): parameter i joins the
+    first spec whose 'names' - a list of prefixes, one prefix, or a predicate of the name - matches; the unmatched ones form a
+    last, default group (no keys of its own).  A spec nothing matches stays in the list, empty: FusedAdam refuses it by name."""
+    specs = list(specs)
+    groups = []
+    for k, spec in enumerate(specs):
+        if not isinstance(spec, dict) or 'names' not in spec:
+            raise _C.EfghError("param_groups[%d]: expected a dict with 'names' (prefixes of state_dict names, or a predicate)" % k)
+        sel = spec['names']
+        label = getattr(sel, '__name__', 'predicate') if callable(sel) else ','.join([sel] if isinstance(sel, str) else list(sel))
+        groups.append(dict({key: v for key, v in spec.items() if key != 'names'}, name=spec.get('name', label), params=[]))
+    default = []
+    for i, name in enumerate(names):
+        for spec, group in zip(specs, groups):
+            sel = spec['names']
+            if sel(name) if callable(sel) else name.startswith((sel,) if isinstance(sel, str) else tuple(sel)):
+                group['params'].append(i)
+                break
+        else:
+            default.append(i)
+    if default:
+        groups.append({'name': 'default', 'params': default})
+    return groups
 
 
 def adjust_learning_rate(base_lr, it, every=50000, gamma=0.7):
@@ -624,10 +803,17 @@ class Trainer:
     device.  The ranks of a data-parallel run average bit-identical weights, so no collective is needed.  `ema_state_dict()` gives
     the model's state_dict with the averaged parameters (BatchNorm buffers and frozen parameters keep their live values);
     `with trainer.ema_weights():` puts the averaged weights under the model in place for validation; save_checkpoint(ema=trainer.ema)
-    / load_checkpoint carry the average."""
+    / load_checkpoint carry the average.
+
+    `param_groups` (None, the default: one set of hyper-parameters, the launches above) gives FusedAdam's parameter groups by name:
+    a list of {'names': prefixes or a predicate, 'lr':, 'weight_decay':, 'decoupled':} matched against the state_dict names of the
+    trainable parameters - a parameter joins the FIRST entry one of whose prefixes its name starts with (or whose predicate holds);
+    those no entry matches form a default group with the Trainer's own `lr` / `weight_decay`.  A lower rate on a pre-trained
+    sub-network ({'names': ['G.'], 'lr': 1e-5}) or no decay on BatchNorm and bias is one entry each.  The step schedule multiplies
+    every group's own base rate.  betas and eps are shared (see FusedAdam)."""
 
     def __init__(self, model, criterion, lr=1e-4, weight_decay=0.0, max_grad_norm=None, skip_nonfinite=False, transactional=False,
-                 ema_decay=None, ema_warmup=True):
+                 ema_decay=None, ema_warmup=True, param_groups=None):
         max_grad_norm = check_max_grad_norm(max_grad_norm)                       # (before anything is re-homed or broadcast)
         ema_decay = check_ema_decay(ema_decay)
         if transactional and not skip_nonfinite:
@@ -646,8 +832,13 @@ class Trainer:
             names = [k for k, p in model.named_parameters() if p.requires_grad]
             segments = name_segments(names, [k for _, k in self.flat.offsets])
         self.txn = BnTransaction(model, self.flat) if transactional else None     # (after the broadcast: it copies the values)
+        groups = None
+        if param_groups is not None:
+            groups = named_param_groups([k for k, p in model.named_parameters() if p.requires_grad], param_groups)
         self.opt = FusedAdam(self.flat, lr=lr, weight_decay=weight_decay, max_grad_norm=max_grad_norm,
-                             skip_nonfinite=skip_nonfinite, segments=segments, txn=self.txn)
+                             skip_nonfinite=skip_nonfinite, segments=segments, txn=self.txn, groups=groups)
+        # the step schedule multiplies every group's OWN base rate
+        self.group_base_lr = [g['lr'] for g in self.opt.param_groups] if groups is not None else None
         self.comm = OverlappedAllReduce(self.flat, self.world)
         if self.world > 1:
             ops.reserve_comm_queue()
@@ -791,6 +982,9 @@ class Trainer:
         self._not_in_ema_scope(what)
         self._check_frozen()
         self.opt.lr = adjust_learning_rate(self.base_lr, self.it)
+        if self.group_base_lr is not None:
+            for group, base in zip(self.opt.param_groups, self.group_base_lr):
+                group['lr'] = adjust_learning_rate(base, self.it)
         self.model.train()
         weights = self.depth_weights(depth_weights_of) if depth_weights_of is not None else None
         if self.txn is not None:

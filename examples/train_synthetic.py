@@ -6,6 +6,7 @@ loop of the reference's iterater.py:25-60 with nothing on the CPU between the de
     python examples/train_synthetic.py --iters 3 --batch 4 --accumulate 2        # gradient accumulation over micro-batches
     python examples/train_synthetic.py --iters 3 --transactional                 # a skipped step also restores BatchNorm's state
     python examples/train_synthetic.py --iters 5 --ema 0.999                     # validate the live and the averaged weights
+    python examples/train_synthetic.py --iters 3 --groups                        # parameter groups: G at a tenth of the rate, no decay on 1-D parameters
 """
 import argparse
 import os
@@ -58,6 +59,9 @@ def main(argv=None):
     ap.add_argument('--ema', type=float, default=None, metavar='DECAY',
                     help='keep an exponential moving average of the weights inside the fused step and run the error meter on the last '
                          'batch once with the live and once with the averaged weights')
+    ap.add_argument('--groups', action='store_true',
+                    help='parameter groups inside the fused step: the ResNet branch G at a tenth of the learning rate, weight '
+                         'decay on the rest except BatchNorm weights and biases')
     a = ap.parse_args(argv)
     a.skip_nonfinite = a.skip_nonfinite or a.transactional
     raw = tuple(a.raw)
@@ -66,8 +70,16 @@ def main(argv=None):
                  'dclb': {'l_rot_range': 1 / 12., 'l_trs_range': 1.0, 'c_rot_range': 1 / 12.}})
     torch.manual_seed(0)
     model = EFGHBackbone(args).cuda()
-    trainer = Trainer(model, EFGHCriterion(args), lr=1e-4, max_grad_norm=a.max_grad_norm, skip_nonfinite=a.skip_nonfinite,
-                      transactional=a.transactional, ema_decay=a.ema)
+    groups = None
+    if a.groups:                                             # first match wins; what nothing matches is the default group
+        one_d = {k for k, p in model.named_parameters() if p.dim() <= 1}
+        groups = [{'names': ['G.'], 'lr': 1e-5, 'name': 'G'},
+                  {'names': lambda k: k in one_d, 'weight_decay': 0.0, 'name': 'bn_and_bias'}]
+    trainer = Trainer(model, EFGHCriterion(args), lr=1e-4, weight_decay=1e-2 if a.groups else 0.0, max_grad_norm=a.max_grad_norm,
+                      skip_nonfinite=a.skip_nonfinite, transactional=a.transactional, ema_decay=a.ema, param_groups=groups)
+    if a.groups:
+        print('parameter groups:', ', '.join('%s: %d parameters, lr %g, weight_decay %g' % (g['name'], len(g['params']), g['lr'], g['weight_decay'])
+                                             for g in trainer.opt.param_groups))
     prep = ProcessKITTIODOM(args)
     err = Err(args['dataset'])
     calib0, _ = syn.calib_and_A(raw)

@@ -61,7 +61,8 @@ const char *efgh_last_error(void);
  *      efgh_grad_drain, efgh_gimg_valid_count (gradient accumulation over micro-batches);
  *      efgh_txn_snapshot, efgh_txn_probe, efgh_txn_resolve and the struct efgh_txn_state (BatchNorm running statistics and counters
  *      rolled back when the guarded step is skipped; a non-finite forward skips it);
- *      efgh_ema_update, efgh_ema_swap (exponential moving average of the flat weights). */
+ *      efgh_ema_update, efgh_ema_swap (exponential moving average of the flat weights);
+ *      efgh_adam_step_groups and the struct efgh_adam_groups (the fused optimizer step with torch.optim's parameter groups). */
 #define EFGH_ABI_VERSION 4
 int efgh_version(void);
 
@@ -662,6 +663,45 @@ int efgh_grad_guard_measure(const float *g, int64_t n, const int64_t *bounds, in
  * efgh_adam_step(step = applied, grad_scale).  w, g, m, v 16-byte aligned as there. */
 int efgh_adam_step_guarded(float *w, const float *g, float *m, float *v, int64_t n, float lr, float beta1, float beta2,
                            float eps, float weight_decay, const efgh_guard_state *state, void *stream);
+
+/* ---- fused Adam with parameter groups (torch.optim's param_groups): efgh_adam_step / efgh_adam_step_guarded in ONE launch over the
+ * flat buffers w, g, m, v of n elements, where every element takes the learning rate, the weight decay and the coupled / decoupled
+ * choice of its group.  beta1, beta2, eps, the step count and grad_scale are shared by all groups.
+ *
+ * Segment table: nseg (1 <= nseg <= EFGH_ADAM_MAX_SEGMENTS) segments cut [0, n) without gaps; seg_ends[s] is the (exclusive) end of
+ * segment s - strictly ascending, seg_ends[nseg - 1] = n - and seg_group[s] < n_groups its group.  Adjacent segments of one group
+ * are merged by the caller.  seg_ends / seg_group are DEVICE arrays (uploaded once, 8-byte aligned ends) read by the kernel;
+ * host_ends / host_group are HOST copies of the same table, checked during the call (device memory is never read back).
+ *
+ * *groups is a HOST struct copied into the kernel arguments by value: no copy to the device and no synchronisation per step, and a
+ * learning rate written between two calls takes effect at the next launch.  Per element, with its group's values:
+ *   coupled    (decoupled[k] == 0)  efgh_adam_step's expressions with lr[k], weight_decay[k]: a segment holds the bits that
+ *              efgh_adam_step (state == NULL) or efgh_adam_step_guarded (state given) leaves when run on that segment alone
+ *   decoupled  (AdamW)  w = w * decay[k], one fp32 product, decay[k] = (float)(1.0 - (double)lr[k] * (double)weight_decay[k]) formed
+ *              by the caller (torch.optim.AdamW's param.mul_(1 - lr * weight_decay)), then the coupled expressions with weight_decay 0
+ * state == NULL: unguarded; the bias corrections of step `groups->step` >= 1 are computed on the host exactly as efgh_adam_step
+ * computes them and g is multiplied by groups->grad_scale.  Otherwise *state is the block efgh_grad_guard_measure (and
+ * efgh_txn_resolve) left on the same stream: skip, scale, bc1 and bc2_sqrt are read from it as efgh_adam_step_guarded reads them
+ * (step and grad_scale of *groups are ignored) and a set skip leaves w, m and v untouched.
+ * grid: workgroups of the launch, 0 = that of efgh_adam_step (the result does not depend on it).
+ * w, g, m, v 16-byte aligned.  A table that is not ascending, does not end at n or names a group >= n_groups, n_groups outside
+ * [1, EFGH_ADAM_MAX_GROUPS], a negative or non-finite lr / weight_decay: EFGH_E_INVALID, nothing is launched. */
+#define EFGH_ADAM_MAX_GROUPS 16
+#define EFGH_ADAM_MAX_SEGMENTS 4096
+typedef struct efgh_adam_groups {
+    int32_t n_groups;
+    int32_t step;                               /* Adam's step count of this call (unguarded form only) */
+    float beta1, beta2, eps;
+    float grad_scale;                           /* unguarded form only; the guarded form reads state->scale */
+    float lr[EFGH_ADAM_MAX_GROUPS];
+    float weight_decay[EFGH_ADAM_MAX_GROUPS];
+    float decay[EFGH_ADAM_MAX_GROUPS];          /* decoupled groups: (float)(1.0 - (double)lr * (double)weight_decay) */
+    int32_t decoupled[EFGH_ADAM_MAX_GROUPS];
+} efgh_adam_groups;
+int efgh_adam_step_groups(float *w, const float *g, float *m, float *v, int64_t n, const int64_t *seg_ends,
+                          const uint8_t *seg_group, int32_t nseg, const int64_t *host_ends, const uint8_t *host_group,
+                          const efgh_adam_groups *groups, const efgh_guard_state *state /* may be NULL */, int32_t grid,
+                          void *stream);
 
 /* ---- gradient accumulation over micro-batches: a second flat buffer `acc` that the flat gradient g is DRAINED into after every
  * micro-batch's backward; the optimizer entry points above then read acc instead of g (they take the gradient pointer) with
