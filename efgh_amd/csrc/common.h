@@ -1,6 +1,7 @@
 // Shared host-side helpers for libefgh_hip.so (gfx950 only).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <math.h>
 #include <stdint.h>
 #include <stdlib.h>
 #include <stdio.h>
@@ -30,6 +31,13 @@ void efgh_set_error(const char *fmt, ...);
     } while (0)
 
 static inline int cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
+
+// Adam's bias corrections of a step count the HOST knows (adam.hip's entry points, and guard.hip's when no step can be skipped; a
+// count that lives on the device is corrected there, by k_guard_decide): fp32 throughout
+struct efgh_bias_corr { float bc1, bc2_sqrt; };         // 1 - beta1^step, sqrt(1 - beta2^step)
+static inline efgh_bias_corr efgh_bias_corrections(float beta1, float beta2, int step) {
+    return {1.f - powf(beta1, (float)step), sqrtf(1.f - powf(beta2, (float)step))};
+}
 
 // activation of the fused epilogues: v for v > 0, neg * v otherwise (neg = 1: none, 0: ReLU, slope: LeakyReLU) as one compare, one
 // fma and one select - no branch.  A NaN stays a NaN under every activation (the max / min form max(v,0) + neg * min(v,0) returns

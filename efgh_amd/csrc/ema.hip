@@ -3,7 +3,7 @@
 //                 the skip decision come from the guard's state block when there is one, so a skipped step leaves the average alone
 //                 and the warm-up counts applied steps only - without a host read.
 //   k_ema_swap    exchanges two flat buffers by bits (16n bytes): the averaged weights go under the model, and back.
-// Launch shape of k_adam (elementwise.hip): 256 threads, float4 grid-stride, at most 16384 workgroups, the n & 3 tail by workgroup 0.
+// Launch shape of k_adam_flat (adam.hip): 256 threads, float4 grid-stride, at most 16384 workgroups, the n & 3 tail by workgroup 0.
 // No atomics, no workspace, nothing outside [0, n) is touched.
 #include <math.h>
 

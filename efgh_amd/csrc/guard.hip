@@ -1,12 +1,10 @@
 // Gradient guard of the fused training step: global-norm clipping (torch.nn.utils.clip_grad_norm_, norm_type 2) and skipping of
-// non-finite steps, decided on the device.  Three launches, no host read, no atomics:
+// non-finite steps, decided on the device.  Three launches, no host read, no atomics - the first two are here:
 //   k_guard_measure  one pass over the flat gradient (HBM-bound, 4n bytes): float64 sum of squares and an exact count of inf / NaN
 //                    elements per run of EFGH_GUARD_RUN elements, one workgroup per run, fixed tree
 //   k_guard_decide   one workgroup folds the runs per segment (fixed tree) and writes the state block: norms, clip coefficient,
 //                    skip flag, step counters, Adam's bias corrections
-//   k_adam_guarded   k_adam (elementwise.hip) with scale, bias corrections and skip flag read from the state block
-#include <math.h>
-
+//   k_adam_flat<true>  Adam (adam.hip) with scale, bias corrections and skip flag read from the state block
 #include "common.h"
 
 namespace {
@@ -137,38 +135,6 @@ k_guard_decide(const double *__restrict__ part, const int *__restrict__ cnt, Gua
     st->skip = skip; st->nseg = sg.nseg;
 }
 
-// k_adam of elementwise.hip, expression for expression; gscale / bc1 / bc2_sqrt come from the state block
-__global__ void __launch_bounds__(256)
-k_adam_guarded(float *__restrict__ w, const float *__restrict__ g, float *__restrict__ m, float *__restrict__ v,
-               long long n, float lr, float b1, float b2, float eps, float wd, const efgh_guard_state *__restrict__ st) {
-    if (st->skip) return;
-    const float bc1 = st->bc1, bc2_sqrt = st->bc2_sqrt, gscale = st->scale;
-    long long n4 = n >> 2;
-    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long long)gridDim.x * 256) {
-        float4 ww = reinterpret_cast<float4 *>(w)[i], gg = reinterpret_cast<const float4 *>(g)[i];
-        float4 mm = reinterpret_cast<float4 *>(m)[i], vv = reinterpret_cast<float4 *>(v)[i];
-        float *wp = &ww.x, *gp = &gg.x, *mp = &mm.x, *vp = &vv.x;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            float gr = gp[q] * gscale + wd * wp[q];
-            mp[q] = b1 * mp[q] + (1.f - b1) * gr;
-            vp[q] = b2 * vp[q] + (1.f - b2) * gr * gr;
-            float denom = sqrtf(vp[q]) / bc2_sqrt + eps;
-            wp[q] -= (lr / bc1) * (mp[q] / denom);
-        }
-        reinterpret_cast<float4 *>(w)[i] = ww;
-        reinterpret_cast<float4 *>(m)[i] = mm;
-        reinterpret_cast<float4 *>(v)[i] = vv;
-    }
-    if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
-        long long i = (n4 << 2) + threadIdx.x;
-        float gr = g[i] * gscale + wd * w[i];
-        m[i] = b1 * m[i] + (1.f - b1) * gr;
-        v[i] = b2 * v[i] + (1.f - b2) * gr * gr;
-        w[i] -= (lr / bc1) * (m[i] / (sqrtf(v[i]) / bc2_sqrt + eps));
-    }
-}
-
 long long max_runs(long long n) { return n / RUN + EFGH_GUARD_MAX_SEGMENTS; }      // sum of ceil(len_s / RUN) over <= 8 segments
 }  // namespace
 
@@ -198,27 +164,12 @@ extern "C" int efgh_grad_guard_measure(const float *g, int64_t n, const int64_t 
     double *part = (double *)workspace;
     int *cnt = (int *)(part + max_runs(n));
     const long long blocks = grid > 0 ? grid : (total_runs > 16384 ? 16384 : total_runs);
-    float bc1 = 0.f, bc2_sqrt = 0.f;
-    if (!skip_nonfinite) {                          // as efgh_adam_step computes them
-        bc1 = 1.f - powf(beta1, (float)step);
-        bc2_sqrt = sqrtf(1.f - powf(beta2, (float)step));
-    }
+    efgh_bias_corr bc = {0.f, 0.f};
+    if (!skip_nonfinite) bc = efgh_bias_corrections(beta1, beta2, step);
     k_guard_measure<<<(int)blocks, GTPB, 0, (hipStream_t)stream>>>(g, sg, total_runs, part, cnt);
     EFGH_CHECK_LAUNCH();
     k_guard_decide<<<1, GTPB, 0, (hipStream_t)stream>>>(part, cnt, sg, state, max_norm, grad_scale, skip_nonfinite ? 1 : 0, beta1,
-                                                        beta2, step, bc1, bc2_sqrt);
-    EFGH_CHECK_LAUNCH();
-    return EFGH_OK;
-}
-
-extern "C" int efgh_adam_step_guarded(float *w, const float *g, float *m, float *v, int64_t n, float lr, float beta1,
-                                      float beta2, float eps, float weight_decay, const efgh_guard_state *state,
-                                      void *stream) {
-    EFGH_CHECK_ARG(w && g && m && v && state && n > 0);
-    EFGH_CHECK_ARG(((((uintptr_t)w) | ((uintptr_t)g) | ((uintptr_t)m) | ((uintptr_t)v)) & 15) == 0 && (((uintptr_t)state) & 7) == 0);
-    long long blocks = (n / 4 + 1 + 255) / 256;     // the grid of efgh_adam_step
-    blocks = blocks > 16384 ? 16384 : (blocks < 1 ? 1 : blocks);
-    k_adam_guarded<<<(int)blocks, 256, 0, (hipStream_t)stream>>>(w, g, m, v, n, lr, beta1, beta2, eps, weight_decay, state);
+                                                        beta2, step, bc.bc1, bc.bc2_sqrt);
     EFGH_CHECK_LAUNCH();
     return EFGH_OK;
 }

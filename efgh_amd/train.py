@@ -596,11 +596,10 @@ class FusedAdam:
     groups BY DESIGN (one pair of moment buffers, one bias correction per step, one step count): a group that asks for its own is
     refused, as are amsgrad and maximize.  The segment table (runs of consecutive parameters of one group) goes to the device once,
     here.
-    Which bits a grouped step leaves depends on that table: every SEGMENT holds the bits of the ungrouped kernel run on it alone,
-    and that kernel rounds m and v twice (a product and a sum, not a fused multiply-add) in its last `length & 3` elements.  So
-    the last `length & 3` elements of every segment take that form, wherever the segment lies - up to 3 elements per segment may
-    differ in the last bit of m and v from an ungrouped FusedAdam over the whole buffer, which treats only ITS last `n & 3`
-    elements so.  (From zero moments the two forms coincide: b * 0 is exact.)"""
+    All three launches share one written-out update (csrc/adam.hip), which rounds m and v twice (a product and a sum, not a fused
+    multiply-add) in the last `length & 3` elements of a buffer - and, with groups, of every segment: up to 3 elements per segment
+    may differ in the last bit of m and v from an ungrouped FusedAdam over the whole buffer.  (From zero moments the two forms
+    coincide: b * 0 is exact.)"""
 
     def __init__(self, flat, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_grad_norm=None,
                  skip_nonfinite=False, segments=None, txn=None, groups=None):
@@ -692,16 +691,23 @@ class FusedAdam:
         if self.guarded:
             return self._step_guarded(grad_scale, g)
         self.t += 1
-        f = self.flat
+        self._launch_adam(g, grad_scale, None)
+
+    def _launch_adam(self, g, grad_scale, state):
+        """the step's one Adam launch - grouped, guarded (`state`: the guard's block) or plain - and what follows every one of them"""
+        f, lib = self.flat, _C.lib()
         if self.param_groups is not None:
-            self._launch_groups(g, grad_scale, None)
-            ops.bump_epoch(self.flat.epoch)
-            return
-        _C.check(_C.lib().efgh_adam_step(_C.ptr(f.w), _C.ptr(g), _C.ptr(self.m), _C.ptr(self.v), _C.c_int64(f.n),
-                                         _C.c_float(self.lr), _C.c_float(self.betas[0]), _C.c_float(self.betas[1]),
-                                         _C.c_float(self.eps), _C.c_float(self.wd), _C.c_int32(self.t),
-                                         _C.c_float(grad_scale), _C.stream_ptr()))
-        ops.bump_epoch(self.flat.epoch)            # packed-weight / folded-BN caches are stale now
+            self._launch_groups(g, grad_scale, state)
+        elif state is not None:
+            _C.check(lib.efgh_adam_step_guarded(f.w.data_ptr(), g.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), f.n, self.lr,
+                                                self.betas[0], self.betas[1], self.eps, self.wd, state.data_ptr(), _C.stream_ptr()))
+        else:
+            _C.check(lib.efgh_adam_step(_C.ptr(f.w), _C.ptr(g), _C.ptr(self.m), _C.ptr(self.v), _C.c_int64(f.n),
+                                        _C.c_float(self.lr), _C.c_float(self.betas[0]), _C.c_float(self.betas[1]),
+                                        _C.c_float(self.eps), _C.c_float(self.wd), _C.c_int32(self.t),
+                                        _C.c_float(grad_scale), _C.stream_ptr()))
+        # packed-weight / folded-BN caches are stale now (also after a skipped step: the host does not know, a repack is harmless)
+        ops.bump_epoch(f.epoch)
 
     def _launch_groups(self, g, grad_scale, state, grid=0):
         """efgh_adam_step_groups with the groups' values as they are NOW (a host struct passed by value: no upload)"""
@@ -737,13 +743,7 @@ class FusedAdam:
                                              self.workspace.data_ptr(), self.state.data_ptr(), 0, stream))
         if self.txn is not None:                   # veto / restore: after decide, before Adam reads state->skip, same stream
             self.txn.resolve(self.state, self.betas)
-        if self.param_groups is not None:
-            self._launch_groups(g, grad_scale, self.state)
-            ops.bump_epoch(self.flat.epoch)
-            return
-        _C.check(lib.efgh_adam_step_guarded(f.w.data_ptr(), g.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), f.n, self.lr,
-                                            self.betas[0], self.betas[1], self.eps, self.wd, self.state.data_ptr(), stream))
-        ops.bump_epoch(self.flat.epoch)            # (also after a skipped step: the host does not know, a repack is harmless)
+        self._launch_adam(g, grad_scale, self.state)
 
 
 def named_param_groups(names, specs):

@@ -608,7 +608,14 @@ int efgh_corr_unpad(const float *drp, int32_t B, int32_t h, int32_t w, int32_t C
 
 /* fused Adam over ONE flat fp32 buffer holding all 47.8 M parameters (replaces the 353 per-tensor
  * updates of torch.optim.Adam, main.py:181-183; lr schedule of common/helper.py:28-38 is the
- * caller's).  g is multiplied by grad_scale first (1/world for a summed all-reduce).          */
+ * caller's).  g is multiplied by grad_scale first (1/world for a summed all-reduce).
+ * THE UPDATE, shared by efgh_adam_step, efgh_adam_step_guarded and efgh_adam_step_groups (written out once, csrc/adam.hip; fp32,
+ * every operation rounded where it stands, fma = fused), with bc1 = 1 - beta1^step, bc2_sqrt = sqrt(1 - beta2^step):
+ *   gr = fma(g, grad_scale, weight_decay * w)
+ *   m  = fma(beta1, m, (1 - beta1) * gr)      v = fma(beta2, v, ((1 - beta2) * gr) * gr)         all but the last n & 3 elements
+ *   m  = beta1 * m + (1 - beta1) * gr         v = beta2 * v + ((1 - beta2) * gr) * gr            the last n & 3 elements
+ *   w  = fma(-(lr / bc1), m / (sqrt(v) / bc2_sqrt + eps), w)
+ * w, g, m, v 16-byte aligned, n > 0, step >= 1.                                                */
 int efgh_adam_step(float *w, const float *g, float *m, float *v, int64_t n, float lr, float beta1,
                    float beta2, float eps, float weight_decay, int32_t step, float grad_scale, void *stream);
 
@@ -657,9 +664,9 @@ int64_t efgh_grad_guard_workspace(int64_t n);
 int efgh_grad_guard_measure(const float *g, int64_t n, const int64_t *bounds, int32_t nseg, double max_norm, float grad_scale,
                             int32_t skip_nonfinite, float beta1, float beta2, int32_t step, void *workspace,
                             efgh_guard_state *state, int32_t grid, void *stream);
-/* efgh_adam_step (torch.optim.Adam.step over all parameters) with the gradient scale, the bias corrections and the skip flag read from
- * *state (device memory, written by efgh_grad_guard_measure earlier on the same stream) instead of passed by value.  With
- * state->skip set nothing is written (the `optimizer.step()` that was not called).  With coef == 1 the result has the bits of
+/* efgh_adam_step's update (the same kernel) with the gradient scale, the bias corrections and the skip flag read from *state (device
+ * memory, written by efgh_grad_guard_measure earlier on the same stream) instead of passed by value.  With state->skip set nothing
+ * is written (the `optimizer.step()` that was not called).  With coef == 1 the result has the bits of
  * efgh_adam_step(step = applied, grad_scale).  w, g, m, v 16-byte aligned as there. */
 int efgh_adam_step_guarded(float *w, const float *g, float *m, float *v, int64_t n, float lr, float beta1, float beta2,
                            float eps, float weight_decay, const efgh_guard_state *state, void *stream);
@@ -675,10 +682,11 @@ int efgh_adam_step_guarded(float *w, const float *g, float *m, float *v, int64_t
  *
  * *groups is a HOST struct copied into the kernel arguments by value: no copy to the device and no synchronisation per step, and a
  * learning rate written between two calls takes effect at the next launch.  Per element, with its group's values:
- *   coupled    (decoupled[k] == 0)  efgh_adam_step's expressions with lr[k], weight_decay[k]: a segment holds the bits that
- *              efgh_adam_step (state == NULL) or efgh_adam_step_guarded (state given) leaves when run on that segment alone
+ *   coupled    (decoupled[k] == 0)  efgh_adam_step's update with lr[k], weight_decay[k]; all three entry points share its one
+ *              written-out form, and the last (length & 3) elements of every SEGMENT take its second form, so a segment holds the
+ *              bits that efgh_adam_step (state == NULL) or efgh_adam_step_guarded (state given) leaves when run on that segment alone
  *   decoupled  (AdamW)  w = w * decay[k], one fp32 product, decay[k] = (float)(1.0 - (double)lr[k] * (double)weight_decay[k]) formed
- *              by the caller (torch.optim.AdamW's param.mul_(1 - lr * weight_decay)), then the coupled expressions with weight_decay 0
+ *              by the caller (torch.optim.AdamW's param.mul_(1 - lr * weight_decay)), then the coupled update with weight_decay 0
  * state == NULL: unguarded; the bias corrections of step `groups->step` >= 1 are computed on the host exactly as efgh_adam_step
  * computes them and g is multiplied by groups->grad_scale.  Otherwise *state is the block efgh_grad_guard_measure (and
  * efgh_txn_resolve) left on the same stream: skip, scale, bc1 and bc2_sqrt are read from it as efgh_adam_step_guarded reads them

@@ -1,7 +1,8 @@
 """efgh_adam_step_groups through the C-ABI.  The yardstick is the library's own ungrouped kernels, bit for bit: for any segment
 table the launch must leave in every segment exactly the bits that efgh_adam_step (or efgh_adam_step_guarded reading the same
 state block) leaves when run on fresh 16-byte-aligned copies of that segment alone with its group's lr / weight_decay; a decoupled
-group is `w.mul_(decay)` by torch in fp32 followed by that kernel with weight_decay = 0."""
+group is `w.mul_(decay)` by torch in fp32 followed by that kernel with weight_decay = 0.  (Both sides share one written-out update,
+csrc/adam.hip; what anchors it is tests/test_gpu_adam_bits.py.)"""
 import ctypes
 import os
 import sys

@@ -98,7 +98,7 @@ def kernel_section(rounds, reps, lines):
                         'OUTSIDE the spread by %.2f %% (same bytes, same arithmetic on a sweep that lies inside one segment; what the '
                         'grouped kernel adds is a prologue that stages the 16 groups\' values in LDS behind a barrier and, per '
                         '1024-element sweep, uniform loads of the segment\'s ends and group id and the LDS reads of its values ahead '
-                        'of the arithmetic.  Not occupancy: forced to k_adam\'s 8 waves per SIMD it measured the same)'
+                        'of the arithmetic.  Not occupancy: forced to the flat kernel\'s 8 waves per SIMD it measured the same)'
                         % (100.0 * (ratio - (hi if ratio > hi else lo)))))
 
 

@@ -8,7 +8,7 @@
 
     python tools/bench_grad_accum.py [--out profiles/grad_accum.txt]
 
-Bytes: the drain moves 12 n with `first` (read g; write acc, g) and 16 n otherwise; k_adam moves 28 n."""
+Bytes: the drain moves 12 n with `first` (read g; write acc, g) and 16 n otherwise; k_adam_flat moves 28 n."""
 import statistics
 import time
 

@@ -5,7 +5,7 @@ gradient is read from HBM and not from the 256-MB last-level cache it would othe
 
     python tools/bench_grad_guard.py [--out profiles/grad_guard.txt]
 
-Bytes: k_adam moves 28 n (reads w, g, m, v; writes w, m, v), the measure pass reads 4 n."""
+Bytes: k_adam_flat moves 28 n (reads w, g, m, v; writes w, m, v), the measure pass reads 4 n."""
 import argparse
 import ctypes
 import json
