@@ -182,6 +182,181 @@ __global__ void k_gather_transform(const float *__restrict__ pcd, const int *__r
     }
 }
 
+// ---- sweep SET: K packed float32 sweeps, each with its own float64 [3][4] transform into the frame of sweep 0 --------
+// (get_accumulated_pc / search_for_accumulation, kitti_odom_loader.py:160-225, rellis3d_loader.py:218-280;
+// accumulate_lidar_points / lidar_frame_accumulation, nusc_loader.py:83-146).  The accumulated float64 cloud is never
+// written: the point kernels index the concatenation 0 .. n_total-1 and compute q = M_k . (p, 1) where they need it.
+constexpr int SWEEPS_MAX = 64;
+
+struct SweepSet {
+    const float *pts;          // packed rows, `stride` (3 or 4) floats each
+    const int *off;            // [K+1] first row of each sweep, off[K] = n_total
+    const double *M;           // [K][3][4]
+    const int *ident;          // [K] != 0: the sweep passes through untouched (q = (double)p, no arithmetic)
+    int K, stride, n_total;
+};
+
+// offsets -> LDS (one block-wide load; the caller synchronises)
+__device__ __forceinline__ void stage_offsets(const SweepSet &s, int *lds_off) {
+    for (int k = threadIdx.x; k <= s.K; k += TPB) lds_off[k] = s.off[k];
+}
+
+// the sweep k with off[k] <= i < off[k+1] (empty sweeps have off[k] == off[k+1] and are never returned)
+__device__ __forceinline__ int sweep_of(const int *lds_off, int K, int i) {
+    int lo = 0, hi = K;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (lds_off[mid] <= i) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
+struct Raw3 { float x, y, z; };
+
+__device__ __forceinline__ Raw3 load_raw(const SweepSet &s, int i) {
+    if (s.stride == 4) {
+        const float4 v = *reinterpret_cast<const float4 *>(s.pts + 4LL * i);
+        return {v.x, v.y, v.z};
+    }
+    const float *p = s.pts + 3LL * i;
+    return {p[0], p[1], p[2]};
+}
+
+// q = M_k . (p, 1) in float64, the four terms summed left to right (numpy's product goes through BLAS, which fixes neither
+// the order nor the use of FMA: tests/sweeps_contract.py carries the bound that covers every evaluation)
+__device__ __forceinline__ void sweep_position(const SweepSet &s, int k, const Raw3 &p, double q[3]) {
+    const double x = (double)p.x, y = (double)p.y, z = (double)p.z;
+    if (s.ident[k]) { q[0] = x; q[1] = y; q[2] = z; return; }
+    const double *m = s.M + 12 * k;
+#pragma unroll
+    for (int r = 0; r < 3; ++r) q[r] = ((m[r * 4] * x + m[r * 4 + 1] * y) + m[r * 4 + 2] * z) + m[r * 4 + 3];
+}
+
+struct SweepPred {
+    double radius, sxy;        // radius <= 0: no radius test; sxy = -1: RELLIS sign flip of x and y before it
+    float ego_x, ego_y;        // ego_x <= 0: no ego box
+};
+
+// not strictly inside the ego box (float32 compare on the RAW point, nusc_loader.py:88-93), and inside the half-open
+// radius box (float64 compare on the transformed position, loader_utils.py:182-187)
+__device__ __forceinline__ bool keep_sweep_point(const SweepSet &s, const SweepPred &f, const int *lds_off, int i) {
+    if (i < 0 || i >= s.n_total) return false;
+    const Raw3 p = load_raw(s, i);
+    if (f.ego_x > 0.f) {
+        const bool inside = (p.x < f.ego_x && p.x > -f.ego_x) && (p.y < f.ego_y && p.y > -f.ego_y);
+        if (inside) return false;
+    }
+    if (f.radius > 0.) {
+        double q[3];
+        sweep_position(s, sweep_of(lds_off, s.K, i), p, q);
+        const double x = q[0] * f.sxy, y = q[1] * f.sxy;
+        return x >= -f.radius && x < f.radius && y >= -f.radius && y < f.radius;
+    }
+    return true;
+}
+
+__global__ void k_sweeps_flag_count(SweepSet s, SweepPred f, const int *__restrict__ pre, int n,
+                                    int *__restrict__ block_count) {
+    __shared__ int lds_off[SWEEPS_MAX + 1];
+    __shared__ int wave_cnt[TPB / 64];
+    stage_offsets(s, lds_off);
+    __syncthreads();
+    const int i = blockIdx.x * TPB + threadIdx.x;
+    const bool k = i < n && keep_sweep_point(s, f, lds_off, pre ? pre[i] : i);
+    const unsigned long long m = __ballot(k);
+    if ((threadIdx.x & 63) == 0) wave_cnt[threadIdx.x >> 6] = __popcll(m);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int c = 0;
+        for (int q = 0; q < TPB / 64; ++q) c += wave_cnt[q];
+        block_count[blockIdx.x] = c;
+    }
+}
+
+__global__ void k_sweeps_compact(SweepSet s, SweepPred f, const int *__restrict__ pre, int n,
+                                 const int *__restrict__ block_off, int *__restrict__ keep_idx) {
+    __shared__ int lds_off[SWEEPS_MAX + 1];
+    __shared__ int wave_cnt[TPB / 64];
+    stage_offsets(s, lds_off);
+    __syncthreads();
+    const int i = blockIdx.x * TPB + threadIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int src = i < n ? (pre ? pre[i] : i) : 0;
+    const bool k = i < n && keep_sweep_point(s, f, lds_off, src);
+    const unsigned long long m = __ballot(k);
+    if (lane == 0) wave_cnt[wave] = __popcll(m);
+    __syncthreads();
+    int o = block_off[blockIdx.x];
+    for (int q = 0; q < wave; ++q) o += wave_cnt[q];
+    if (k) keep_idx[o + __popcll(m & ((1ull << lane) - 1ull))] = src;      // o + rank < the kept total <= n
+}
+
+// k_gather_transform reading q of the concatenated index keep_idx[sel[j]] instead of a float32 row
+__global__ void k_sweeps_gather_transform(SweepSet s, const int *__restrict__ keep_idx, const int *__restrict__ sel,
+                                          int n_keep, int n_sel, double sxy, const double *__restrict__ T,
+                                          int num_points, float *__restrict__ out32, double *__restrict__ out64) {
+    __shared__ int lds_off[SWEEPS_MAX + 1];
+    stage_offsets(s, lds_off);
+    __syncthreads();
+    const int j = blockIdx.x * TPB + threadIdx.x;
+    if (j >= num_points) return;
+    double x = 0., y = 0., z = 0.;
+    if (j < n_sel) {
+        const int k = sel ? sel[j] : j;
+        const int i = k >= 0 && k < n_keep ? keep_idx[k] : -1;
+        if (i >= 0 && i < s.n_total) {
+            double q[3];
+            sweep_position(s, sweep_of(lds_off, s.K, i), load_raw(s, i), q);
+            x = q[0] * sxy; y = q[1] * sxy; z = q[2];
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+        const double v = ((T[r * 4] * x + T[r * 4 + 1] * y) + T[r * 4 + 2] * z) + T[r * 4 + 3] * 1.0;
+        if (out32) out32[(long long)r * num_points + j] = (float)v;
+        if (out64) out64[(long long)r * num_points + j] = v;
+    }
+}
+
+// the accumulated cloud itself, for the callers that want what get_accumulated_pc returns: out[j] = q of keep_idx[j]
+__global__ void k_sweeps_materialize(SweepSet s, const int *__restrict__ keep_idx, int n, double *__restrict__ out) {
+    __shared__ int lds_off[SWEEPS_MAX + 1];
+    stage_offsets(s, lds_off);
+    __syncthreads();
+    const int j = blockIdx.x * TPB + threadIdx.x;
+    if (j >= n) return;
+    const int i = keep_idx ? keep_idx[j] : j;
+    double q[3] = {0., 0., 0.};
+    if (i >= 0 && i < s.n_total) sweep_position(s, sweep_of(lds_off, s.K, i), load_raw(s, i), q);
+    double *d = out + 3LL * j;
+    d[0] = q[0]; d[1] = q[1]; d[2] = q[2];
+}
+
+// the shared argument contract of the three efgh_prep_sweeps_* entry points; 0 or EFGH_E_INVALID with a message
+int sweeps_check(const float *pts, int32_t stride, const int32_t *off, const double *M, const int32_t *ident, int32_t K,
+                 int32_t n_total) {
+    if (!pts || !off || !M || !ident) {
+        efgh_set_error("sweep set: null points, offsets, transforms or identity flags");
+        return EFGH_E_INVALID;
+    }
+    if (K < 1 || K > SWEEPS_MAX) {
+        efgh_set_error("sweep set: K = %d sweeps, supported are 1 .. %d", (int)K, SWEEPS_MAX);
+        return EFGH_E_INVALID;
+    }
+    if (n_total < 1 || n_total >= (1 << 29)) {
+        efgh_set_error("sweep set: n_total = %d points, supported are 1 .. 2^29 - 1", (int)n_total);
+        return EFGH_E_INVALID;
+    }
+    if (stride != 3 && stride != 4) {
+        efgh_set_error("sweep set: row stride %d, supported are 3 and 4 floats", (int)stride);
+        return EFGH_E_INVALID;
+    }
+    if (stride == 4 && ((uintptr_t)pts & 15)) {
+        efgh_set_error("sweep set: stride-4 points must be 16-byte aligned");
+        return EFGH_E_INVALID;
+    }
+    return EFGH_OK;
+}
+
 }  // namespace
 
 extern "C" int efgh_prep_affine_nearest_u8(const uint8_t *in, int32_t h, int32_t w, const int64_t *coef6,
@@ -250,6 +425,54 @@ extern "C" int efgh_prep_gather_transform(const float *pcd, const int32_t *keep_
     const float s = flip_xy ? -1.f : 1.f;
     k_gather_transform<<<cdiv(num_points, TPB), TPB, 0, (hipStream_t)stream>>>(pcd, keep_idx, sel, n_sel, s, s, T34,
                                                                              num_points, out32, out64);
+    EFGH_CHECK_LAUNCH();
+    return EFGH_OK;
+}
+
+extern "C" int efgh_prep_sweeps_filter(const float *pts, int32_t stride, const int32_t *sweep_off, const double *M34,
+                                       const int32_t *identity, int32_t K, int32_t n_total, const int32_t *pre_idx,
+                                       int32_t n, int32_t flip_xy, double radius, float ego_x_half, float ego_y_half,
+                                       int32_t *block_scratch, int32_t *keep_idx, int32_t *count, void *stream) {
+    hipStream_t st = (hipStream_t)stream;
+    const int rc = sweeps_check(pts, stride, sweep_off, M34, identity, K, n_total);
+    if (rc) return rc;
+    EFGH_CHECK_ARG(block_scratch && keep_idx && count && n > 0 && n < (1 << 29) && (pre_idx || n == n_total));
+    EFGH_CHECK_ARG((radius > 0. || ego_x_half > 0.f) && (ego_x_half > 0.f) == (ego_y_half > 0.f));
+    const SweepSet s{pts, sweep_off, M34, identity, K, stride, n_total};
+    const SweepPred f{radius > 0. ? radius : 0., flip_xy ? -1. : 1., ego_x_half > 0.f ? ego_x_half : 0.f,
+                      ego_y_half > 0.f ? ego_y_half : 0.f};
+    const int nb = (n + TPB - 1) / TPB;
+    k_sweeps_flag_count<<<nb, TPB, 0, st>>>(s, f, pre_idx, n, block_scratch);
+    k_scan_blocks<<<1, TPB, 0, st>>>(block_scratch, nb, count);
+    k_sweeps_compact<<<nb, TPB, 0, st>>>(s, f, pre_idx, n, block_scratch, keep_idx);
+    EFGH_CHECK_LAUNCH();
+    return EFGH_OK;
+}
+
+extern "C" int efgh_prep_sweeps_gather_transform(const float *pts, int32_t stride, const int32_t *sweep_off,
+                                                 const double *M34, const int32_t *identity, int32_t K, int32_t n_total,
+                                                 const int32_t *keep_idx, int32_t n_keep, const int32_t *sel,
+                                                 int32_t n_sel, int32_t flip_xy, const double *T34, int32_t num_points,
+                                                 float *out32, double *out64, void *stream) {
+    const int rc = sweeps_check(pts, stride, sweep_off, M34, identity, K, n_total);
+    if (rc) return rc;
+    EFGH_CHECK_ARG(keep_idx && T34 && (out32 || out64) && num_points > 0 && n_keep >= 0 && n_sel >= 0 &&
+                   n_sel <= num_points && (sel || n_sel <= n_keep));
+    const SweepSet s{pts, sweep_off, M34, identity, K, stride, n_total};
+    k_sweeps_gather_transform<<<cdiv(num_points, TPB), TPB, 0, (hipStream_t)stream>>>(
+        s, keep_idx, sel, n_keep, n_sel, flip_xy ? -1. : 1., T34, num_points, out32, out64);
+    EFGH_CHECK_LAUNCH();
+    return EFGH_OK;
+}
+
+extern "C" int efgh_prep_sweeps_materialize(const float *pts, int32_t stride, const int32_t *sweep_off, const double *M34,
+                                            const int32_t *identity, int32_t K, int32_t n_total, const int32_t *keep_idx,
+                                            int32_t n, double *out, void *stream) {
+    const int rc = sweeps_check(pts, stride, sweep_off, M34, identity, K, n_total);
+    if (rc) return rc;
+    EFGH_CHECK_ARG(out && n > 0 && n < (1 << 29) && (keep_idx || n <= n_total));
+    const SweepSet s{pts, sweep_off, M34, identity, K, stride, n_total};
+    k_sweeps_materialize<<<cdiv(n, TPB), TPB, 0, (hipStream_t)stream>>>(s, keep_idx, n, out);
     EFGH_CHECK_LAUNCH();
     return EFGH_OK;
 }

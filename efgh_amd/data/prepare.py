@@ -1,6 +1,8 @@
 """GPU-side sample preparation: drop-in for the reference's `ProcessKITTIODOM` /
-`ProcessRELLIS` callables (data_loader/kitti_odom_loader.py:237-273, rellis3d_loader.py:292-339) and the
-`preproc_*` helpers they call (data_loader/loader_utils.py:63-202).
+`ProcessRELLIS` / `ProcessKITTIRAW` / `ProcessNUSC` callables (data_loader/kitti_odom_loader.py:237-273,
+rellis3d_loader.py:292-339, kitti_raw_loader.py:227-263, nusc_loader.py:227-262), the `preproc_*` helpers they call
+(data_loader/loader_utils.py:63-202), and the loaders' multi-sweep accumulation as a `SweepSet` the point kernels read
+without ever building the accumulated float64 cloud.
 
 Same constructor (`args` dict), same `__call__(pcd, img, calibs, posej_T_posei, fname, rand_init=None)` and the same
 return tuple `(pc[:3], img, calib, A, gts, fname)` — but the pixel and point work runs in libefgh_hip.so
@@ -239,14 +241,245 @@ def lidar_line_indices(n_points, reduce_to):
     return np.where(idx < 0, idx + n_points, idx).astype(np.int32)
 
 
+def _subsample(n_keep, num_points, sampled_indices, device):
+    """loader_utils.py:189-196: num_points of the n_keep survivors without replacement -> (index tensor, num_points), or all of
+    them (the caller zero-pads) -> (None, n_keep)"""
+    if num_points >= n_keep:
+        return None, n_keep
+    if sampled_indices is None:
+        sel = torch.randperm(n_keep, device=device)[:num_points].to(torch.int32)
+    else:
+        sel = torch.as_tensor(np.asarray(sampled_indices)).to(device=device, dtype=torch.int32)
+        assert sel.numel() == num_points
+    return sel, num_points
+
+
+# ------------------------------------------------------------------------------------------------
+# multi-sweep accumulation: host helpers (float64, the reference's product order) and the sweep set
+# ------------------------------------------------------------------------------------------------
+SWEEPS_MAX = 64          # K of efgh_prep_sweeps_* (include/efgh_hip.h)
+
+
+def accumulation_indices(seq_i, n_frames, num, skip):
+    """`search_for_accumulation` (kitti_odom_loader.py:160-190, rellis3d_loader.py:218-245) as index lists: up to `num` frames
+    seq_i -/+ skip*c, c = 1, 2, ..., stopping at the first one past either end of the sequence.  Returns (prev, next)."""
+    def walk(stride):
+        out, counter = [], 0
+        while len(out) < num:
+            counter += 1
+            seq_j = seq_i + stride * counter
+            if seq_j < 0 or seq_j >= n_frames:
+                break
+            out.append(seq_j)
+        return out
+    return walk(-skip), walk(skip)
+
+
+def accumulation_transform(P_oi, P_oj, Tr=None):
+    """sweep j -> frame of sweep i: `inv(P_oi) @ P_oj` (rellis3d_loader.py:220,237); with the KITTI calibration `Tr`,
+    `Tr_inv @ P_ij @ Tr` evaluated left to right as kitti_odom_loader.py:185 does (Tr_inv = inv(Tr), loader_utils.py:46)"""
+    P_ij = np.linalg.inv(P_oi) @ P_oj
+    if Tr is None:
+        return P_ij
+    return np.linalg.inv(Tr) @ P_ij @ Tr
+
+
+def nusc_accumulation_transform(P_io, P_oj, P_lidar_vehicle, P_vehicle_lidar):
+    """nusc_loader.py:113-114"""
+    P_ij = np.dot(P_io, P_oj)
+    return np.dot(np.dot(P_lidar_vehicle, P_ij), P_vehicle_lidar)
+
+
+def nusc_walk(record, get, direction, num, skip):
+    """the `counter % skip` walk of `lidar_frame_accumulation` (nusc_loader.py:99-123) along record[direction] ('next' or
+    'prev') with `get(token)` in place of `nusc.get('sample_data', token)`: the tokens whose sweeps are accumulated, in order"""
+    out, counter, lidar = [], 1, record
+    while len(out) < num:
+        if lidar[direction] == '':
+            break
+        if counter % skip != 0:
+            counter += 1
+            lidar = get(lidar[direction])
+            continue
+        out.append(lidar[direction])
+        counter += 1
+        lidar = get(lidar[direction])
+    return out
+
+
+class SweepSet(object):
+    """The own sweep plus neighbouring sweeps, each with the 4x4 float64 transform into the own sweep's frame: what the
+    reference's `get_accumulated_pc` / `accumulate_lidar_points` concatenate into one float64 cloud, kept as the float32
+    sweeps it was read from.  `preproc_pcd` and the Process classes take it in place of an array; the kernels compute the
+    float64 positions on the fly (csrc/prep.hip), so the accumulated cloud is never built unless `.accumulated()` asks.
+
+    sweeps      [n_k, 3 | 4] float32 arrays or tensors (one column count for all), the own sweep first; n_k = 0 is allowed
+                for every sweep but the own one
+    transforms  one 4x4 float64 matrix per further sweep (`accumulation_transform`, `nusc_accumulation_transform`)
+    own_order   optional permutation of the own sweep (the reference shuffles it, kitti_odom_loader.py:197)
+    ego_box     (x_half, y_half): drop what lies strictly inside, per sweep, before the transform (nusc_loader.py:88-93
+                uses (0.8, 2.7))
+    Uploads happen once, at the first use: the packed points, and one buffer with offsets, matrices and flags."""
+
+    def __init__(self, sweeps, transforms=None, own_order=None, ego_box=None):
+        sweeps = list(sweeps)
+        transforms = [] if transforms is None else list(transforms)
+        if not 1 <= len(sweeps) <= SWEEPS_MAX:
+            raise _C.EfghError('SweepSet: %d sweeps, supported are 1 .. %d' % (len(sweeps), SWEEPS_MAX))
+        if len(transforms) != len(sweeps) - 1:
+            raise _C.EfghError('SweepSet: %d sweeps need %d transforms (none for the own sweep), got %d'
+                               % (len(sweeps), len(sweeps) - 1, len(transforms)))
+        self._sweeps = []
+        for k, sw in enumerate(sweeps):
+            if not torch.is_tensor(sw):
+                sw = np.ascontiguousarray(sw, dtype=np.float32)
+            if sw.ndim != 2 or sw.shape[1] not in (3, 4) or (self._sweeps and sw.shape[1] != self._sweeps[0].shape[1]):
+                raise _C.EfghError('SweepSet: sweep %d has shape %s, expected [n, 3] or [n, 4] with one column count for all'
+                                   % (k, tuple(sw.shape)))
+            self._sweeps.append(sw)
+        self.lengths = [int(sw.shape[0]) for sw in self._sweeps]
+        self.stride = int(self._sweeps[0].shape[1])
+        self.K = len(sweeps)
+        self.n_total = sum(self.lengths)
+        if self.lengths[0] < 1:
+            raise _C.EfghError('SweepSet: the own sweep is empty')
+        if self.n_total >= 1 << 29:
+            raise _C.EfghError('SweepSet: %d points, supported are fewer than 2^29' % self.n_total)
+        self.M = np.zeros((self.K, 3, 4), np.float64)
+        self.M[0] = np.eye(4)[:3]
+        for k, T in enumerate(transforms):
+            T = np.asarray(T, np.float64)
+            if T.shape != (4, 4):
+                raise _C.EfghError('SweepSet: transform %d has shape %s, expected (4, 4)' % (k, T.shape))
+            self.M[k + 1] = T[:3]
+        self.own_order = None
+        if own_order is not None:
+            order = np.asarray(own_order, np.int64)
+            if order.shape != (self.lengths[0],) or not np.array_equal(np.sort(order), np.arange(self.lengths[0])):
+                raise _C.EfghError('SweepSet: own_order is not a permutation of the own sweep')
+            self.own_order = order
+        self.ego_box = None
+        if ego_box is not None:
+            self.ego_box = (float(ego_box[0]), float(ego_box[1]))
+            if not (self.ego_box[0] > 0. and self.ego_box[1] > 0.):
+                raise _C.EfghError('SweepSet: ego_box is (x_half, y_half), both positive')
+        self._staged = None
+
+    def _stage(self, device):
+        """(points tensor, descriptor tensor, pointers of offsets / matrices / flags) on `device`"""
+        device = torch.device(device)
+        if self._staged is not None and self._staged[0] == device:
+            return self._staged[1]
+        sweeps = list(self._sweeps)
+        if not any(torch.is_tensor(sw) for sw in sweeps):
+            if self.own_order is not None:
+                sweeps[0] = sweeps[0][self.own_order]
+            pts = torch.from_numpy(np.concatenate(sweeps, axis=0) if self.K > 1 else np.ascontiguousarray(sweeps[0]))
+            pts = pts.to(device)
+        else:
+            sweeps = [torch.as_tensor(sw).to(device=device, dtype=torch.float32) for sw in sweeps]
+            if self.own_order is not None:
+                sweeps[0] = sweeps[0][torch.from_numpy(self.own_order).to(device)]
+            pts = (torch.cat(sweeps, dim=0) if self.K > 1 else sweeps[0]).contiguous()
+        _C.require_cuda(pts)
+        off = np.zeros(self.K + 1, np.int32)
+        off[1:] = np.cumsum(self.lengths)
+        ident = np.zeros(self.K, np.int32)
+        ident[0] = 1
+        desc = torch.from_numpy(np.frombuffer(self.M.tobytes() + off.tobytes() + ident.tobytes(), np.uint8).copy()).to(device)
+        base = desc.data_ptr()
+        st = (pts, desc, _C.c_void_p(base + 96 * self.K), _C.c_void_p(base), _C.c_void_p(base + 96 * self.K + 4 * (self.K + 1)))
+        self._staged = (device, st)
+        return st
+
+    def _args(self, device):
+        pts, _, off, M, ident = self._stage(device)
+        return pts, (ptr(pts), c_int32(self.stride), off, M, ident, c_int32(self.K), c_int32(self.n_total))
+
+    def _filter(self, device, pre, n, flip_xy, radius):
+        """stable compaction of the n candidates by ego box and radius -> (keep [n] int32, count [1] int32)"""
+        pts, a = self._args(device)
+        keep = torch.empty(n, dtype=torch.int32, device=pts.device)
+        count = torch.zeros(1, dtype=torch.int32, device=pts.device)
+        scratch = torch.empty(_L().efgh_prep_filter_blocks(c_int32(n)), dtype=torch.int32, device=pts.device)
+        ex, ey = self.ego_box if self.ego_box is not None else (0., 0.)
+        _C.check(_L().efgh_prep_sweeps_filter(*a, ptr(pre), c_int32(n), c_int32(1 if flip_xy else 0),
+                                              ctypes.c_double(0. if radius is None else radius), c_float(ex), c_float(ey),
+                                              ptr(scratch), ptr(keep), ptr(count), _st()))
+        return keep, count
+
+    def kept_indices(self, radius=50., lidar_line=None, flip_xy=False, device='cuda'):
+        """rows of the concatenation (own sweep first, before the ego box) that `preproc_pcd` keeps, in its order: int32 on
+        the device.  For carrying per-point data (intensity, labels) through the same selection."""
+        keep, n_keep = _sweeps_keep(self, lidar_line, radius, flip_xy, device)
+        return keep[:n_keep]
+
+    def accumulated(self, device='cuda'):
+        """the accumulated cloud itself, [n, 3] float64 on the device: what `get_accumulated_pc` (kitti_odom_loader.py:192-225)
+        returns, or `accumulate_lidar_points(...)[:3].T` with the ego box (nusc_loader.py:126-146,156)"""
+        pts, a = self._args(device)
+        keep, n = None, self.n_total
+        if self.ego_box is not None:
+            keep, count = self._filter(device, None, n, False, None)
+            n = int(count.item())
+        out = torch.empty((n, 3), dtype=torch.float64, device=pts.device)
+        if n > 0:
+            _C.check(_L().efgh_prep_sweeps_materialize(*a, ptr(keep), c_int32(n), ptr(out), _st()))
+        return out
+
+
+def _check_line_and_box(ss, lidar_line):
+    if lidar_line is not None and ss.ego_box is not None:
+        raise _C.EfghError('preproc_pcd: lidar_line with an ego_box is not supported: the line reduction indexes the '
+                           'concatenated cloud, whose length after the ego box is known on the device only')
+
+
+def _sweeps_keep(ss, lidar_line, radius, flip_xy, device):
+    """(lidar-line reduction,) ego box and radius filter of a sweep set -> (keep int32 tensor, n_keep)"""
+    _check_line_and_box(ss, lidar_line)
+    pts, _ = ss._args(device)
+    n, pre = ss.n_total, None
+    if lidar_line is not None:
+        idx = lidar_line_indices(n, lidar_line)
+        if idx.size == 0:
+            raise _C.EfghError('preproc_pcd: lidar_line on %d points leaves none' % n)
+        pre = torch.from_numpy(idx).to(pts.device)
+        n = int(pre.numel())
+    if radius is None and ss.ego_box is None:
+        return (pre if pre is not None else torch.arange(n, dtype=torch.int32, device=pts.device)), n
+    # an all-identity set stays float32 in the reference, where numpy compares with float32(radius)
+    r = radius if radius is None or ss.K > 1 else float(np.float32(radius))
+    keep, count = ss._filter(device, pre, n, flip_xy, r)
+    return keep, int(count.item())                       # one host read per sample: the caller's branch depends on it
+
+
+def _preproc_sweeps(ss, gts, num_points, lidar_line, radius, sampled_indices, flip_xy, device, want_float64):
+    """`preproc_pcd` over a sweep set: the same chain on the concatenated index space (efgh_prep_sweeps_*)"""
+    keep, n_keep = _sweeps_keep(ss, lidar_line, radius, flip_xy, device)
+    pts, a = ss._args(device)
+    sel, n_sel = _subsample(n_keep, num_points, sampled_indices, pts.device)
+    T = torch.from_numpy(np.ascontiguousarray(np.asarray(gts['rand_init_l'], np.float64)[:3, :])).to(pts.device)
+    out32 = torch.empty((3, num_points), dtype=torch.float32, device=pts.device)
+    out64 = torch.empty((3, num_points), dtype=torch.float64, device=pts.device) if want_float64 else None
+    _C.check(_L().efgh_prep_sweeps_gather_transform(*a, ptr(keep), c_int32(n_keep), ptr(sel), c_int32(n_sel),
+                                                    c_int32(1 if flip_xy else 0), ptr(T), c_int32(num_points), ptr(out32),
+                                                    ptr(out64), _st()))
+    return (out32, out64) if want_float64 else out32
+
+
 def preproc_pcd(pcd, gts, num_points, lidar_line=None, radius=50., sampled_indices=None, flip_xy=False, device='cuda',
                 want_float64=False):
     """loader_utils.py:160-202: (lidar-line reduction,) radius filter, sub-sample without replacement (or zero pad),
     homogeneous transform by `rand_init_l` in float64.  Returns (3, num_points) float32 on the device
     (the reference's float64 rows are cast by the training loop, iterater.py:29)."""
+    if isinstance(pcd, SweepSet):
+        return _preproc_sweeps(pcd, gts, num_points, lidar_line, radius, sampled_indices, flip_xy, device, want_float64)
     p = torch.as_tensor(np.ascontiguousarray(pcd, dtype=np.float32)) if not torch.is_tensor(pcd) else pcd
     p = p.to(device=device, dtype=torch.float32).contiguous()
     _C.require_cuda(p)
+    if p.dim() == 2 and p.shape[1] == 3:                 # [n, 3] rows (the KITTI-raw and nuScenes readers): read at stride 3
+        return _preproc_sweeps(SweepSet([p]), gts, num_points, lidar_line, radius, sampled_indices, flip_xy, device,
+                               want_float64)
     assert p.dim() == 2 and p.shape[1] == 4
     n_src = p.shape[0]
     pre = None
@@ -264,16 +497,7 @@ def preproc_pcd(pcd, gts, num_points, lidar_line=None, radius=50., sampled_indic
     else:
         keep = pre if pre is not None else torch.arange(n, dtype=torch.int32, device=p.device)
         n_keep = n
-    sel = None
-    if num_points < n_keep:
-        if sampled_indices is None:
-            sel = torch.randperm(n_keep, device=p.device)[:num_points].to(torch.int32)
-        else:
-            sel = torch.as_tensor(np.asarray(sampled_indices)).to(device=p.device, dtype=torch.int32)
-            assert sel.numel() == num_points
-        n_sel = num_points
-    else:
-        n_sel = n_keep
+    sel, n_sel = _subsample(n_keep, num_points, sampled_indices, p.device)
     T = torch.from_numpy(np.ascontiguousarray(np.asarray(gts['rand_init_l'], np.float64)[:3, :])).to(p.device)
     out32 = torch.empty((3, num_points), dtype=torch.float32, device=p.device)
     out64 = torch.empty((3, num_points), dtype=torch.float64, device=p.device) if want_float64 else None
@@ -287,10 +511,11 @@ def preproc_pcd(pcd, gts, num_points, lidar_line=None, radius=50., sampled_indic
 # ------------------------------------------------------------------------------------------------
 class _Process(object):
     rellis = False
+    has_lidar_line = True
 
     def __init__(self, args):
         self.raw_cam_img_size = args['raw_cam_img_size']
-        self.lidar_line = args['lidar_line']
+        self.lidar_line = args['lidar_line'] if self.has_lidar_line else None
         self.num_points = args['num_points']
         self.device = args.get('DEVICE', 'cuda')
         if args['test'] is False:
@@ -303,7 +528,8 @@ class _Process(object):
     def _calib(self, calibs):
         raise NotImplementedError
 
-    def __call__(self, pcd, img, calibs, posej_T_posei, fname, rand_init=None, sampled_indices=None):
+    def _run(self, pcd, img, calib, posej_T_posei, rand_init, sampled_indices):
+        """the body all four callables share; `pcd` is an array or a SweepSet, `calib` the camera matrix as it is returned"""
         rr, rp, ry, tx, ty, tz, rt = rand_init_params(rand_init, self.l_rot_range, self.l_trs_range, self.c_rot_range)
         gts = preproc_gt(rr, rp, ry, tx, ty, tz, rt, posej_T_posei)
         imgs = preproc_img(img, gts, self.raw_cam_img_size, self.rellis, self.device)
@@ -311,9 +537,11 @@ class _Process(object):
                          flip_xy=self.rellis, device=self.device)
         gts['img_raw'], gts['img_rot'], gts['img_mask'] = imgs['raw'], imgs['rot'], imgs['img_mask']
         A = np.array([[1, 0, -self.raw_cam_img_size[1] / 2], [0, 1, -self.raw_cam_img_size[0] / 2], [0, 0, 1]])
-        calib = self._calib(calibs)[:3, :]
         gts['cam_T_velo'] = np.linalg.inv(A) @ gts['intrinsic_sensor2'] @ A @ calib @ gts['sensor2_T_sensor1']
-        return pc, imgs['in'], calib, A, gts, fname
+        return pc, imgs['in'], calib, A, gts
+
+    def __call__(self, pcd, img, calibs, posej_T_posei, fname, rand_init=None, sampled_indices=None):
+        return self._run(pcd, img, self._calib(calibs)[:3, :], posej_T_posei, rand_init, sampled_indices) + (fname,)
 
 
 class ProcessKITTIODOM(_Process):
@@ -331,3 +559,27 @@ class ProcessRELLIS(_Process):
     def _calib(self, calibs):
         R = np.array([[-1, 0, 0, 0], [0, -1, 0, 0], [0, 0, 1, 0], [0, 0, 0, 1]])
         return calibs['P'] @ calibs['Tr'] @ np.linalg.inv(R)
+
+
+class ProcessKITTIRAW(_Process):
+    """data_loader/kitti_raw_loader.py:227-263: no pose between sweep and image (`posej_T_posei` = I), the calibration is
+    `calibs.T_cam2_velo` / `T_cam3_velo` chosen by `cam` and returned as it is; the reader hands over [n, 3] rows"""
+
+    def __call__(self, pcd, img, calibs, cam, fname, rand_init=None, sampled_indices=None):
+        if cam not in ('image_02', 'image_03'):
+            raise ValueError("ProcessKITTIRAW: cam is 'image_02' or 'image_03', got %r" % (cam,))
+        calib = calibs.T_cam2_velo if cam == 'image_02' else calibs.T_cam3_velo
+        return self._run(pcd, img, calib, np.eye(4), rand_init, sampled_indices) + (fname,)
+
+
+class ProcessNUSC(_Process):
+    """data_loader/nusc_loader.py:227-262: no lidar-line reduction, pose and camera matrix come in `calibs`, and the token
+    pair is returned in place of a file name"""
+    has_lidar_line = False
+
+    def __init__(self, args):
+        super().__init__(args)
+        self.is_test = args['test']
+
+    def __call__(self, pcd, img, calibs, tokeni_tokenj, rand_init=None, sampled_indices=None):
+        return self._run(pcd, img, calibs['T_cam_velo'], calibs['posej_T_posei'], rand_init, sampled_indices) + (tokeni_tokenj,)

@@ -7,6 +7,7 @@ loop of the reference's iterater.py:25-60 with nothing on the CPU between the de
     python examples/train_synthetic.py --iters 3 --transactional                 # a skipped step also restores BatchNorm's state
     python examples/train_synthetic.py --iters 5 --ema 0.999                     # validate the live and the averaged weights
     python examples/train_synthetic.py --iters 3 --groups                        # parameter groups: G at a tenth of the rate, no decay on 1-D parameters
+    python examples/train_synthetic.py --iters 3 --accumulate-sweeps 2           # 2 neighbouring sweeps on either side, merged on the GPU
 """
 import argparse
 import os
@@ -18,7 +19,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from efgh_amd import synthetic as syn  # noqa: E402
 from efgh_amd.common.metrics import Err  # noqa: E402
-from efgh_amd.data import ProcessKITTIODOM  # noqa: E402
+from efgh_amd.data import ProcessKITTIODOM, SweepSet, accumulation_indices, accumulation_transform  # noqa: E402
 from efgh_amd.losses import EFGHCriterion  # noqa: E402
 from efgh_amd.nets import EFGHBackbone  # noqa: E402
 from efgh_amd.train import Trainer  # noqa: E402
@@ -62,6 +63,9 @@ def main(argv=None):
     ap.add_argument('--groups', action='store_true',
                     help='parameter groups inside the fused step: the ResNet branch G at a tenth of the learning rate, weight '
                          'decay on the rest except BatchNorm weights and biases')
+    ap.add_argument('--accumulate-sweeps', type=int, default=0, metavar='N',
+                    help='merge up to N neighbouring LiDAR sweeps on either side into every sample (the loaders\' '
+                         'accumulation_frame_num; not to be confused with --accumulate, which accumulates gradients)')
     a = ap.parse_args(argv)
     a.skip_nonfinite = a.skip_nonfinite or a.transactional
     raw = tuple(a.raw)
@@ -90,6 +94,15 @@ def main(argv=None):
         for b in range(a.batch):
             seed = it * a.batch + b
             sweep = np.concatenate([syn.lidar_sweep(a.points * 2, seed).T, np.ones((a.points * 2, 1), np.float32)], 1)
+            if a.accumulate_sweeps:
+                # frame `own` of a 2N+1-frame drive along x: what get_accumulated_pc concatenates, kept as float32 sweeps with
+                # one 4x4 each; near the ends of the drive fewer frames are found, as in the loaders
+                n_frames, own = 2 * a.accumulate_sweeps + 1, seed % (2 * a.accumulate_sweeps + 1)
+                pose = lambda f: np.array([[1., 0, 0, 0.5 * f], [0, 1, 0, 0.02 * f], [0, 0, 1, 0], [0, 0, 0, 1]])
+                prev, nxt = accumulation_indices(own, n_frames, a.accumulate_sweeps, 1)
+                others = [np.concatenate([syn.lidar_sweep(a.points, 1000 * seed + f).T, np.ones((a.points, 1), np.float32)], 1)
+                          for f in prev + nxt]
+                sweep = SweepSet([sweep] + others, [accumulation_transform(pose(own), pose(f)) for f in prev + nxt])
             samples.append(prep(sweep, raw_frame(raw, seed), {'P2': P2, 'Tr': np.eye(4)}, np.eye(4), 'f%06d' % seed)[:5])
         pc, img, calib, A, gt = collate(samples, 'cuda')
         if a.accumulate:                                     # one loss over the whole batch, BatchNorm statistics per micro-batch

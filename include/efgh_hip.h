@@ -62,7 +62,9 @@ const char *efgh_last_error(void);
  *      efgh_txn_snapshot, efgh_txn_probe, efgh_txn_resolve and the struct efgh_txn_state (BatchNorm running statistics and counters
  *      rolled back when the guarded step is skipped; a non-finite forward skips it);
  *      efgh_ema_update, efgh_ema_swap (exponential moving average of the flat weights);
- *      efgh_adam_step_groups and the struct efgh_adam_groups (the fused optimizer step with torch.optim's parameter groups). */
+ *      efgh_adam_step_groups and the struct efgh_adam_groups (the fused optimizer step with torch.optim's parameter groups);
+ *      efgh_prep_sweeps_filter, efgh_prep_sweeps_gather_transform, efgh_prep_sweeps_materialize (multi-sweep accumulation and
+ *      stride-3 rows in sample preparation). */
 #define EFGH_ABI_VERSION 4
 int efgh_version(void);
 
@@ -959,6 +961,34 @@ int efgh_prep_radius_filter(const float *pcd, const int32_t *pre_idx, int32_t n,
 int efgh_prep_gather_transform(const float *pcd, const int32_t *keep_idx, const int32_t *sel, int32_t n_sel,
                                int32_t flip_xy, const double *T34, int32_t num_points, float *out32, double *out64,
                                void *stream);
+/* Sweep sets: multi-sweep accumulation (get_accumulated_pc / search_for_accumulation, kitti_odom_loader.py:160-225 and
+ * rellis3d_loader.py:218-280; accumulate_lidar_points / lidar_frame_accumulation, nusc_loader.py:83-146) without ever writing
+ * the accumulated float64 cloud.  A set is: pts, K sweeps packed back to back as fp32 rows of `stride` (3 or 4) floats
+ * (stride 4: 16-byte aligned); sweep_off [K+1] int32 (first row of each sweep, sweep_off[K] = n_total; an empty sweep repeats its
+ * offset); M34 [K][3][4] float64; identity [K] int32.  Point p of sweep k stands at q = M_k . (p, 1) in float64, the four terms
+ * summed left to right; where identity[k] != 0 it passes through untouched, q = (double)p (so -0.0, inf and NaN survive as in
+ * numpy's concatenate).  All five arrays are device memory.  1 <= K <= 64 and 1 <= n_total < 2^29, otherwise EFGH_E_INVALID with a
+ * message and nothing is launched.  Indices are rows of the concatenation, 0 .. n_total-1; an index outside it is never read.
+ *
+ * efgh_prep_sweeps_filter: efgh_prep_radius_filter over the n candidates pre_idx[0..n) (NULL: 0..n_total-1, n == n_total).  Kept is
+ * what is NOT strictly inside the ego box |x| < ego_x_half && |y| < ego_y_half (fp32 compare on the RAW point, the per-sweep filter
+ * of nusc_loader.py:88-93; both halves <= 0: no box) AND has -r <= q.x < r && -r <= q.y < r (float64 compare, after negating q.x and
+ * q.y when flip_xy; radius <= 0: no radius test).  At least one of the two tests must be on.  keep_idx [n] receives the kept indices
+ * in candidate order, *count their number; block_scratch has efgh_prep_filter_blocks(n) ints.
+ * efgh_prep_sweeps_gather_transform: efgh_prep_gather_transform reading q of keep_idx[sel[j]] (sel NULL: j; an entry outside
+ * [0, n_keep) gives the zero point).
+ * efgh_prep_sweeps_materialize: out [n][3] float64 = q of keep_idx[j] (NULL: j), the accumulated cloud itself.               */
+int efgh_prep_sweeps_filter(const float *pts, int32_t stride, const int32_t *sweep_off, const double *M34,
+                            const int32_t *identity, int32_t K, int32_t n_total, const int32_t *pre_idx, int32_t n,
+                            int32_t flip_xy, double radius, float ego_x_half, float ego_y_half, int32_t *block_scratch,
+                            int32_t *keep_idx, int32_t *count, void *stream);
+int efgh_prep_sweeps_gather_transform(const float *pts, int32_t stride, const int32_t *sweep_off, const double *M34,
+                                      const int32_t *identity, int32_t K, int32_t n_total, const int32_t *keep_idx,
+                                      int32_t n_keep, const int32_t *sel, int32_t n_sel, int32_t flip_xy, const double *T34,
+                                      int32_t num_points, float *out32, double *out64, void *stream);
+int efgh_prep_sweeps_materialize(const float *pts, int32_t stride, const int32_t *sweep_off, const double *M34,
+                                 const int32_t *identity, int32_t K, int32_t n_total, const int32_t *keep_idx, int32_t n,
+                                 double *out, void *stream);
 
 /* ------------------------------------------------------------------ evaluation metrics --
  * Err.calc_error_odom_np (mode 0: arccos((tr(pred_R^T gt_R)-1)/2) in degrees, |pred_t - gt_t|_2; common/helper.py:198-207)
