@@ -5,7 +5,9 @@ are wrapped for the duration of a run; ops._L is replaced by a proxy that record
 launch is compared at its real shape, with its real data, strides and offsets, whichever kernel served it: the written region within
 tau[family] * S, every element of the destination outside the declared write set bit-unchanged, the statistics epilogue and the
 returned BatchNorm-backward partials.  The runs: (a) the golden size, (b) config R, (c) config R with every activation materialised,
-then again on the split-bf16 planes, (d) config S at batch 2 and its eval forward, (e) the E net at BCL radius 2."""
+then again on the split-bf16 planes, (d) config S at batch 2 and its eval forward, (e) the E net at BCL radius 2.
+The operands of the launches recorded as `unchecked (pre_v / pre_gy)` - Vd and Gy of efgh_wino2d_bwd_transforms(_pooled) - are held
+element by element by tests/w2_contract.py (tests/test_gpu_w2_contract.py)."""
 import threading
 import time
 
