@@ -129,6 +129,8 @@ def lib():
         _lib.efgh_offsets_invert_workspace.argtypes = [c_int32, c_int32]
         _lib.efgh_slice_bwd_workspace.restype = c_int64
         _lib.efgh_slice_bwd_workspace.argtypes = [c_int32]
+        _lib.efgh_prep_voxel_workspace.restype = c_int64
+        _lib.efgh_prep_voxel_workspace.argtypes = [c_int32]
         _lib.efgh_grad_guard_workspace.restype = c_int64
         _lib.efgh_grad_guard_workspace.argtypes = [c_int64]
         _lib.efgh_grad_guard_measure.argtypes = [c_void_p, c_int64, ctypes.POINTER(c_int64), c_int32, ctypes.c_double, c_float,

@@ -32,6 +32,12 @@ void efgh_set_error(const char *fmt, ...);
 
 static inline int cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 
+// the hash finaliser of the open-addressing tables (lattice.hip's vertex table, prep.hip's voxel table): home slot = mix64(key) & mask
+__device__ __forceinline__ uint64_t mix64(uint64_t x) {
+    x ^= x >> 33; x *= 0xff51afd7ed558ccdULL; x ^= x >> 33; x *= 0xc4ceb9fe1a85ec53ULL; x ^= x >> 33;
+    return x;
+}
+
 // Adam's bias corrections of a step count the HOST knows (adam.hip's entry points, and guard.hip's when no step can be skipped; a
 // count that lives on the device is corrected there, by k_guard_decide): fp32 throughout
 struct efgh_bias_corr { float bc1, bc2_sqrt; };         // 1 - beta1^step, sqrt(1 - beta2^step)

@@ -61,11 +61,6 @@ __device__ __forceinline__ int64_t key2int(const int k[4], const int *mm) {
     return res;
 }
 
-__device__ __forceinline__ uint64_t mix64(uint64_t x) {
-    x ^= x >> 33; x *= 0xff51afd7ed558ccdULL; x ^= x >> 33; x *= 0xc4ceb9fe1a85ec53ULL; x ^= x >> 33;
-    return x;
-}
-
 __device__ __forceinline__ int n_of(const int *n_dev, int n_cap) {
     if (!n_dev) return n_cap;
     int n = *n_dev;

@@ -357,6 +357,171 @@ int sweeps_check(const float *pts, int32_t stride, const int32_t *off, const dou
     return EFGH_OK;
 }
 
+// ---- voxel thinning: of the candidate rows j = 0 .. n-1 keep the FIRST one of every occupied voxel (stable) ---------------
+// Row j stands at q (sweep_position above for a sweep set, (double)p for plain rows; before the RELLIS flip and before
+// rand_init_l).  Per axis t = floor(q / v) in float64, an IEEE division.  The row is representable when every t is finite and
+// |t| < 2^20; its key is (tx + 2^20) | (ty + 2^20) << 21 | (tz + 2^20) << 42: 63 bits, never the empty marker.  Any other row
+// (NaN, inf, out of range, or a source index outside the rows) is kept alone and takes no part in the table.
+// Table: cap = the smallest power of two >= 2 n_cap (at least 2), keys[cap] u64 and first[cap] u32, both all ones when empty; home
+// slot mix64(key) & (cap - 1), linear probing +1 with wrap.  As in lattice.hip every global atomic costs the same ~1/26 ns
+// chip-wide, so the pass pays one CAS per VOXEL (the key is looked up with a plain load first: a key never changes once written,
+// so a match is final, and a stale empty only sends the row to the CAS, which returns the truth) and at most one atomicMin per ROW
+// (first[slot] only decreases: a plain load that already shows a value <= j is final too).  first[slot] ends as the smallest j of
+// the voxel whatever the order of insertion, so the kept set depends on neither the schedule nor the grid.  The representative
+// is an input row: no floating-point atomic, no centroid.
+// The probe loop is bounded by cap.  At load <= 0.5 it cannot run out; if it ever does, the row is kept alone and count[1] is set,
+// which the caller turns into an error: a bug becomes a message, not a hang.
+constexpr unsigned long long VOX_EMPTY = ~0ull;
+constexpr int VOX_ALONE = -1;                            // slot of a row that is kept alone
+
+struct VoxelTable {
+    unsigned long long *keys;  // [cap]
+    unsigned *first;           // [cap]
+    int *slot;                 // [n_cap] the slot of row j, or VOX_ALONE
+    unsigned mask;             // cap - 1
+};
+
+// rows in use: the device count where there is one (the count of the filter in front), clamped to the capacity
+__device__ __forceinline__ int rows_of(const int *n_dev, int n_cap) {
+    if (!n_dev) return n_cap;
+    const int n = *n_dev;
+    return n < 0 ? 0 : (n < n_cap ? n : n_cap);
+}
+
+template <bool SWEEPS>
+__device__ __forceinline__ bool voxel_key(const SweepSet &s, const int *lds_off, int i, double v, unsigned long long *key) {
+    if (i < 0 || i >= s.n_total) return false;
+    const Raw3 p = load_raw(s, i);
+    double q[3] = {(double)p.x, (double)p.y, (double)p.z};
+    if (SWEEPS) sweep_position(s, sweep_of(lds_off, s.K, i), p, q);
+    unsigned long long k = 0;
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+        const double t = floor(q[r] / v);
+        if (!(fabs(t) < 1048576.0)) return false;        // tested in double, before any integer cast: NaN and inf fail it
+        k |= (unsigned long long)((long long)t + 1048576) << (21 * r);
+    }
+    *key = k;
+    return true;
+}
+
+// keys and first <- all ones over the whole table, count[0..1] <- 0
+__global__ void k_voxel_init(VoxelTable t, int *__restrict__ count) {
+    const unsigned i = blockIdx.x * TPB + threadIdx.x;
+    if (i <= t.mask) { t.keys[i] = VOX_EMPTY; t.first[i] = ~0u; }
+    if (i < 2) count[i] = 0;
+}
+
+template <bool SWEEPS>
+__global__ void k_voxel_insert(SweepSet s, const int *__restrict__ keep_in, int n_cap, const int *__restrict__ n_dev, double v,
+                               VoxelTable t, int *__restrict__ count) {
+    __shared__ int lds_off[SWEEPS_MAX + 1];
+    if (SWEEPS) {
+        stage_offsets(s, lds_off);
+        __syncthreads();
+    }
+    const int j = blockIdx.x * TPB + threadIdx.x;
+    if (j >= rows_of(n_dev, n_cap)) return;
+    unsigned long long key;
+    if (!voxel_key<SWEEPS>(s, lds_off, keep_in ? keep_in[j] : j, v, &key)) { t.slot[j] = VOX_ALONE; return; }
+    unsigned h = (unsigned)mix64(key) & t.mask;
+    int found = VOX_ALONE;
+    for (unsigned probe = 0; probe <= t.mask; ++probe) {
+        unsigned long long cur = t.keys[h];
+        if (cur == VOX_EMPTY) {
+            cur = atomicCAS(&t.keys[h], VOX_EMPTY, key);
+            if (cur == VOX_EMPTY) cur = key;             // claimed
+        }
+        if (cur == key) { found = (int)h; break; }
+        h = (h + 1) & t.mask;
+    }
+    t.slot[j] = found;
+    if (found == VOX_ALONE) { count[1] = 1; return; }    // table exhausted
+    if (t.first[found] > (unsigned)j) atomicMin(&t.first[found], (unsigned)j);
+}
+
+__device__ __forceinline__ bool voxel_flag(const VoxelTable &t, int j, int n) {
+    if (j >= n) return false;
+    const int sl = t.slot[j];
+    return sl == VOX_ALONE || t.first[sl] == (unsigned)j;
+}
+
+// k_flag_count / k_compact of the radius filter over the voxel flag (k_scan_blocks runs between them as it is)
+__global__ void k_voxel_flag_count(VoxelTable t, int n_cap, const int *__restrict__ n_dev, int *__restrict__ block_count) {
+    __shared__ int wave_cnt[TPB / 64];
+    const bool k = voxel_flag(t, blockIdx.x * TPB + threadIdx.x, rows_of(n_dev, n_cap));
+    const unsigned long long m = __ballot(k);
+    if ((threadIdx.x & 63) == 0) wave_cnt[threadIdx.x >> 6] = __popcll(m);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int c = 0;
+        for (int q = 0; q < TPB / 64; ++q) c += wave_cnt[q];
+        block_count[blockIdx.x] = c;
+    }
+}
+
+__global__ void k_voxel_compact(VoxelTable t, const int *__restrict__ keep_in, int n_cap, const int *__restrict__ n_dev,
+                                const int *__restrict__ block_off, int *__restrict__ keep_out) {
+    __shared__ int wave_cnt[TPB / 64];
+    const int j = blockIdx.x * TPB + threadIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const bool k = voxel_flag(t, j, rows_of(n_dev, n_cap));
+    const unsigned long long m = __ballot(k);
+    if (lane == 0) wave_cnt[wave] = __popcll(m);
+    __syncthreads();
+    int o = block_off[blockIdx.x];
+    for (int q = 0; q < wave; ++q) o += wave_cnt[q];
+    if (k) keep_out[o + __popcll(m & ((1ull << lane) - 1ull))] = keep_in ? keep_in[j] : j;   // o + rank <= j < n_cap
+}
+
+long long voxel_capacity(long long n) {
+    long long cap = 2;
+    while (cap < 2 * n) cap <<= 1;
+    return cap;
+}
+
+// the argument contract shared by the two efgh_prep_*voxel_keep entry points, then the five launches
+template <bool SWEEPS>
+int voxel_keep(const SweepSet &s, const int32_t *keep_in, int32_t n_cap, const int32_t *n_dev, double voxel, void *workspace,
+               int32_t *keep_out, int32_t *count, hipStream_t st) {
+    if (!(voxel > 0.) || !isfinite(voxel)) {
+        efgh_set_error("voxel thinning: voxel = %g, the edge length must be positive and finite", voxel);
+        return EFGH_E_INVALID;
+    }
+    if (n_cap < 0 || n_cap >= (1 << 29)) {
+        efgh_set_error("voxel thinning: n_cap = %d candidate rows, supported are 0 .. 2^29 - 1", (int)n_cap);
+        return EFGH_E_INVALID;
+    }
+    if (!keep_in && n_cap > s.n_total) {
+        efgh_set_error("voxel thinning: n_cap = %d exceeds the %d rows and there is no keep_in", (int)n_cap, s.n_total);
+        return EFGH_E_INVALID;
+    }
+    if (!workspace || ((uintptr_t)workspace & 7)) {
+        efgh_set_error("voxel thinning: workspace is null or not 8-byte aligned");
+        return EFGH_E_INVALID;
+    }
+    if (!keep_out || !count) {
+        efgh_set_error("voxel thinning: null keep_out or count");
+        return EFGH_E_INVALID;
+    }
+    const long long cap = voxel_capacity(n_cap);
+    VoxelTable t;
+    t.keys = (unsigned long long *)workspace;
+    t.first = (unsigned *)(t.keys + cap);
+    t.slot = (int *)(t.first + cap);
+    t.mask = (unsigned)(cap - 1);
+    int *blocks = t.slot + n_cap;
+    k_voxel_init<<<cdiv(cap, TPB), TPB, 0, st>>>(t, count);
+    if (n_cap > 0) {
+        const int nb = (n_cap + TPB - 1) / TPB;
+        k_voxel_insert<SWEEPS><<<nb, TPB, 0, st>>>(s, keep_in, n_cap, n_dev, voxel, t, count);
+        k_voxel_flag_count<<<nb, TPB, 0, st>>>(t, n_cap, n_dev, blocks);
+        k_scan_blocks<<<1, TPB, 0, st>>>(blocks, nb, count);
+        k_voxel_compact<<<nb, TPB, 0, st>>>(t, keep_in, n_cap, n_dev, blocks, keep_out);
+    }
+    EFGH_CHECK_LAUNCH();
+    return EFGH_OK;
+}
+
 }  // namespace
 
 extern "C" int efgh_prep_affine_nearest_u8(const uint8_t *in, int32_t h, int32_t w, const int64_t *coef6,
@@ -475,4 +640,34 @@ extern "C" int efgh_prep_sweeps_materialize(const float *pts, int32_t stride, co
     k_sweeps_materialize<<<cdiv(n, TPB), TPB, 0, (hipStream_t)stream>>>(s, keep_idx, n, out);
     EFGH_CHECK_LAUNCH();
     return EFGH_OK;
+}
+
+extern "C" int64_t efgh_prep_voxel_workspace(int32_t n) {
+    if (n < 0 || n >= (1 << 29)) return -1;
+    return voxel_capacity(n) * 12 + 4LL * n + 4LL * ((n + TPB - 1) / TPB);
+}
+
+extern "C" int efgh_prep_voxel_keep(const float *pts, int32_t stride, int32_t n_rows, const int32_t *keep_in, int32_t n_cap,
+                                    const int32_t *n_dev, double voxel, void *workspace, int32_t *keep_out, int32_t *count,
+                                    void *stream) {
+    if (!pts || n_rows < 1 || n_rows >= (1 << 29)) {
+        efgh_set_error("voxel thinning: null pts, or n_rows = %d rows, supported are 1 .. 2^29 - 1", (int)n_rows);
+        return EFGH_E_INVALID;
+    }
+    if ((stride != 3 && stride != 4) || (stride == 4 && ((uintptr_t)pts & 15))) {
+        efgh_set_error("voxel thinning: row stride %d, supported are 3 and 4 floats (stride 4: 16-byte aligned)", (int)stride);
+        return EFGH_E_INVALID;
+    }
+    const SweepSet s{pts, nullptr, nullptr, nullptr, 0, stride, n_rows};
+    return voxel_keep<false>(s, keep_in, n_cap, n_dev, voxel, workspace, keep_out, count, (hipStream_t)stream);
+}
+
+extern "C" int efgh_prep_sweeps_voxel_keep(const float *pts, int32_t stride, const int32_t *sweep_off, const double *M34,
+                                           const int32_t *identity, int32_t K, int32_t n_total, const int32_t *keep_in,
+                                           int32_t n_cap, const int32_t *n_dev, double voxel, void *workspace, int32_t *keep_out,
+                                           int32_t *count, void *stream) {
+    const int rc = sweeps_check(pts, stride, sweep_off, M34, identity, K, n_total);
+    if (rc) return rc;
+    const SweepSet s{pts, sweep_off, M34, identity, K, stride, n_total};
+    return voxel_keep<true>(s, keep_in, n_cap, n_dev, voxel, workspace, keep_out, count, (hipStream_t)stream);
 }

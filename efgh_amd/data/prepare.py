@@ -255,6 +255,85 @@ def _subsample(n_keep, num_points, sampled_indices, device):
 
 
 # ------------------------------------------------------------------------------------------------
+# thinning on a voxel grid (efgh_prep_voxel_keep / efgh_prep_sweeps_voxel_keep, csrc/prep.hip)
+# ------------------------------------------------------------------------------------------------
+def _check_voxel_size(voxel_size):
+    try:
+        v = float(voxel_size)
+    except (TypeError, ValueError):
+        raise _C.EfghError('voxel_size: expected a positive finite edge length, got %r' % (voxel_size,))
+    if not (v > 0. and math.isfinite(v)):
+        raise _C.EfghError('voxel_size: expected a positive finite edge length, got %r' % (voxel_size,))
+    return v
+
+
+def _read_counts(counts):
+    """the one host read of a thinned sample: (kept count, table-exhausted flag)"""
+    return [int(c) for c in counts.cpu()]
+
+
+def _upload_T(gts, device, wait=True):
+    """rows 0..2 of rand_init_l as float64 on the device.  `wait=False` stages through pinned memory and copies asynchronously, so
+    the thinning path waits for the device once per sample, at `_read_counts`"""
+    T = torch.from_numpy(np.ascontiguousarray(np.asarray(gts['rand_init_l'], np.float64)[:3, :]))
+    return T.to(device) if wait else T.pin_memory().to(device, non_blocking=True)
+
+
+def _voxel_thin(src, keep, n, n_dev, voxel_size, device):
+    """of the candidates keep[0 .. n) (None: rows 0 .. n-1; `n_dev`: their count on the device, None: n) the first row of every
+    occupied voxel, in order -> (int32 tensor, count).  `src` is a SweepSet or a resident [rows, 3 | 4] float32 tensor."""
+    v = _check_voxel_size(voxel_size)
+    L = _L()
+    if isinstance(src, SweepSet):
+        pts, a = src._args(device)
+        fn = L.efgh_prep_sweeps_voxel_keep
+    else:
+        pts = src
+        a = (ptr(pts), c_int32(int(pts.shape[1])), c_int32(int(pts.shape[0])))
+        fn = L.efgh_prep_voxel_keep
+    nbytes = L.efgh_prep_voxel_workspace(c_int32(n))
+    if nbytes < 0:
+        raise _C.EfghError('voxel thinning: %d candidate rows, supported are fewer than 2^29' % n)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=pts.device)
+    out = torch.empty(n, dtype=torch.int32, device=pts.device)
+    counts = torch.empty(2, dtype=torch.int32, device=pts.device)
+    _C.check(fn(*a, ptr(keep), c_int32(n), ptr(n_dev), ctypes.c_double(v), ptr(ws), ptr(out), ptr(counts), _st()))
+    n_keep, exhausted = _read_counts(counts)
+    if exhausted:
+        raise _C.EfghError('voxel thinning: the hash table of %d candidate rows ran out of slots (a bug: it is sized at load <= 0.5)' % n)
+    return out, n_keep
+
+
+def voxel_keep(points, voxel_size, keep=None, device='cuda'):
+    """Thin a cloud on a voxel grid of edge `voxel_size`: the rows whose voxel no earlier row occupies (first seen wins, so the own
+    sweep of a SweepSet wins over its neighbours), ascending, int32 on the device.  A row with a NaN or inf coordinate, or more than
+    2^20 voxels from the origin, is kept alone.  `points` is a SweepSet (rows of its concatenation, positions in the own sweep's
+    frame) or a [n, 3 | 4] float32 array or tensor; `keep` optionally restricts and orders the candidates (e.g.
+    `SweepSet.kept_indices()`).  The representative is an input row, so per-point data can be carried through the indices."""
+    _check_voxel_size(voxel_size)
+    if isinstance(points, SweepSet):
+        src, rows = points, points.n_total
+        dev = points._args(device)[0].device
+    else:
+        p = torch.as_tensor(np.ascontiguousarray(points, dtype=np.float32)) if not torch.is_tensor(points) else points
+        if p.dim() != 2 or p.shape[1] not in (3, 4) or p.shape[0] < 1:
+            raise _C.EfghError('voxel_keep: points has shape %s, expected [n, 3] or [n, 4] with n >= 1' % (tuple(p.shape),))
+        src = p.to(device=device, dtype=torch.float32).contiguous()
+        _C.require_cuda(src)
+        rows, dev = int(src.shape[0]), src.device
+    if keep is not None:
+        keep = torch.as_tensor(np.asarray(keep)) if not torch.is_tensor(keep) else keep
+        if keep.dim() != 1 or keep.dtype in (torch.float16, torch.float32, torch.float64, torch.bool):
+            raise _C.EfghError('voxel_keep: keep is a 1-D integer index list, got %s of shape %s' % (keep.dtype, tuple(keep.shape)))
+        keep = keep.to(device=dev, dtype=torch.int32).contiguous()
+        rows = int(keep.numel())
+        if rows == 0:
+            return keep
+    out, n_keep = _voxel_thin(src, keep, rows, None, voxel_size, dev)
+    return out[:n_keep]
+
+
+# ------------------------------------------------------------------------------------------------
 # multi-sweep accumulation: host helpers (float64, the reference's product order) and the sweep set
 # ------------------------------------------------------------------------------------------------
 SWEEPS_MAX = 64          # K of efgh_prep_sweeps_* (include/efgh_hip.h)
@@ -408,10 +487,11 @@ class SweepSet(object):
                                               ptr(scratch), ptr(keep), ptr(count), _st()))
         return keep, count
 
-    def kept_indices(self, radius=50., lidar_line=None, flip_xy=False, device='cuda'):
+    def kept_indices(self, radius=50., lidar_line=None, flip_xy=False, device='cuda', voxel_size=None):
         """rows of the concatenation (own sweep first, before the ego box) that `preproc_pcd` keeps, in its order: int32 on
-        the device.  For carrying per-point data (intensity, labels) through the same selection."""
-        keep, n_keep = _sweeps_keep(self, lidar_line, radius, flip_xy, device)
+        the device.  For carrying per-point data (intensity, labels) through the same selection.  `voxel_size`: thinned on
+        that grid after the ego box and the radius (`voxel_keep`)."""
+        keep, n_keep = _sweeps_keep(self, lidar_line, radius, flip_xy, device, voxel_size)
         return keep[:n_keep]
 
     def accumulated(self, device='cuda'):
@@ -434,8 +514,10 @@ def _check_line_and_box(ss, lidar_line):
                            'concatenated cloud, whose length after the ego box is known on the device only')
 
 
-def _sweeps_keep(ss, lidar_line, radius, flip_xy, device):
-    """(lidar-line reduction,) ego box and radius filter of a sweep set -> (keep int32 tensor, n_keep)"""
+def _sweeps_keep(ss, lidar_line, radius, flip_xy, device, voxel_size=None):
+    """(lidar-line reduction,) ego box and radius filter (and voxel thinning) of a sweep set -> (keep int32 tensor, n_keep)"""
+    if voxel_size is not None:
+        _check_voxel_size(voxel_size)
     _check_line_and_box(ss, lidar_line)
     pts, _ = ss._args(device)
     n, pre = ss.n_total, None
@@ -446,19 +528,23 @@ def _sweeps_keep(ss, lidar_line, radius, flip_xy, device):
         pre = torch.from_numpy(idx).to(pts.device)
         n = int(pre.numel())
     if radius is None and ss.ego_box is None:
+        if voxel_size is not None:
+            return _voxel_thin(ss, pre, n, None, voxel_size, device)
         return (pre if pre is not None else torch.arange(n, dtype=torch.int32, device=pts.device)), n
     # an all-identity set stays float32 in the reference, where numpy compares with float32(radius)
     r = radius if radius is None or ss.K > 1 else float(np.float32(radius))
     keep, count = ss._filter(device, pre, n, flip_xy, r)
+    if voxel_size is not None:                           # the filter's count stays on the device: the thinning reads it there
+        return _voxel_thin(ss, keep, n, count, voxel_size, device)
     return keep, int(count.item())                       # one host read per sample: the caller's branch depends on it
 
 
-def _preproc_sweeps(ss, gts, num_points, lidar_line, radius, sampled_indices, flip_xy, device, want_float64):
+def _preproc_sweeps(ss, gts, num_points, lidar_line, radius, sampled_indices, flip_xy, device, want_float64, voxel_size=None):
     """`preproc_pcd` over a sweep set: the same chain on the concatenated index space (efgh_prep_sweeps_*)"""
-    keep, n_keep = _sweeps_keep(ss, lidar_line, radius, flip_xy, device)
+    keep, n_keep = _sweeps_keep(ss, lidar_line, radius, flip_xy, device, voxel_size)
     pts, a = ss._args(device)
     sel, n_sel = _subsample(n_keep, num_points, sampled_indices, pts.device)
-    T = torch.from_numpy(np.ascontiguousarray(np.asarray(gts['rand_init_l'], np.float64)[:3, :])).to(pts.device)
+    T = _upload_T(gts, pts.device, wait=voxel_size is None)
     out32 = torch.empty((3, num_points), dtype=torch.float32, device=pts.device)
     out64 = torch.empty((3, num_points), dtype=torch.float64, device=pts.device) if want_float64 else None
     _C.check(_L().efgh_prep_sweeps_gather_transform(*a, ptr(keep), c_int32(n_keep), ptr(sel), c_int32(n_sel),
@@ -468,18 +554,23 @@ def _preproc_sweeps(ss, gts, num_points, lidar_line, radius, sampled_indices, fl
 
 
 def preproc_pcd(pcd, gts, num_points, lidar_line=None, radius=50., sampled_indices=None, flip_xy=False, device='cuda',
-                want_float64=False):
+                want_float64=False, voxel_size=None):
     """loader_utils.py:160-202: (lidar-line reduction,) radius filter, sub-sample without replacement (or zero pad),
     homogeneous transform by `rand_init_l` in float64.  Returns (3, num_points) float32 on the device
-    (the reference's float64 rows are cast by the training loop, iterater.py:29)."""
+    (the reference's float64 rows are cast by the training loop, iterater.py:29).
+    `voxel_size` (not in the reference; None: off, and nothing runs differently): after the radius filter, keep the first row of
+    every occupied voxel of that edge (`voxel_keep`), then sub-sample or zero-pad what is left."""
+    if voxel_size is not None:
+        _check_voxel_size(voxel_size)
     if isinstance(pcd, SweepSet):
-        return _preproc_sweeps(pcd, gts, num_points, lidar_line, radius, sampled_indices, flip_xy, device, want_float64)
+        return _preproc_sweeps(pcd, gts, num_points, lidar_line, radius, sampled_indices, flip_xy, device, want_float64,
+                               voxel_size)
     p = torch.as_tensor(np.ascontiguousarray(pcd, dtype=np.float32)) if not torch.is_tensor(pcd) else pcd
     p = p.to(device=device, dtype=torch.float32).contiguous()
     _C.require_cuda(p)
     if p.dim() == 2 and p.shape[1] == 3:                 # [n, 3] rows (the KITTI-raw and nuScenes readers): read at stride 3
         return _preproc_sweeps(SweepSet([p]), gts, num_points, lidar_line, radius, sampled_indices, flip_xy, device,
-                               want_float64)
+                               want_float64, voxel_size)
     assert p.dim() == 2 and p.shape[1] == 4
     n_src = p.shape[0]
     pre = None
@@ -493,12 +584,17 @@ def preproc_pcd(pcd, gts, num_points, lidar_line=None, radius=50., sampled_indic
         scratch = torch.empty(_L().efgh_prep_filter_blocks(c_int32(n)), dtype=torch.int32, device=p.device)
         _C.check(_L().efgh_prep_radius_filter(ptr(p), ptr(pre), c_int32(n), c_int32(1 if flip_xy else 0), c_float(radius),
                                               ptr(scratch), ptr(keep), ptr(count), _st()))
-        n_keep = int(count.item())                       # one host read per sample: the branch below depends on it
+        if voxel_size is not None:                       # the count stays on the device: the thinning reads it there
+            keep, n_keep = _voxel_thin(p, keep, n, count, voxel_size, p.device)
+        else:
+            n_keep = int(count.item())                   # one host read per sample: the branch below depends on it
+    elif voxel_size is not None:
+        keep, n_keep = _voxel_thin(p, pre, n, None, voxel_size, p.device)
     else:
         keep = pre if pre is not None else torch.arange(n, dtype=torch.int32, device=p.device)
         n_keep = n
     sel, n_sel = _subsample(n_keep, num_points, sampled_indices, p.device)
-    T = torch.from_numpy(np.ascontiguousarray(np.asarray(gts['rand_init_l'], np.float64)[:3, :])).to(p.device)
+    T = _upload_T(gts, p.device, wait=voxel_size is None)
     out32 = torch.empty((3, num_points), dtype=torch.float32, device=p.device)
     out64 = torch.empty((3, num_points), dtype=torch.float64, device=p.device) if want_float64 else None
     _C.check(_L().efgh_prep_gather_transform(ptr(p), ptr(keep), ptr(sel), c_int32(n_sel), c_int32(1 if flip_xy else 0),
@@ -518,6 +614,9 @@ class _Process(object):
         self.lidar_line = args['lidar_line'] if self.has_lidar_line else None
         self.num_points = args['num_points']
         self.device = args.get('DEVICE', 'cuda')
+        self.voxel_size = args.get('voxel_size')         # optional (not in the reference): thin on a voxel grid, see preproc_pcd
+        if self.voxel_size is not None:
+            _check_voxel_size(self.voxel_size)
         if args['test'] is False:
             self.l_rot_range = args['dclb']['l_rot_range']
             self.l_trs_range = args['dclb']['l_trs_range']
@@ -534,7 +633,7 @@ class _Process(object):
         gts = preproc_gt(rr, rp, ry, tx, ty, tz, rt, posej_T_posei)
         imgs = preproc_img(img, gts, self.raw_cam_img_size, self.rellis, self.device)
         pc = preproc_pcd(pcd, gts, self.num_points, self.lidar_line, sampled_indices=sampled_indices,
-                         flip_xy=self.rellis, device=self.device)
+                         flip_xy=self.rellis, device=self.device, voxel_size=self.voxel_size)
         gts['img_raw'], gts['img_rot'], gts['img_mask'] = imgs['raw'], imgs['rot'], imgs['img_mask']
         A = np.array([[1, 0, -self.raw_cam_img_size[1] / 2], [0, 1, -self.raw_cam_img_size[0] / 2], [0, 0, 1]])
         gts['cam_T_velo'] = np.linalg.inv(A) @ gts['intrinsic_sensor2'] @ A @ calib @ gts['sensor2_T_sensor1']

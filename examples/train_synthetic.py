@@ -8,6 +8,7 @@ loop of the reference's iterater.py:25-60 with nothing on the CPU between the de
     python examples/train_synthetic.py --iters 5 --ema 0.999                     # validate the live and the averaged weights
     python examples/train_synthetic.py --iters 3 --groups                        # parameter groups: G at a tenth of the rate, no decay on 1-D parameters
     python examples/train_synthetic.py --iters 3 --accumulate-sweeps 2           # 2 neighbouring sweeps on either side, merged on the GPU
+    python examples/train_synthetic.py --iters 3 --accumulate-sweeps 2 --voxel 0.2   # ... thinned on a 0.2 grid before the sub-sampling
 """
 import argparse
 import os
@@ -66,12 +67,17 @@ def main(argv=None):
     ap.add_argument('--accumulate-sweeps', type=int, default=0, metavar='N',
                     help='merge up to N neighbouring LiDAR sweeps on either side into every sample (the loaders\' '
                          'accumulation_frame_num; not to be confused with --accumulate, which accumulates gradients)')
+    ap.add_argument('--voxel', type=float, default=None, metavar='SIZE',
+                    help='thin every cloud on a voxel grid of edge SIZE before it is sub-sampled (first point of a voxel wins, the '
+                         'own sweep first); goes together with --accumulate-sweeps')
     a = ap.parse_args(argv)
     a.skip_nonfinite = a.skip_nonfinite or a.transactional
     raw = tuple(a.raw)
     args = syn.default_args(raw, 'cuda')
     args.update({'lidar_line': None, 'num_points': a.points, 'test': False,
                  'dclb': {'l_rot_range': 1 / 12., 'l_trs_range': 1.0, 'c_rot_range': 1 / 12.}})
+    if a.voxel is not None:
+        args['voxel_size'] = a.voxel
     torch.manual_seed(0)
     model = EFGHBackbone(args).cuda()
     groups = None

@@ -64,7 +64,8 @@ const char *efgh_last_error(void);
  *      efgh_ema_update, efgh_ema_swap (exponential moving average of the flat weights);
  *      efgh_adam_step_groups and the struct efgh_adam_groups (the fused optimizer step with torch.optim's parameter groups);
  *      efgh_prep_sweeps_filter, efgh_prep_sweeps_gather_transform, efgh_prep_sweeps_materialize (multi-sweep accumulation and
- *      stride-3 rows in sample preparation). */
+ *      stride-3 rows in sample preparation);
+ *      efgh_prep_voxel_workspace, efgh_prep_voxel_keep, efgh_prep_sweeps_voxel_keep (thinning on a voxel grid in sample preparation). */
 #define EFGH_ABI_VERSION 4
 int efgh_version(void);
 
@@ -989,6 +990,36 @@ int efgh_prep_sweeps_gather_transform(const float *pts, int32_t stride, const in
 int efgh_prep_sweeps_materialize(const float *pts, int32_t stride, const int32_t *sweep_off, const double *M34,
                                  const int32_t *identity, int32_t K, int32_t n_total, const int32_t *keep_idx, int32_t n,
                                  double *out, void *stream);
+/* Voxel thinning: of the candidate rows j = 0 .. n-1 (keep_in[j], NULL: j; n = min(*n_dev, n_cap) clamped at 0, n_dev NULL: n_cap)
+ * keep the first one of every occupied voxel of edge `voxel`, in candidate order.  It sits between the filters above and the
+ * sub-sampling; n_dev is the filter's count, so nothing is read back in between.
+ *   position   q of efgh_prep_sweeps_* for a sweep set; (double)p for plain rows (pts [n_rows] rows of `stride` 3 or 4 floats,
+ *              stride 4: 16-byte aligned).  Always before the RELLIS sign flip and before rand_init_l.
+ *   index      t = floor(q / voxel) per axis, float64, an IEEE division.
+ *   key        a row is representable when its three t are finite and |t| < 2^20:
+ *              key = (tx + 2^20) | (ty + 2^20) << 21 | (tz + 2^20) << 42   (63 bits: never the all-ones empty marker).
+ *              Any other row (NaN or inf coordinate, index out of range, a source index outside the rows, which is never read) is
+ *              kept, alone, and never merged.
+ *   kept       row j is kept when it is not representable or no row j' < j has its key: first seen wins, so the own sweep wins over
+ *              its neighbours.  The kept set depends on neither the order of insertion, the grid nor the run; the representative is
+ *              an input row (no floating-point atomics, no centroid).
+ *   table      cap = the smallest power of two >= 2 n_cap (at least 2); keys [cap] uint64 and first [cap] uint32, all ones when empty.
+ *              Home slot = mix64(key) & (cap - 1), where
+ *                  mix64(x): x ^= x >> 33; x *= 0xff51afd7ed558ccd; x ^= x >> 33; x *= 0xc4ceb9fe1a85ec53; x ^= x >> 33   (mod 2^64)
+ *              and probing is linear, +1 with wrap, at most cap steps.
+ *   output     keep_out [n_cap] receives the kept source indices, ascending in j; count[0] their number, count[1] != 0 when the
+ *              probe bound was reached (at load <= 0.5 it cannot be; a caller treats it as an error).  keep_out must not overlap
+ *              keep_in, and count must not overlap n_dev.
+ *   workspace  efgh_prep_voxel_workspace(n_cap) bytes, 8-byte aligned (-1 for n outside 0 .. 2^29 - 1); five launches, no host read.
+ * EFGH_E_INVALID with a message, and nothing launched, for: voxel not positive and finite, n_cap < 0 (or >= 2^29, or > the rows
+ * without keep_in), a null or misaligned workspace, null pts / keep_out / count, a stride other than 3 or 4, or a bad sweep set. */
+int64_t efgh_prep_voxel_workspace(int32_t n);
+int efgh_prep_voxel_keep(const float *pts, int32_t stride, int32_t n_rows, const int32_t *keep_in, int32_t n_cap,
+                         const int32_t *n_dev, double voxel, void *workspace, int32_t *keep_out, int32_t *count, void *stream);
+int efgh_prep_sweeps_voxel_keep(const float *pts, int32_t stride, const int32_t *sweep_off, const double *M34,
+                                const int32_t *identity, int32_t K, int32_t n_total, const int32_t *keep_in, int32_t n_cap,
+                                const int32_t *n_dev, double voxel, void *workspace, int32_t *keep_out, int32_t *count,
+                                void *stream);
 
 /* ------------------------------------------------------------------ evaluation metrics --
  * Err.calc_error_odom_np (mode 0: arccos((tr(pred_R^T gt_R)-1)/2) in degrees, |pred_t - gt_t|_2; common/helper.py:198-207)
