@@ -38,6 +38,74 @@ __device__ __forceinline__ uint64_t mix64(uint64_t x) {
     return x;
 }
 
+// rows in use of a buffer of n_cap: the device count where there is one (lattice.hip: the level above's H; prep.hip: the count of the
+// filter in front), clamped to the capacity.  The counts are written by this library's own kernels and are never negative (prep.hip only ever asks
+// `row < rows_of(...)`, for which a negative count would be no rows).
+__device__ __forceinline__ int rows_of(const int *n_dev, int n_cap) {
+    if (!n_dev) return n_cap;
+    const int n = *n_dev;
+    return n < n_cap ? n : n_cap;
+}
+
+// ---- the one block scan (lattice.hip's segment, rank and bucket kernels, prep.hip's k_scan_blocks).  Exclusive prefix over the NT
+// threads of a block, one value each; *total = block sum, in every thread.  Shuffles inside the wave, the wave sums through LDS: two
+// barriers, the second so that the next call may overwrite the sums.
+template <int NT>
+__device__ __forceinline__ int block_exclusive_scan(int v, int *total) {
+    __shared__ int wsum[NT / 64];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    int x = v;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) { const int y = __shfl_up(x, o); if (lane >= o) x += y; }
+    if (lane == 63) wsum[w] = x;
+    __syncthreads();
+    int base = 0, tot = 0;
+#pragma unroll
+    for (int i = 0; i < NT / 64; ++i) { if (i < w) base += wsum[i]; tot += wsum[i]; }
+    __syncthreads();
+    *total = tot;
+    return base + x - v;
+}
+
+// two scans in one pass (lattice.hip: list length and occupancy of a slot)
+template <int NT>
+__device__ __forceinline__ int2 block_exclusive_scan(int2 v, int2 *total) {
+    __shared__ int2 wsum2[NT / 64];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    int2 x = v;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const int y0 = __shfl_up(x.x, o), y1 = __shfl_up(x.y, o);
+        if (lane >= o) { x.x += y0; x.y += y1; }
+    }
+    if (lane == 63) wsum2[w] = x;
+    __syncthreads();
+    int2 base = make_int2(0, 0), tot = make_int2(0, 0);
+#pragma unroll
+    for (int i = 0; i < NT / 64; ++i) {
+        if (i < w) { base.x += wsum2[i].x; base.y += wsum2[i].y; }
+        tot.x += wsum2[i].x; tot.y += wsum2[i].y;
+    }
+    __syncthreads();
+    *total = tot;
+    return make_int2(base.x + x.x - v.x, base.y + x.y - v.y);
+}
+
+// a SINGLE block of NT threads: a[0 .. n) <- its exclusive prefix, NT elements at a time with the running sum carried in a register
+// (every thread gets every chunk's total); returns the sum of all n, in every thread.  T is int or int2.
+template <int NT, class T>
+__device__ __forceinline__ T block_scan_in_place(T *__restrict__ a, int n) {
+    T carry = T();
+    for (int s = 0; s < n; s += NT) {
+        const int i = s + threadIdx.x;
+        T tot;
+        const T ex = block_exclusive_scan<NT>(i < n ? a[i] : T(), &tot);
+        if (i < n) a[i] = carry + ex;
+        carry = carry + tot;
+    }
+    return carry;
+}
+
 // Adam's bias corrections of a step count the HOST knows (adam.hip's entry points, and guard.hip's when no step can be skipped; a
 // count that lives on the device is corrected there, by k_guard_decide): fp32 throughout
 struct efgh_bias_corr { float bc1, bc2_sqrt; };         // 1 - beta1^step, sqrt(1 - beta2^step)

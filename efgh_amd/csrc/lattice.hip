@@ -8,6 +8,9 @@
 //   build_it (ii) blur neighbours        transforms.py:168-180 -> k_neighbors
 // The sequential "first seen" numbering is restated as: index(v) = rank of v among the distinct key integers ordered by
 // their smallest flat position f = 4*p + rem.
+// Every prefix sum here is common.h's block_exclusive_scan<NT> (int, and int2 for two sums at once); the single-block kernels that
+// turn block sums into their prefix (k_seg_scan, k_scan_sums) are block_scan_in_place with their own last line.  rows_of (the
+// device count clamped to the capacity) lives there too.
 //
 // What is different from a line-by-line GPU version (round 1), and why (tools/probes/probe_atomics.hip, profiles/r02_probes.txt):
 // every global atomic on gfx950 executes at the memory side at ~26 G operations/s chip-wide whatever its scope, width or
@@ -59,12 +62,6 @@ __device__ __forceinline__ int64_t key2int(const int k[4], const int *mm) {
     }
     res += (int64_t)k[3] - mm[3];
     return res;
-}
-
-__device__ __forceinline__ int n_of(const int *n_dev, int n_cap) {
-    if (!n_dev) return n_cap;
-    int n = *n_dev;
-    return n < n_cap ? n : n_cap;
 }
 
 __device__ __forceinline__ int sample_of(const int *sid, int pps, int p) { return sid ? sid[p] : p / pps; }
@@ -180,7 +177,7 @@ __global__ void __launch_bounds__(TPB)
 k_point_keys(const float *__restrict__ pts, int64_t cstride, const int *__restrict__ n_dev, int n_cap, float scale32,
              float std32, float4 *__restrict__ bary, float4 *__restrict__ emg, int *__restrict__ mm,
              int *__restrict__ part, const int *__restrict__ sid, int pps) {
-    const int n = n_of(n_dev, n_cap);
+    const int n = rows_of(n_dev, n_cap);
     const int p = blockIdx.x * TPB + threadIdx.x;
     const int wave = p >> 6, lane = threadIdx.x & 63;
     if ((p & ~63) >= n) {                       // wave past the end: an empty record
@@ -273,7 +270,7 @@ k_insert(const float *__restrict__ pts, int64_t cstride, const int *__restrict__
          float std32, const int *__restrict__ mm, unsigned long long *__restrict__ hkeys, int *__restrict__ cnt,
          int64_t hmask, int4 *__restrict__ slot, int4 *__restrict__ rnk, const int *__restrict__ sid, int pps,
          int nsamples, int *__restrict__ info) {
-    const int n = n_of(n_dev, n_cap);
+    const int n = rows_of(n_dev, n_cap);
     const int p = blockIdx.x * TPB + threadIdx.x;
     if (p >= n) return;
     PointKeys pk;
@@ -328,45 +325,10 @@ k_seg_count(const int4 *__restrict__ cnt4, int2 *__restrict__ bsum2) {
     }
 }
 
-__device__ __forceinline__ int2 block_exclusive_scan2(int2 v, int2 *total) {
-    __shared__ int2 wsum2[TPB / 64];
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    int2 x = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int y0 = __shfl_up(x.x, o), y1 = __shfl_up(x.y, o);
-        if (lane >= o) { x.x += y0; x.y += y1; }
-    }
-    if (lane == 63) wsum2[w] = x;
-    __syncthreads();
-    int2 base = make_int2(0, 0), tot = make_int2(0, 0);
-#pragma unroll
-    for (int i = 0; i < TPB / 64; ++i) {
-        if (i < w) { base.x += wsum2[i].x; base.y += wsum2[i].y; }
-        tot.x += wsum2[i].x; tot.y += wsum2[i].y;
-    }
-    __syncthreads();
-    *total = tot;
-    return make_int2(base.x + x.x - v.x, base.y + x.y - v.y);
-}
-
 __global__ void __launch_bounds__(TPB)
 k_seg_scan(int2 *__restrict__ bsum2, int nb, int *__restrict__ n_occ) {
-    __shared__ int2 carry_s;
-    if (threadIdx.x == 0) carry_s = make_int2(0, 0);
-    __syncthreads();
-    for (int s = 0; s < nb; s += TPB) {
-        const int i = s + threadIdx.x;
-        const int2 v = i < nb ? bsum2[i] : make_int2(0, 0);
-        int2 tot;
-        const int2 ex = block_exclusive_scan2(v, &tot);
-        const int2 carry = carry_s;
-        if (i < nb) bsum2[i] = make_int2(carry.x + ex.x, carry.y + ex.y);
-        __syncthreads();
-        if (threadIdx.x == 0) carry_s = make_int2(carry.x + tot.x, carry.y + tot.y);
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) *n_occ = carry_s.y;
+    const int2 tot = block_scan_in_place<TPB>(bsum2, nb);
+    if (threadIdx.x == 0) *n_occ = tot.y;
 }
 
 // occ[k] = (slot, start, length) of the k-th occupied slot
@@ -379,7 +341,7 @@ k_seg_assign(const int4 *__restrict__ cnt4, const int2 *__restrict__ bsum2, int4
         const int4 c = cnt4[i];
         const int2 mine = make_int2(c.x + c.y + c.z + c.w, (c.x > 0) + (c.y > 0) + (c.z > 0) + (c.w > 0));
         int2 tot;
-        const int2 ex = block_exclusive_scan2(mine, &tot);
+        const int2 ex = block_exclusive_scan<TPB>(mine, &tot);
         int st = run.x + ex.x, k = run.y + ex.y;
         run.x += tot.x; run.y += tot.y;
         const int s0 = (int)(i * 4);
@@ -399,7 +361,7 @@ k_seg_assign(const int4 *__restrict__ cnt4, const int2 *__restrict__ bsum2, int4
 __global__ void __launch_bounds__(TPB)
 k_place(const int4 *__restrict__ slot, const int4 *__restrict__ rnk, const int *__restrict__ n_dev, int n_cap,
         const int *__restrict__ sstart, int *__restrict__ list0) {
-    const int n = n_of(n_dev, n_cap);
+    const int n = rows_of(n_dev, n_cap);
     const int p = blockIdx.x * TPB + threadIdx.x;
     if (p >= n) return;
     const int4 s = slot[p], r = rnk[p];
@@ -456,53 +418,25 @@ k_sortmin(const int4 *__restrict__ occ, const int *__restrict__ n_occ, const int
     }
 }
 
-__device__ __forceinline__ int block_exclusive_scan(int v, int *total) {
-    // 256 threads, one value each -> exclusive prefix; *total = block sum
-    __shared__ int wsum[TPB / 64];
-    int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    int x = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) { int y = __shfl_up(x, o); if (lane >= o) x += y; }
-    if (lane == 63) wsum[w] = x;
-    __syncthreads();
-    int base = 0, tot = 0;
-#pragma unroll
-    for (int i = 0; i < TPB / 64; ++i) { if (i < w) base += wsum[i]; tot += wsum[i]; }
-    __syncthreads();
-    *total = tot;
-    return base + x - v;
-}
-
 __device__ __forceinline__ int flag_count(unsigned w) { return __popc(w & 0x01010101u); }
 
 // ---- K2e: count first-seen positions per block of 256 points (1024 flat positions) -------------------------
 __global__ void __launch_bounds__(TPB)
 k_flag_count(const unsigned *__restrict__ flags, const int *__restrict__ n_dev, int n_cap, int *__restrict__ bsum) {
-    const int n = n_of(n_dev, n_cap);
+    const int n = rows_of(n_dev, n_cap);
     const int p = blockIdx.x * TPB + threadIdx.x;
     int tot;
-    block_exclusive_scan(p < n ? flag_count(flags[p]) : 0, &tot);
+    block_exclusive_scan<TPB>(p < n ? flag_count(flags[p]) : 0, &tot);
     if (threadIdx.x == 0) bsum[blockIdx.x] = tot;
 }
 
 // ---- K2f: exclusive scan of the block sums (single block), writes H -------------------------
 __global__ void __launch_bounds__(TPB)
 k_scan_sums(int *__restrict__ bsum, int nb, int *__restrict__ info, int h_cap) {
-    __shared__ int carry_s;
-    if (threadIdx.x == 0) carry_s = 0;
-    __syncthreads();
-    for (int s = 0; s < nb; s += TPB) {
-        int i = s + threadIdx.x, v = (i < nb) ? bsum[i] : 0, tot;
-        int ex = block_exclusive_scan(v, &tot);
-        int carry = carry_s;
-        if (i < nb) bsum[i] = carry + ex;
-        __syncthreads();
-        if (threadIdx.x == 0) carry_s = carry + tot;
-        __syncthreads();
-    }
+    const int H = block_scan_in_place<TPB>(bsum, nb);
     if (threadIdx.x == 0) {
-        info[EFGH_LATTICE_INFO_H] = carry_s;
-        if (carry_s > h_cap) atomicOr(&info[EFGH_LATTICE_INFO_ERR], 1);
+        info[EFGH_LATTICE_INFO_H] = H;
+        if (H > h_cap) atomicOr(&info[EFGH_LATTICE_INFO_ERR], 1);
     }
 }
 
@@ -513,11 +447,11 @@ k_assign(const float *__restrict__ pts, int64_t cstride, const int *__restrict__
          const int *__restrict__ cnt, const int *__restrict__ sstart, int *__restrict__ hvals, int4 *__restrict__ vkeys,
          int2 *__restrict__ vseg, float *__restrict__ pts_next, int h_cap, float div32, const int *__restrict__ sid,
          int pps, int *__restrict__ vsid, int *__restrict__ info) {
-    const int n = n_of(n_dev, n_cap);
+    const int n = rows_of(n_dev, n_cap);
     const int p = blockIdx.x * TPB + threadIdx.x;
     const unsigned fw = p < n ? (flags[p] & 0x01010101u) : 0u;
     int tot;
-    int idx = bsum[blockIdx.x] + block_exclusive_scan(__popc(fw), &tot);
+    int idx = bsum[blockIdx.x] + block_exclusive_scan<TPB>(__popc(fw), &tot);
     if (!fw) return;
     PointKeys pk;
     point_keys(pts[p], pts[cstride + p], pts[2 * cstride + p], scale32, std32, pk);
@@ -558,7 +492,7 @@ k_assign(const float *__restrict__ pts, int64_t cstride, const int *__restrict__
 __global__ void __launch_bounds__(TPB)
 k_offsets(const int4 *__restrict__ slot, const int *__restrict__ hvals, const int *__restrict__ n_dev, int n_cap,
           int4 *__restrict__ off) {
-    const int n = n_of(n_dev, n_cap);
+    const int n = rows_of(n_dev, n_cap);
     const int p = blockIdx.x * TPB + threadIdx.x;
     if (p >= n) return;
     const int4 s = slot[p];
@@ -858,7 +792,7 @@ __global__ void __launch_bounds__(TPB)
 k_lat_keys(const float *__restrict__ pts, int64_t cstride, const int *__restrict__ n_dev, int n_cap, float scale32,
            float std32, float4 *__restrict__ bary, float4 *__restrict__ emg, int *__restrict__ part,
            const int *__restrict__ sid, int pps) {
-    const int n = n_of(n_dev, n_cap);
+    const int n = rows_of(n_dev, n_cap);
     const int p = blockIdx.x * TPB + threadIdx.x;
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     int kmin[4] = {INT32_MAX, INT32_MAX, INT32_MAX, INT32_MAX};
@@ -919,7 +853,7 @@ k_lat_minmax(const int *__restrict__ part, const float *__restrict__ pts, int64_
     for (int i = threadIdx.x; i < nsamples * 8; i += MMT) lmm[i] = (i & 7) < 4 ? INT32_MAX : INT32_MIN;
     if (threadIdx.x == 0) nstr = 0;
     __syncthreads();
-    const int n = n_of(n_dev, n_cap);
+    const int n = rows_of(n_dev, n_cap);
     const int nrec = (n + TPB - 1) / TPB;
     {
         // every thread folds a contiguous run of records (almost always one sample) in registers, four loads in flight; a change of
@@ -985,24 +919,6 @@ k_lat_minmax(const int *__restrict__ part, const float *__restrict__ pts, int64_
     for (int i = threadIdx.x; i < nsamples * 8; i += MMT) mm[i] = lmm[i];
 }
 
-// exclusive prefix over the NT threads of a block (NT = 256 or 512), one value each; *total = block sum
-template <int NT>
-__device__ __forceinline__ int block_exclusive_scan_n(int v, int *total) {
-    __shared__ int wsum_n[NT / 64];
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    int x = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) { const int y = __shfl_up(x, o); if (lane >= o) x += y; }
-    if (lane == 63) wsum_n[w] = x;
-    __syncthreads();
-    int base = 0, tot = 0;
-#pragma unroll
-    for (int i = 0; i < NT / 64; ++i) { if (i < w) base += wsum_n[i]; tot += wsum_n[i]; }
-    __syncthreads();
-    *total = tot;
-    return base + x - v;
-}
-
 // ---- tile-local bucket sort of the entries.  A tile = STP * PPT points.
 template <int PPT>
 __global__ void __launch_bounds__(STP)
@@ -1010,7 +926,7 @@ k_lat_scatter(const float *__restrict__ pts, int64_t cstride, const int *__restr
               float std32, const int *__restrict__ mm, const int *__restrict__ sid, int pps, int nsamples, LatPart P,
               int *__restrict__ info) {
     __shared__ int cnt[NBMAX];
-    const int n = n_of(n_dev, n_cap);
+    const int n = rows_of(n_dev, n_cap);
     const int p0 = blockIdx.x * (STP * PPT);
     if (p0 >= n) return;
     for (int b = threadIdx.x; b < P.nb; b += STP) cnt[b] = 0;
@@ -1045,7 +961,7 @@ k_lat_scatter(const float *__restrict__ pts, int64_t cstride, const int *__restr
         int mine = 0;
         for (int q = 0; q < per; ++q) if (b0 + q < P.nb) mine += cnt[b0 + q];
         int tot;
-        int ex = block_exclusive_scan_n<STP>(mine, &tot);
+        int ex = block_exclusive_scan<STP>(mine, &tot);
         int *row = P.toff + (int64_t)blockIdx.x * (P.nb + 1);
         for (int q = 0; q < per; ++q) if (b0 + q < P.nb) {
             const int c = cnt[b0 + q];
@@ -1076,29 +992,6 @@ k_lat_scatter(const float *__restrict__ pts, int64_t cstride, const int *__restr
 
 // ---- one workgroup per bucket: gather its runs into LDS, group the entries by key there.  Nothing is carried in registers
 // across the phases (the kernel is a chain of dependent LDS / memory round trips: what hides them is workgroups per CU).
-template <int NT>
-__device__ __forceinline__ int2 block_exclusive_scan2_n(int2 v, int2 *total) {
-    __shared__ int2 wsum2_n[NT / 64];
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    int2 x = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int y0 = __shfl_up(x.x, o), y1 = __shfl_up(x.y, o);
-        if (lane >= o) { x.x += y0; x.y += y1; }
-    }
-    if (lane == 63) wsum2_n[w] = x;
-    __syncthreads();
-    int2 base = make_int2(0, 0), tot = make_int2(0, 0);
-#pragma unroll
-    for (int i = 0; i < NT / 64; ++i) {
-        if (i < w) { base.x += wsum2_n[i].x; base.y += wsum2_n[i].y; }
-        tot.x += wsum2_n[i].x; tot.y += wsum2_n[i].y;
-    }
-    __syncthreads();
-    *total = tot;
-    return make_int2(base.x + x.x - v.x, base.y + x.y - v.y);
-}
-
 template <int MAXE, int BT, bool BIG>
 __device__ __forceinline__ void
 bucket_body(const LatPart &P, const int b, const int *__restrict__ n_dev, int n_cap, int *__restrict__ list, int *__restrict__ info) {
@@ -1118,7 +1011,7 @@ bucket_body(const LatPart &P, const int b, const int *__restrict__ n_dev, int n_
     int *runpre = lst + NTMAX;                                                    // [NTMAX] arrival position of its head
     unsigned short *rid = reinterpret_cast<unsigned short *>(lst + 2 * NTMAX);    // [MAXE]  run of arrival position i
     static_assert(NTMAX * 8 + MAXE * 2 <= MAXE * 6, "run table must fit the list area");
-    const int n = n_of(n_dev, n_cap);
+    const int n = rows_of(n_dev, n_cap);
     const int ntl = (n + P.tp - 1) / P.tp;                                        // tiles that hold points
     for (int s = threadIdx.x; s < S; s += BT) { tkey[s] = EMPTY; tcnt[s] = 0; }
     for (int i = threadIdx.x; i < MAXE; i += BT) rid[i] = 0;
@@ -1141,7 +1034,7 @@ bucket_body(const LatPart &P, const int b, const int *__restrict__ n_dev, int n_
             mine += c[q];
         }
         int tot;
-        int ex = block_exclusive_scan_n<BT>(mine, &tot);
+        int ex = block_exclusive_scan<BT>(mine, &tot);
 #pragma unroll
         for (int q = 0; q < PER; ++q) {
             const int t = threadIdx.x * PER + q;
@@ -1246,7 +1139,7 @@ bucket_body(const LatPart &P, const int b, const int *__restrict__ n_dev, int n_
         for (int q = 0; q < per; ++q) if (s0 + q < S) { const int c = tcnt[s0 + q]; mine.x += c; mine.y += c > 0; cmax = max(cmax, c); }
         if (cmax > LONGL) maxc_s = 1;                 // (some list of this bucket needs the sorting network)
         int2 tot;
-        int2 ex = block_exclusive_scan2_n<BT>(mine, &tot);
+        int2 ex = block_exclusive_scan<BT>(mine, &tot);
         for (int q = 0; q < per; ++q) if (s0 + q < S) {
             const int c = tcnt[s0 + q];
             tstart[s0 + q] = ex.x; tgid[s0 + q] = ex.y;
@@ -1367,7 +1260,7 @@ k_lat_rank(LatPart P, int W, int *__restrict__ info, int h_cap) {
 #pragma unroll
     for (int k = 0; k < RWT; ++k) { c[k] = w0 + k < W ? __popc(P.fbits[w0 + k]) : 0; mine += c[k]; }
     int tot;
-    int ex = block_exclusive_scan(mine, &tot);
+    int ex = block_exclusive_scan<TPB>(mine, &tot);
 #pragma unroll
     for (int k = 0; k < RWT; ++k) { if (w0 + k < W) P.wprefix[w0 + k] = ex; ex += c[k]; }
     __shared__ int last_s;
@@ -1387,7 +1280,7 @@ k_lat_rank(LatPart P, int W, int *__restrict__ info, int h_cap) {
         const int i = s + threadIdx.x;
         const int v = i < nb ? __hip_atomic_load(&P.bsum[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0;
         int t2;
-        const int e2 = block_exclusive_scan(v, &t2);
+        const int e2 = block_exclusive_scan<TPB>(v, &t2);
         const int carry = carry_s;
         if (i < nb) P.bsum[i] = carry + e2;
         __syncthreads();
@@ -1469,7 +1362,7 @@ k_lat_nbr(LatPart P, LatGeom G, const int *__restrict__ mm, int *__restrict__ in
         return;
     }
     if ((int)blockIdx.x >= nbr_blocks) {
-        const int n = n_of(n_dev, n_cap);
+        const int n = rows_of(n_dev, n_cap);
         const int p = (blockIdx.x - nbr_blocks) * TPB + threadIdx.x;
         if (p >= n) return;
         const uint4 w4 = reinterpret_cast<const uint4 *>(P.where)[p];

@@ -4,6 +4,7 @@
 // The O(1) geometry (rotation matrix -> 16.16 fixed-point affine coefficients, resample coefficient tables, crop
 // offsets) is computed on the host exactly as Pillow / numpy_utils.py do (efgh_amd/data/prepare.py) and handed in.
 #include "common.h"
+#include <limits.h>
 
 namespace {
 constexpr int TPB = 256;
@@ -100,92 +101,12 @@ __global__ void k_u8_to_f32_chw_pad(const uint8_t *__restrict__ in, int h, int w
     }
 }
 
-// ---- sweep: radius filter (stable compaction), sub-sample gather, mis-calibration transform ---------------
-// flag[i] = -radius <= x < radius && -radius <= y < radius of the (optionally pre-gathered, sign-flipped) point
-__device__ __forceinline__ bool keep_point(const float *p, float sx, float sy, float radius) {
-    const float x = p[0] * sx, y = p[1] * sy;
-    return x >= -radius && x < radius && y >= -radius && y < radius;
-}
-
-__global__ void k_flag_count(const float *__restrict__ pcd, const int *__restrict__ pre, int n, float sx, float sy,
-                             float radius, int *__restrict__ block_count) {
-    __shared__ int cnt;
-    if (threadIdx.x == 0) cnt = 0;
-    __syncthreads();
-    const int i = blockIdx.x * TPB + threadIdx.x;
-    bool k = false;
-    if (i < n) k = keep_point(pcd + 4LL * (pre ? pre[i] : i), sx, sy, radius);
-    const unsigned long long m = __ballot(k);
-    if ((threadIdx.x & 63) == 0) atomicAdd(&cnt, __popcll(m));
-    __syncthreads();
-    if (threadIdx.x == 0) block_count[blockIdx.x] = cnt;
-}
-
-__global__ void k_scan_blocks(int *__restrict__ block_count, int nblocks, int *__restrict__ total) {
-    // single block: exclusive scan of the per-block counts (nblocks is a few thousand at most)
-    __shared__ int carry;
-    __shared__ int buf[TPB];
-    if (threadIdx.x == 0) carry = 0;
-    __syncthreads();
-    for (int base = 0; base < nblocks; base += TPB) {
-        const int i = base + threadIdx.x;
-        const int v = i < nblocks ? block_count[i] : 0;
-        buf[threadIdx.x] = v;
-        __syncthreads();
-        for (int o = 1; o < TPB; o <<= 1) {
-            int t = threadIdx.x >= o ? buf[threadIdx.x - o] : 0;
-            __syncthreads();
-            buf[threadIdx.x] += t;
-            __syncthreads();
-        }
-        if (i < nblocks) block_count[i] = carry + buf[threadIdx.x] - v;
-        __syncthreads();
-        if (threadIdx.x == TPB - 1) carry += buf[TPB - 1];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) *total = carry;
-}
-
-__global__ void k_compact(const float *__restrict__ pcd, const int *__restrict__ pre, int n, float sx, float sy,
-                          float radius, const int *__restrict__ block_off, int *__restrict__ keep_idx) {
-    __shared__ int wave_cnt[TPB / 64];
-    const int i = blockIdx.x * TPB + threadIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int src = i < n ? (pre ? pre[i] : i) : 0;
-    const bool k = i < n && keep_point(pcd + 4LL * src, sx, sy, radius);
-    const unsigned long long m = __ballot(k);
-    if (lane == 0) wave_cnt[wave] = __popcll(m);
-    __syncthreads();
-    int off = block_off[blockIdx.x];
-    for (int q = 0; q < wave; ++q) off += wave_cnt[q];
-    if (k) keep_idx[off + __popcll(m & ((1ull << lane) - 1ull))] = src;
-}
-
-// out[r][j] = (float)(T[r][0]*x + T[r][1]*y + T[r][2]*z + T[r][3]) in float64, for the j-th selected point;
-// columns past the population are the transform of (0,0,0,1) (loader_utils.py:190-199)
-__global__ void k_gather_transform(const float *__restrict__ pcd, const int *__restrict__ keep_idx,
-                                   const int *__restrict__ sel, int n_sel, float sx, float sy, const double *__restrict__ T,
-                                   int num_points, float *__restrict__ out32, double *__restrict__ out64) {
-    const int j = blockIdx.x * TPB + threadIdx.x;
-    if (j >= num_points) return;
-    double x = 0., y = 0., z = 0.;
-    if (j < n_sel) {
-        const int k = sel ? sel[j] : j;
-        const float *p = pcd + 4LL * keep_idx[k];
-        x = (double)(p[0] * sx); y = (double)(p[1] * sy); z = (double)p[2];
-    }
-#pragma unroll
-    for (int r = 0; r < 3; ++r) {
-        // numpy's (4x4)@(4xN) float64 product: a plain left-to-right sum of the four terms
-        const double v = ((T[r * 4] * x + T[r * 4 + 1] * y) + T[r * 4 + 2] * z) + T[r * 4 + 3] * 1.0;
-        if (out32) out32[(long long)r * num_points + j] = (float)v;
-        if (out64) out64[(long long)r * num_points + j] = v;
-    }
-}
-
-// ---- sweep SET: K packed float32 sweeps, each with its own float64 [3][4] transform into the frame of sweep 0 --------
+// ---- point rows: K packed float32 sweeps, each with its own float64 [3][4] transform into the frame of sweep 0 ---------------------
 // (get_accumulated_pc / search_for_accumulation, kitti_odom_loader.py:160-225, rellis3d_loader.py:218-280;
 // accumulate_lidar_points / lidar_frame_accumulation, nusc_loader.py:83-146).  The accumulated float64 cloud is never
 // written: the point kernels index the concatenation 0 .. n_total-1 and compute q = M_k . (p, 1) where they need it.
+// A plain array of rows (the entry points without `sweeps` in their name) is the same struct with K = 0 and no offsets, matrices
+// or flags: the kernels take it as SWEEPS = false and touch none of the three.
 constexpr int SWEEPS_MAX = 64;
 
 struct SweepSet {
@@ -193,12 +114,15 @@ struct SweepSet {
     const int *off;            // [K+1] first row of each sweep, off[K] = n_total
     const double *M;           // [K][3][4]
     const int *ident;          // [K] != 0: the sweep passes through untouched (q = (double)p, no arithmetic)
-    int K, stride, n_total;
+    int K, stride, n_total;    // n_total: the rows an index is checked against (INT_MAX where the entry point is told no row count)
 };
 
-// offsets -> LDS (one block-wide load; the caller synchronises)
+// offsets -> LDS, one block-wide load and a barrier; nothing at all for plain rows
+template <bool SWEEPS>
 __device__ __forceinline__ void stage_offsets(const SweepSet &s, int *lds_off) {
+    if (!SWEEPS) return;
     for (int k = threadIdx.x; k <= s.K; k += TPB) lds_off[k] = s.off[k];
+    __syncthreads();
 }
 
 // the sweep k with off[k] <= i < off[k+1] (empty sweeps have off[k] == off[k+1] and are never returned)
@@ -232,40 +156,35 @@ __device__ __forceinline__ void sweep_position(const SweepSet &s, int k, const R
     for (int r = 0; r < 3; ++r) q[r] = ((m[r * 4] * x + m[r * 4 + 1] * y) + m[r * 4 + 2] * z) + m[r * 4 + 3];
 }
 
-struct SweepPred {
-    double radius, sxy;        // radius <= 0: no radius test; sxy = -1: RELLIS sign flip of x and y before it
-    float ego_x, ego_y;        // ego_x <= 0: no ego box
-};
-
-// not strictly inside the ego box (float32 compare on the RAW point, nusc_loader.py:88-93), and inside the half-open
-// radius box (float64 compare on the transformed position, loader_utils.py:182-187)
-__device__ __forceinline__ bool keep_sweep_point(const SweepSet &s, const SweepPred &f, const int *lds_off, int i) {
-    if (i < 0 || i >= s.n_total) return false;
-    const Raw3 p = load_raw(s, i);
-    if (f.ego_x > 0.f) {
-        const bool inside = (p.x < f.ego_x && p.x > -f.ego_x) && (p.y < f.ego_y && p.y > -f.ego_y);
-        if (inside) return false;
-    }
-    if (f.radius > 0.) {
-        double q[3];
-        sweep_position(s, sweep_of(lds_off, s.K, i), p, q);
-        const double x = q[0] * f.sxy, y = q[1] * f.sxy;
-        return x >= -f.radius && x < f.radius && y >= -f.radius && y < f.radius;
-    }
-    return true;
+// where row i stands: in the frame of sweep 0 for a sweep set, (double)p for plain rows (decided at compile time: no search, no flag)
+template <bool SWEEPS>
+__device__ __forceinline__ void row_position(const SweepSet &s, const int *lds_off, int i, const Raw3 &p, double q[3]) {
+    if (SWEEPS) { sweep_position(s, sweep_of(lds_off, s.K, i), p, q); return; }
+    q[0] = (double)p.x; q[1] = (double)p.y; q[2] = (double)p.z;
 }
 
-__global__ void k_sweeps_flag_count(SweepSet s, SweepPred f, const int *__restrict__ pre, int n,
-                                    int *__restrict__ block_count) {
-    __shared__ int lds_off[SWEEPS_MAX + 1];
-    __shared__ int wave_cnt[TPB / 64];
-    stage_offsets(s, lds_off);
-    __syncthreads();
-    const int i = blockIdx.x * TPB + threadIdx.x;
-    const bool k = i < n && keep_sweep_point(s, f, lds_off, pre ? pre[i] : i);
+// ---- stable compaction: of the candidates j = 0 .. n-1 (n = the device count where there is one, else n_cap) the source rows
+// pre[j] (or j) that a predicate keeps, in order.  Three launches: flags counted per block, the block counts scanned by one block,
+// and the flags taken again to place every kept row at block offset + kept rows of the waves in front + kept lanes below its own.
+// A predicate is a struct passed by value with
+//   void stage(int *lds_off)                           what it wants in LDS before the first flag (ends with a barrier if anything)
+//   bool operator()(const int *lds_off, int j, const int *pre)     the flag of candidate j < n
+// the block's flags: the wave's ballot, and every wave's count in wave_cnt[] behind a barrier
+__device__ __forceinline__ unsigned long long block_ballot(bool k, int *wave_cnt) {
     const unsigned long long m = __ballot(k);
     if ((threadIdx.x & 63) == 0) wave_cnt[threadIdx.x >> 6] = __popcll(m);
     __syncthreads();
+    return m;
+}
+
+template <class Pred>
+__global__ void k_flag_count(Pred f, const int *__restrict__ pre, int n_cap, const int *__restrict__ n_dev,
+                             int *__restrict__ block_count) {
+    __shared__ int lds_off[SWEEPS_MAX + 1];
+    __shared__ int wave_cnt[TPB / 64];
+    f.stage(lds_off);
+    const int j = blockIdx.x * TPB + threadIdx.x;
+    block_ballot(j < rows_of(n_dev, n_cap) && f(lds_off, j, pre), wave_cnt);
     if (threadIdx.x == 0) {
         int c = 0;
         for (int q = 0; q < TPB / 64; ++q) c += wave_cnt[q];
@@ -273,30 +192,72 @@ __global__ void k_sweeps_flag_count(SweepSet s, SweepPred f, const int *__restri
     }
 }
 
-__global__ void k_sweeps_compact(SweepSet s, SweepPred f, const int *__restrict__ pre, int n,
-                                 const int *__restrict__ block_off, int *__restrict__ keep_idx) {
-    __shared__ int lds_off[SWEEPS_MAX + 1];
-    __shared__ int wave_cnt[TPB / 64];
-    stage_offsets(s, lds_off);
-    __syncthreads();
-    const int i = blockIdx.x * TPB + threadIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int src = i < n ? (pre ? pre[i] : i) : 0;
-    const bool k = i < n && keep_sweep_point(s, f, lds_off, src);
-    const unsigned long long m = __ballot(k);
-    if (lane == 0) wave_cnt[wave] = __popcll(m);
-    __syncthreads();
-    int o = block_off[blockIdx.x];
-    for (int q = 0; q < wave; ++q) o += wave_cnt[q];
-    if (k) keep_idx[o + __popcll(m & ((1ull << lane) - 1ull))] = src;      // o + rank < the kept total <= n
+// single block: the per-block counts -> their exclusive prefix, *total = the kept count
+__global__ void k_scan_blocks(int *__restrict__ block_count, int nblocks, int *__restrict__ total) {
+    const int t = block_scan_in_place<TPB>(block_count, nblocks);
+    if (threadIdx.x == 0) *total = t;
 }
 
-// k_gather_transform reading q of the concatenated index keep_idx[sel[j]] instead of a float32 row
-__global__ void k_sweeps_gather_transform(SweepSet s, const int *__restrict__ keep_idx, const int *__restrict__ sel,
-                                          int n_keep, int n_sel, double sxy, const double *__restrict__ T,
-                                          int num_points, float *__restrict__ out32, double *__restrict__ out64) {
+template <class Pred>
+__global__ void k_compact(Pred f, const int *__restrict__ pre, int n_cap, const int *__restrict__ n_dev,
+                          const int *__restrict__ block_off, int *__restrict__ keep_idx) {
     __shared__ int lds_off[SWEEPS_MAX + 1];
-    stage_offsets(s, lds_off);
-    __syncthreads();
+    __shared__ int wave_cnt[TPB / 64];
+    f.stage(lds_off);
+    const int j = blockIdx.x * TPB + threadIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const bool k = j < rows_of(n_dev, n_cap) && f(lds_off, j, pre);
+    const unsigned long long m = block_ballot(k, wave_cnt);
+    int o = block_off[blockIdx.x];
+    for (int q = 0; q < wave; ++q) o += wave_cnt[q];
+    if (k) keep_idx[o + __popcll(m & ((1ull << lane) - 1ull))] = pre ? pre[j] : j;     // o + rank < the kept total <= n_cap
+}
+
+// the box predicate of the radius filters: source row i = pre[j] (or j) is kept when it is NOT strictly inside the ego box (float32
+// compare on the RAW point, nusc_loader.py:88-93) and inside the half-open radius box (float64 compare on the position, sign-flipped
+// by sxy = -1 for RELLIS, loader_utils.py:182-187).  numpy compares plain float32 rows in float32; float64 gives the same flag for
+// every row: a float32 is exactly a double, the product with +-1 is exact, the float32 radius converts exactly, and a comparison with
+// a NaN is false at either width.
+template <bool SWEEPS>
+struct BoxPred {
+    SweepSet s;
+    double radius, sxy;        // radius <= 0: no radius test
+    float ego_x, ego_y;        // ego_x <= 0: no ego box
+    __device__ __forceinline__ void stage(int *lds_off) const { stage_offsets<SWEEPS>(s, lds_off); }
+    __device__ __forceinline__ bool operator()(const int *lds_off, int j, const int *__restrict__ pre) const {
+        const int i = pre ? pre[j] : j;
+        if (i < 0 || i >= s.n_total) return false;
+        const Raw3 p = load_raw(s, i);
+        if (ego_x > 0.f) {
+            const bool inside = (p.x < ego_x && p.x > -ego_x) && (p.y < ego_y && p.y > -ego_y);
+            if (inside) return false;
+        }
+        if (radius > 0.) {
+            double q[3];
+            row_position<SWEEPS>(s, lds_off, i, p, q);
+            const double x = q[0] * sxy, y = q[1] * sxy;
+            return x >= -radius && x < radius && y >= -radius && y < radius;
+        }
+        return true;
+    }
+};
+
+template <bool SWEEPS>
+void launch_filter(const BoxPred<SWEEPS> &f, const int32_t *pre_idx, int32_t n, int32_t *block_scratch, int32_t *keep_idx,
+                   int32_t *count, hipStream_t st) {
+    const int nb = (n + TPB - 1) / TPB;
+    k_flag_count<<<nb, TPB, 0, st>>>(f, pre_idx, n, nullptr, block_scratch);
+    k_scan_blocks<<<1, TPB, 0, st>>>(block_scratch, nb, count);
+    k_compact<<<nb, TPB, 0, st>>>(f, pre_idx, n, nullptr, block_scratch, keep_idx);
+}
+
+// out[r][j] = (float)(T[r][0]*x + T[r][1]*y + T[r][2]*z + T[r][3]) in float64, (x, y, z) the position of source row
+// keep_idx[sel[j]] with x and y times sxy; columns past the population are the transform of (0,0,0,1) (loader_utils.py:190-199)
+template <bool SWEEPS>
+__global__ void k_gather_transform(SweepSet s, const int *__restrict__ keep_idx, const int *__restrict__ sel, int n_keep,
+                                   int n_sel, double sxy, const double *__restrict__ T, int num_points,
+                                   float *__restrict__ out32, double *__restrict__ out64) {
+    __shared__ int lds_off[SWEEPS_MAX + 1];
+    stage_offsets<SWEEPS>(s, lds_off);
     const int j = blockIdx.x * TPB + threadIdx.x;
     if (j >= num_points) return;
     double x = 0., y = 0., z = 0.;
@@ -305,12 +266,13 @@ __global__ void k_sweeps_gather_transform(SweepSet s, const int *__restrict__ ke
         const int i = k >= 0 && k < n_keep ? keep_idx[k] : -1;
         if (i >= 0 && i < s.n_total) {
             double q[3];
-            sweep_position(s, sweep_of(lds_off, s.K, i), load_raw(s, i), q);
+            row_position<SWEEPS>(s, lds_off, i, load_raw(s, i), q);
             x = q[0] * sxy; y = q[1] * sxy; z = q[2];
         }
     }
 #pragma unroll
     for (int r = 0; r < 3; ++r) {
+        // numpy's (4x4)@(4xN) float64 product: a plain left-to-right sum of the four terms
         const double v = ((T[r * 4] * x + T[r * 4 + 1] * y) + T[r * 4 + 2] * z) + T[r * 4 + 3] * 1.0;
         if (out32) out32[(long long)r * num_points + j] = (float)v;
         if (out64) out64[(long long)r * num_points + j] = v;
@@ -320,13 +282,12 @@ __global__ void k_sweeps_gather_transform(SweepSet s, const int *__restrict__ ke
 // the accumulated cloud itself, for the callers that want what get_accumulated_pc returns: out[j] = q of keep_idx[j]
 __global__ void k_sweeps_materialize(SweepSet s, const int *__restrict__ keep_idx, int n, double *__restrict__ out) {
     __shared__ int lds_off[SWEEPS_MAX + 1];
-    stage_offsets(s, lds_off);
-    __syncthreads();
+    stage_offsets<true>(s, lds_off);
     const int j = blockIdx.x * TPB + threadIdx.x;
     if (j >= n) return;
     const int i = keep_idx ? keep_idx[j] : j;
     double q[3] = {0., 0., 0.};
-    if (i >= 0 && i < s.n_total) sweep_position(s, sweep_of(lds_off, s.K, i), load_raw(s, i), q);
+    if (i >= 0 && i < s.n_total) row_position<true>(s, lds_off, i, load_raw(s, i), q);
     double *d = out + 3LL * j;
     d[0] = q[0]; d[1] = q[1]; d[2] = q[2];
 }
@@ -357,8 +318,14 @@ int sweeps_check(const float *pts, int32_t stride, const int32_t *off, const dou
     return EFGH_OK;
 }
 
+// plain [rows][stride] float32 rows as a source.  The radius filter and the gather of plain rows are told no row count, so they have
+// none to check an index against (INT_MAX: every index >= 0 passes, as it always did there)
+SweepSet plain_rows(const float *pts, int stride = 4, int rows = INT_MAX) {
+    return SweepSet{pts, nullptr, nullptr, nullptr, 0, stride, rows};
+}
+
 // ---- voxel thinning: of the candidate rows j = 0 .. n-1 keep the FIRST one of every occupied voxel (stable) ---------------
-// Row j stands at q (sweep_position above for a sweep set, (double)p for plain rows; before the RELLIS flip and before
+// Row j stands at q (row_position above; before the RELLIS flip and before
 // rand_init_l).  Per axis t = floor(q / v) in float64, an IEEE division.  The row is representable when every t is finite and
 // |t| < 2^20; its key is (tx + 2^20) | (ty + 2^20) << 21 | (tz + 2^20) << 42: 63 bits, never the empty marker.  Any other row
 // (NaN, inf, out of range, or a source index outside the rows) is kept alone and takes no part in the table.
@@ -381,19 +348,11 @@ struct VoxelTable {
     unsigned mask;             // cap - 1
 };
 
-// rows in use: the device count where there is one (the count of the filter in front), clamped to the capacity
-__device__ __forceinline__ int rows_of(const int *n_dev, int n_cap) {
-    if (!n_dev) return n_cap;
-    const int n = *n_dev;
-    return n < 0 ? 0 : (n < n_cap ? n : n_cap);
-}
-
 template <bool SWEEPS>
 __device__ __forceinline__ bool voxel_key(const SweepSet &s, const int *lds_off, int i, double v, unsigned long long *key) {
     if (i < 0 || i >= s.n_total) return false;
-    const Raw3 p = load_raw(s, i);
-    double q[3] = {(double)p.x, (double)p.y, (double)p.z};
-    if (SWEEPS) sweep_position(s, sweep_of(lds_off, s.K, i), p, q);
+    double q[3];
+    row_position<SWEEPS>(s, lds_off, i, load_raw(s, i), q);
     unsigned long long k = 0;
 #pragma unroll
     for (int r = 0; r < 3; ++r) {
@@ -416,10 +375,7 @@ template <bool SWEEPS>
 __global__ void k_voxel_insert(SweepSet s, const int *__restrict__ keep_in, int n_cap, const int *__restrict__ n_dev, double v,
                                VoxelTable t, int *__restrict__ count) {
     __shared__ int lds_off[SWEEPS_MAX + 1];
-    if (SWEEPS) {
-        stage_offsets(s, lds_off);
-        __syncthreads();
-    }
+    stage_offsets<SWEEPS>(s, lds_off);
     const int j = blockIdx.x * TPB + threadIdx.x;
     if (j >= rows_of(n_dev, n_cap)) return;
     unsigned long long key;
@@ -440,38 +396,15 @@ __global__ void k_voxel_insert(SweepSet s, const int *__restrict__ keep_in, int 
     if (t.first[found] > (unsigned)j) atomicMin(&t.first[found], (unsigned)j);
 }
 
-__device__ __forceinline__ bool voxel_flag(const VoxelTable &t, int j, int n) {
-    if (j >= n) return false;
-    const int sl = t.slot[j];
-    return sl == VOX_ALONE || t.first[sl] == (unsigned)j;
-}
-
-// k_flag_count / k_compact of the radius filter over the voxel flag (k_scan_blocks runs between them as it is)
-__global__ void k_voxel_flag_count(VoxelTable t, int n_cap, const int *__restrict__ n_dev, int *__restrict__ block_count) {
-    __shared__ int wave_cnt[TPB / 64];
-    const bool k = voxel_flag(t, blockIdx.x * TPB + threadIdx.x, rows_of(n_dev, n_cap));
-    const unsigned long long m = __ballot(k);
-    if ((threadIdx.x & 63) == 0) wave_cnt[threadIdx.x >> 6] = __popcll(m);
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int c = 0;
-        for (int q = 0; q < TPB / 64; ++q) c += wave_cnt[q];
-        block_count[blockIdx.x] = c;
+// the voxel predicate of the stable compaction above: candidate j is kept alone, or is the first of its voxel
+struct VoxelPred {
+    VoxelTable t;
+    __device__ __forceinline__ void stage(int *) const {}
+    __device__ __forceinline__ bool operator()(const int *, int j, const int *) const {
+        const int sl = t.slot[j];
+        return sl == VOX_ALONE || t.first[sl] == (unsigned)j;
     }
-}
-
-__global__ void k_voxel_compact(VoxelTable t, const int *__restrict__ keep_in, int n_cap, const int *__restrict__ n_dev,
-                                const int *__restrict__ block_off, int *__restrict__ keep_out) {
-    __shared__ int wave_cnt[TPB / 64];
-    const int j = blockIdx.x * TPB + threadIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const bool k = voxel_flag(t, j, rows_of(n_dev, n_cap));
-    const unsigned long long m = __ballot(k);
-    if (lane == 0) wave_cnt[wave] = __popcll(m);
-    __syncthreads();
-    int o = block_off[blockIdx.x];
-    for (int q = 0; q < wave; ++q) o += wave_cnt[q];
-    if (k) keep_out[o + __popcll(m & ((1ull << lane) - 1ull))] = keep_in ? keep_in[j] : j;   // o + rank <= j < n_cap
-}
+};
 
 long long voxel_capacity(long long n) {
     long long cap = 2;
@@ -514,9 +447,9 @@ int voxel_keep(const SweepSet &s, const int32_t *keep_in, int32_t n_cap, const i
     if (n_cap > 0) {
         const int nb = (n_cap + TPB - 1) / TPB;
         k_voxel_insert<SWEEPS><<<nb, TPB, 0, st>>>(s, keep_in, n_cap, n_dev, voxel, t, count);
-        k_voxel_flag_count<<<nb, TPB, 0, st>>>(t, n_cap, n_dev, blocks);
+        k_flag_count<<<nb, TPB, 0, st>>>(VoxelPred{t}, keep_in, n_cap, n_dev, blocks);
         k_scan_blocks<<<1, TPB, 0, st>>>(blocks, nb, count);
-        k_voxel_compact<<<nb, TPB, 0, st>>>(t, keep_in, n_cap, n_dev, blocks, keep_out);
+        k_compact<<<nb, TPB, 0, st>>>(VoxelPred{t}, keep_in, n_cap, n_dev, blocks, keep_out);
     }
     EFGH_CHECK_LAUNCH();
     return EFGH_OK;
@@ -574,11 +507,8 @@ extern "C" int efgh_prep_radius_filter(const float *pcd, const int32_t *pre_idx,
                                        void *stream) {
     hipStream_t st = (hipStream_t)stream;
     EFGH_CHECK_ARG(pcd && block_scratch && keep_idx && count && n > 0 && radius > 0.f);
-    const float s = flip_xy ? -1.f : 1.f;
-    const int nb = (n + TPB - 1) / TPB;
-    k_flag_count<<<nb, TPB, 0, st>>>(pcd, pre_idx, n, s, s, radius, block_scratch);
-    k_scan_blocks<<<1, TPB, 0, st>>>(block_scratch, nb, count);
-    k_compact<<<nb, TPB, 0, st>>>(pcd, pre_idx, n, s, s, radius, block_scratch, keep_idx);
+    launch_filter(BoxPred<false>{plain_rows(pcd), (double)radius, flip_xy ? -1. : 1., 0.f, 0.f}, pre_idx, n, block_scratch,
+                  keep_idx, count, st);
     EFGH_CHECK_LAUNCH();
     return EFGH_OK;
 }
@@ -587,9 +517,8 @@ extern "C" int efgh_prep_gather_transform(const float *pcd, const int32_t *keep_
                                           int32_t flip_xy, const double *T34, int32_t num_points, float *out32,
                                           double *out64, void *stream) {
     EFGH_CHECK_ARG(pcd && keep_idx && T34 && (out32 || out64) && num_points > 0 && n_sel >= 0 && n_sel <= num_points);
-    const float s = flip_xy ? -1.f : 1.f;
-    k_gather_transform<<<cdiv(num_points, TPB), TPB, 0, (hipStream_t)stream>>>(pcd, keep_idx, sel, n_sel, s, s, T34,
-                                                                             num_points, out32, out64);
+    k_gather_transform<false><<<cdiv(num_points, TPB), TPB, 0, (hipStream_t)stream>>>(
+        plain_rows(pcd), keep_idx, sel, INT_MAX, n_sel, flip_xy ? -1. : 1., T34, num_points, out32, out64);
     EFGH_CHECK_LAUNCH();
     return EFGH_OK;
 }
@@ -604,12 +533,9 @@ extern "C" int efgh_prep_sweeps_filter(const float *pts, int32_t stride, const i
     EFGH_CHECK_ARG(block_scratch && keep_idx && count && n > 0 && n < (1 << 29) && (pre_idx || n == n_total));
     EFGH_CHECK_ARG((radius > 0. || ego_x_half > 0.f) && (ego_x_half > 0.f) == (ego_y_half > 0.f));
     const SweepSet s{pts, sweep_off, M34, identity, K, stride, n_total};
-    const SweepPred f{radius > 0. ? radius : 0., flip_xy ? -1. : 1., ego_x_half > 0.f ? ego_x_half : 0.f,
-                      ego_y_half > 0.f ? ego_y_half : 0.f};
-    const int nb = (n + TPB - 1) / TPB;
-    k_sweeps_flag_count<<<nb, TPB, 0, st>>>(s, f, pre_idx, n, block_scratch);
-    k_scan_blocks<<<1, TPB, 0, st>>>(block_scratch, nb, count);
-    k_sweeps_compact<<<nb, TPB, 0, st>>>(s, f, pre_idx, n, block_scratch, keep_idx);
+    launch_filter(BoxPred<true>{s, radius > 0. ? radius : 0., flip_xy ? -1. : 1., ego_x_half > 0.f ? ego_x_half : 0.f,
+                                ego_y_half > 0.f ? ego_y_half : 0.f},
+                  pre_idx, n, block_scratch, keep_idx, count, st);
     EFGH_CHECK_LAUNCH();
     return EFGH_OK;
 }
@@ -624,7 +550,7 @@ extern "C" int efgh_prep_sweeps_gather_transform(const float *pts, int32_t strid
     EFGH_CHECK_ARG(keep_idx && T34 && (out32 || out64) && num_points > 0 && n_keep >= 0 && n_sel >= 0 &&
                    n_sel <= num_points && (sel || n_sel <= n_keep));
     const SweepSet s{pts, sweep_off, M34, identity, K, stride, n_total};
-    k_sweeps_gather_transform<<<cdiv(num_points, TPB), TPB, 0, (hipStream_t)stream>>>(
+    k_gather_transform<true><<<cdiv(num_points, TPB), TPB, 0, (hipStream_t)stream>>>(
         s, keep_idx, sel, n_keep, n_sel, flip_xy ? -1. : 1., T34, num_points, out32, out64);
     EFGH_CHECK_LAUNCH();
     return EFGH_OK;
@@ -658,8 +584,7 @@ extern "C" int efgh_prep_voxel_keep(const float *pts, int32_t stride, int32_t n_
         efgh_set_error("voxel thinning: row stride %d, supported are 3 and 4 floats (stride 4: 16-byte aligned)", (int)stride);
         return EFGH_E_INVALID;
     }
-    const SweepSet s{pts, nullptr, nullptr, nullptr, 0, stride, n_rows};
-    return voxel_keep<false>(s, keep_in, n_cap, n_dev, voxel, workspace, keep_out, count, (hipStream_t)stream);
+    return voxel_keep<false>(plain_rows(pts, stride, n_rows), keep_in, n_cap, n_dev, voxel, workspace, keep_out, count, (hipStream_t)stream);
 }
 
 extern "C" int efgh_prep_sweeps_voxel_keep(const float *pts, int32_t stride, const int32_t *sweep_off, const double *M34,

@@ -279,25 +279,38 @@ def _upload_T(gts, device, wait=True):
     return T.to(device) if wait else T.pin_memory().to(device, non_blocking=True)
 
 
-def _voxel_thin(src, keep, n, n_dev, voxel_size, device):
+class _Rows(object):
+    """What the point chain runs over, for the three steps that read points: a SweepSet, or a resident [rows, 3 | 4] float32 tensor.
+    `pts` the points on the device, `rows` their number, `set` the SweepSet or None, and per step (filter, thin, gather) the name of the
+    entry point with the C arguments that describe the points to it."""
+
+    def __init__(self, src, device=None):
+        if isinstance(src, SweepSet):
+            self.set, self.rows = src, src.n_total
+            self.pts, a = src._args(device)
+            self.filter, self.thin, self.gather = (('efgh_prep_sweeps_' + step, a) for step in ('filter', 'voxel_keep', 'gather_transform'))
+        else:
+            self.set, self.pts, self.rows = None, src, int(src.shape[0])
+            self.filter, self.gather = ('efgh_prep_radius_filter', (ptr(src),)), ('efgh_prep_gather_transform', (ptr(src),))
+            self.thin = ('efgh_prep_voxel_keep', (ptr(src), c_int32(int(src.shape[1])), c_int32(self.rows)))
+        self.device = self.pts.device
+
+    def call(self, step, *args):
+        name, lead = step
+        _C.check(getattr(_L(), name)(*lead, *args, _st()))
+
+
+def _voxel_thin(src, keep, n, n_dev, voxel_size):
     """of the candidates keep[0 .. n) (None: rows 0 .. n-1; `n_dev`: their count on the device, None: n) the first row of every
-    occupied voxel, in order -> (int32 tensor, count).  `src` is a SweepSet or a resident [rows, 3 | 4] float32 tensor."""
+    occupied voxel, in order -> (int32 tensor, count).  `src` is a _Rows."""
     v = _check_voxel_size(voxel_size)
-    L = _L()
-    if isinstance(src, SweepSet):
-        pts, a = src._args(device)
-        fn = L.efgh_prep_sweeps_voxel_keep
-    else:
-        pts = src
-        a = (ptr(pts), c_int32(int(pts.shape[1])), c_int32(int(pts.shape[0])))
-        fn = L.efgh_prep_voxel_keep
-    nbytes = L.efgh_prep_voxel_workspace(c_int32(n))
+    nbytes = _L().efgh_prep_voxel_workspace(c_int32(n))
     if nbytes < 0:
         raise _C.EfghError('voxel thinning: %d candidate rows, supported are fewer than 2^29' % n)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=pts.device)
-    out = torch.empty(n, dtype=torch.int32, device=pts.device)
-    counts = torch.empty(2, dtype=torch.int32, device=pts.device)
-    _C.check(fn(*a, ptr(keep), c_int32(n), ptr(n_dev), ctypes.c_double(v), ptr(ws), ptr(out), ptr(counts), _st()))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=src.device)
+    out = torch.empty(n, dtype=torch.int32, device=src.device)
+    counts = torch.empty(2, dtype=torch.int32, device=src.device)
+    src.call(src.thin, ptr(keep), c_int32(n), ptr(n_dev), ctypes.c_double(v), ptr(ws), ptr(out), ptr(counts))
     n_keep, exhausted = _read_counts(counts)
     if exhausted:
         raise _C.EfghError('voxel thinning: the hash table of %d candidate rows ran out of slots (a bug: it is sized at load <= 0.5)' % n)
@@ -312,24 +325,24 @@ def voxel_keep(points, voxel_size, keep=None, device='cuda'):
     `SweepSet.kept_indices()`).  The representative is an input row, so per-point data can be carried through the indices."""
     _check_voxel_size(voxel_size)
     if isinstance(points, SweepSet):
-        src, rows = points, points.n_total
-        dev = points._args(device)[0].device
+        src = _Rows(points, device)
     else:
         p = torch.as_tensor(np.ascontiguousarray(points, dtype=np.float32)) if not torch.is_tensor(points) else points
         if p.dim() != 2 or p.shape[1] not in (3, 4) or p.shape[0] < 1:
             raise _C.EfghError('voxel_keep: points has shape %s, expected [n, 3] or [n, 4] with n >= 1' % (tuple(p.shape),))
-        src = p.to(device=device, dtype=torch.float32).contiguous()
-        _C.require_cuda(src)
-        rows, dev = int(src.shape[0]), src.device
+        p = p.to(device=device, dtype=torch.float32).contiguous()
+        _C.require_cuda(p)
+        src = _Rows(p)
+    rows = src.rows
     if keep is not None:
         keep = torch.as_tensor(np.asarray(keep)) if not torch.is_tensor(keep) else keep
         if keep.dim() != 1 or keep.dtype in (torch.float16, torch.float32, torch.float64, torch.bool):
             raise _C.EfghError('voxel_keep: keep is a 1-D integer index list, got %s of shape %s' % (keep.dtype, tuple(keep.shape)))
-        keep = keep.to(device=dev, dtype=torch.int32).contiguous()
+        keep = keep.to(device=src.device, dtype=torch.int32).contiguous()
         rows = int(keep.numel())
         if rows == 0:
             return keep
-    out, n_keep = _voxel_thin(src, keep, rows, None, voxel_size, dev)
+    out, n_keep = _voxel_thin(src, keep, rows, None, voxel_size)
     return out[:n_keep]
 
 
@@ -475,23 +488,11 @@ class SweepSet(object):
         pts, _, off, M, ident = self._stage(device)
         return pts, (ptr(pts), c_int32(self.stride), off, M, ident, c_int32(self.K), c_int32(self.n_total))
 
-    def _filter(self, device, pre, n, flip_xy, radius):
-        """stable compaction of the n candidates by ego box and radius -> (keep [n] int32, count [1] int32)"""
-        pts, a = self._args(device)
-        keep = torch.empty(n, dtype=torch.int32, device=pts.device)
-        count = torch.zeros(1, dtype=torch.int32, device=pts.device)
-        scratch = torch.empty(_L().efgh_prep_filter_blocks(c_int32(n)), dtype=torch.int32, device=pts.device)
-        ex, ey = self.ego_box if self.ego_box is not None else (0., 0.)
-        _C.check(_L().efgh_prep_sweeps_filter(*a, ptr(pre), c_int32(n), c_int32(1 if flip_xy else 0),
-                                              ctypes.c_double(0. if radius is None else radius), c_float(ex), c_float(ey),
-                                              ptr(scratch), ptr(keep), ptr(count), _st()))
-        return keep, count
-
     def kept_indices(self, radius=50., lidar_line=None, flip_xy=False, device='cuda', voxel_size=None):
         """rows of the concatenation (own sweep first, before the ego box) that `preproc_pcd` keeps, in its order: int32 on
         the device.  For carrying per-point data (intensity, labels) through the same selection.  `voxel_size`: thinned on
         that grid after the ego box and the radius (`voxel_keep`)."""
-        keep, n_keep = _sweeps_keep(self, lidar_line, radius, flip_xy, device, voxel_size)
+        _, keep, n_keep = _keep_rows(self, device, lidar_line, radius, flip_xy, voxel_size)
         return keep[:n_keep]
 
     def accumulated(self, device='cuda'):
@@ -500,7 +501,7 @@ class SweepSet(object):
         pts, a = self._args(device)
         keep, n = None, self.n_total
         if self.ego_box is not None:
-            keep, count = self._filter(device, None, n, False, None)
+            keep, count = _filter(_Rows(self, device), None, n, False, None)
             n = int(count.item())
         out = torch.empty((n, 3), dtype=torch.float64, device=pts.device)
         if n > 0:
@@ -508,49 +509,49 @@ class SweepSet(object):
         return out
 
 
-def _check_line_and_box(ss, lidar_line):
-    if lidar_line is not None and ss.ego_box is not None:
-        raise _C.EfghError('preproc_pcd: lidar_line with an ego_box is not supported: the line reduction indexes the '
-                           'concatenated cloud, whose length after the ego box is known on the device only')
+def _filter(src, pre, n, flip_xy, radius):
+    """stable compaction of the candidates pre[0 .. n) (None: rows 0 .. n-1) of a _Rows by ego box and radius
+    -> (keep [n] int32, count [1] int32)"""
+    keep = torch.empty(n, dtype=torch.int32, device=src.device)
+    count = torch.zeros(1, dtype=torch.int32, device=src.device)
+    scratch = torch.empty(_L().efgh_prep_filter_blocks(c_int32(n)), dtype=torch.int32, device=src.device)
+    if src.set is None:
+        box = (c_float(radius),)
+    else:
+        ex, ey = src.set.ego_box if src.set.ego_box is not None else (0., 0.)
+        box = (ctypes.c_double(0. if radius is None else radius), c_float(ex), c_float(ey))
+    src.call(src.filter, ptr(pre), c_int32(n), c_int32(1 if flip_xy else 0), *box, ptr(scratch), ptr(keep), ptr(count))
+    return keep, count
 
 
-def _sweeps_keep(ss, lidar_line, radius, flip_xy, device, voxel_size=None):
-    """(lidar-line reduction,) ego box and radius filter (and voxel thinning) of a sweep set -> (keep int32 tensor, n_keep)"""
+def _keep_rows(points, device, lidar_line, radius, flip_xy, voxel_size=None):
+    """(lidar-line reduction,) ego box and radius filter (and voxel thinning) of a SweepSet or a resident [n, 4] tensor
+    -> (its _Rows, keep int32 tensor, n_keep)"""
     if voxel_size is not None:
         _check_voxel_size(voxel_size)
-    _check_line_and_box(ss, lidar_line)
-    pts, _ = ss._args(device)
-    n, pre = ss.n_total, None
+    ego = isinstance(points, SweepSet) and points.ego_box is not None
+    if lidar_line is not None and ego:
+        raise _C.EfghError('preproc_pcd: lidar_line with an ego_box is not supported: the line reduction indexes the '
+                           'concatenated cloud, whose length after the ego box is known on the device only')
+    src = _Rows(points, device)                          # (a sweep set is uploaded here, at its first use)
+    n, keep, count = src.rows, None, None
     if lidar_line is not None:
         idx = lidar_line_indices(n, lidar_line)
         if idx.size == 0:
             raise _C.EfghError('preproc_pcd: lidar_line on %d points leaves none' % n)
-        pre = torch.from_numpy(idx).to(pts.device)
-        n = int(pre.numel())
-    if radius is None and ss.ego_box is None:
-        if voxel_size is not None:
-            return _voxel_thin(ss, pre, n, None, voxel_size, device)
-        return (pre if pre is not None else torch.arange(n, dtype=torch.int32, device=pts.device)), n
-    # an all-identity set stays float32 in the reference, where numpy compares with float32(radius)
-    r = radius if radius is None or ss.K > 1 else float(np.float32(radius))
-    keep, count = ss._filter(device, pre, n, flip_xy, r)
+        keep = torch.from_numpy(idx).to(src.device)
+        n = int(keep.numel())
+    if radius is not None or ego:
+        # float32 rows alone (an array, or an all-identity set) stay float32 in the reference, where numpy compares with float32(radius)
+        r = radius if radius is None or (src.set is not None and src.set.K > 1) else float(np.float32(radius))
+        keep, count = _filter(src, keep, n, flip_xy, r)
     if voxel_size is not None:                           # the filter's count stays on the device: the thinning reads it there
-        return _voxel_thin(ss, keep, n, count, voxel_size, device)
-    return keep, int(count.item())                       # one host read per sample: the caller's branch depends on it
-
-
-def _preproc_sweeps(ss, gts, num_points, lidar_line, radius, sampled_indices, flip_xy, device, want_float64, voxel_size=None):
-    """`preproc_pcd` over a sweep set: the same chain on the concatenated index space (efgh_prep_sweeps_*)"""
-    keep, n_keep = _sweeps_keep(ss, lidar_line, radius, flip_xy, device, voxel_size)
-    pts, a = ss._args(device)
-    sel, n_sel = _subsample(n_keep, num_points, sampled_indices, pts.device)
-    T = _upload_T(gts, pts.device, wait=voxel_size is None)
-    out32 = torch.empty((3, num_points), dtype=torch.float32, device=pts.device)
-    out64 = torch.empty((3, num_points), dtype=torch.float64, device=pts.device) if want_float64 else None
-    _C.check(_L().efgh_prep_sweeps_gather_transform(*a, ptr(keep), c_int32(n_keep), ptr(sel), c_int32(n_sel),
-                                                    c_int32(1 if flip_xy else 0), ptr(T), c_int32(num_points), ptr(out32),
-                                                    ptr(out64), _st()))
-    return (out32, out64) if want_float64 else out32
+        keep, n = _voxel_thin(src, keep, n, count, voxel_size)
+    elif count is not None:
+        n = int(count.item())                            # one host read per sample: the caller's branch depends on it
+    elif keep is None:
+        keep = torch.arange(n, dtype=torch.int32, device=src.device)
+    return src, keep, n
 
 
 def preproc_pcd(pcd, gts, num_points, lidar_line=None, radius=50., sampled_indices=None, flip_xy=False, device='cuda',
@@ -558,47 +559,26 @@ def preproc_pcd(pcd, gts, num_points, lidar_line=None, radius=50., sampled_indic
     """loader_utils.py:160-202: (lidar-line reduction,) radius filter, sub-sample without replacement (or zero pad),
     homogeneous transform by `rand_init_l` in float64.  Returns (3, num_points) float32 on the device
     (the reference's float64 rows are cast by the training loop, iterater.py:29).
+    `pcd` is a SweepSet (the chain runs on the concatenated index space, efgh_prep_sweeps_*) or an array or tensor of [n, 4] rows
+    (efgh_prep_radius_filter / efgh_prep_gather_transform) or [n, 3] rows (the KITTI-raw and nuScenes readers: a SweepSet of one).
     `voxel_size` (not in the reference; None: off, and nothing runs differently): after the radius filter, keep the first row of
     every occupied voxel of that edge (`voxel_keep`), then sub-sample or zero-pad what is left."""
     if voxel_size is not None:
         _check_voxel_size(voxel_size)
-    if isinstance(pcd, SweepSet):
-        return _preproc_sweeps(pcd, gts, num_points, lidar_line, radius, sampled_indices, flip_xy, device, want_float64,
-                               voxel_size)
-    p = torch.as_tensor(np.ascontiguousarray(pcd, dtype=np.float32)) if not torch.is_tensor(pcd) else pcd
-    p = p.to(device=device, dtype=torch.float32).contiguous()
-    _C.require_cuda(p)
-    if p.dim() == 2 and p.shape[1] == 3:                 # [n, 3] rows (the KITTI-raw and nuScenes readers): read at stride 3
-        return _preproc_sweeps(SweepSet([p]), gts, num_points, lidar_line, radius, sampled_indices, flip_xy, device,
-                               want_float64, voxel_size)
-    assert p.dim() == 2 and p.shape[1] == 4
-    n_src = p.shape[0]
-    pre = None
-    n = n_src
-    if lidar_line is not None:
-        pre = torch.from_numpy(lidar_line_indices(n_src, lidar_line)).to(p.device)
-        n = int(pre.numel())
-    keep = torch.empty(n, dtype=torch.int32, device=p.device)
-    count = torch.zeros(1, dtype=torch.int32, device=p.device)
-    if radius is not None:
-        scratch = torch.empty(_L().efgh_prep_filter_blocks(c_int32(n)), dtype=torch.int32, device=p.device)
-        _C.check(_L().efgh_prep_radius_filter(ptr(p), ptr(pre), c_int32(n), c_int32(1 if flip_xy else 0), c_float(radius),
-                                              ptr(scratch), ptr(keep), ptr(count), _st()))
-        if voxel_size is not None:                       # the count stays on the device: the thinning reads it there
-            keep, n_keep = _voxel_thin(p, keep, n, count, voxel_size, p.device)
-        else:
-            n_keep = int(count.item())                   # one host read per sample: the branch below depends on it
-    elif voxel_size is not None:
-        keep, n_keep = _voxel_thin(p, pre, n, None, voxel_size, p.device)
-    else:
-        keep = pre if pre is not None else torch.arange(n, dtype=torch.int32, device=p.device)
-        n_keep = n
-    sel, n_sel = _subsample(n_keep, num_points, sampled_indices, p.device)
-    T = _upload_T(gts, p.device, wait=voxel_size is None)
-    out32 = torch.empty((3, num_points), dtype=torch.float32, device=p.device)
-    out64 = torch.empty((3, num_points), dtype=torch.float64, device=p.device) if want_float64 else None
-    _C.check(_L().efgh_prep_gather_transform(ptr(p), ptr(keep), ptr(sel), c_int32(n_sel), c_int32(1 if flip_xy else 0),
-                                             ptr(T), c_int32(num_points), ptr(out32), ptr(out64), _st()))
+    if not isinstance(pcd, SweepSet):
+        p = torch.as_tensor(np.ascontiguousarray(pcd, dtype=np.float32)) if not torch.is_tensor(pcd) else pcd
+        p = p.to(device=device, dtype=torch.float32).contiguous()
+        _C.require_cuda(p)
+        assert p.dim() == 2 and p.shape[1] in (3, 4)
+        pcd = SweepSet([p]) if p.shape[1] == 3 else p    # [n, 3] rows are read at stride 3
+    src, keep, n_keep = _keep_rows(pcd, device, lidar_line, radius, flip_xy, voxel_size)
+    sel, n_sel = _subsample(n_keep, num_points, sampled_indices, src.device)
+    T = _upload_T(gts, src.device, wait=voxel_size is None)
+    out32 = torch.empty((3, num_points), dtype=torch.float32, device=src.device)
+    out64 = torch.empty((3, num_points), dtype=torch.float64, device=src.device) if want_float64 else None
+    rows_kept = (c_int32(n_keep),) if src.set is not None else ()            # a sweep set checks `sel` against the kept rows
+    src.call(src.gather, ptr(keep), *rows_kept, ptr(sel), c_int32(n_sel), c_int32(1 if flip_xy else 0), ptr(T), c_int32(num_points),
+             ptr(out32), ptr(out64))
     return (out32, out64) if want_float64 else out32
 
 

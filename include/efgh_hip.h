@@ -953,7 +953,13 @@ int efgh_prep_u8_to_f32_chw_pad(const uint8_t *in, int32_t h, int32_t w, int32_t
 /* preproc_pcd (loader_utils.py:160-202): stable compaction of the points with -r <= x,y < r (pcd [n][4] fp32,
  * optionally pre-gathered by pre_idx (lidar-line reduction) and with x,y negated (RELLIS axis flip));
  * keep_idx [n] receives the surviving source rows in order, *count their number;
- * block_scratch has efgh_prep_filter_blocks(n) ints.                                                               */
+ * block_scratch has efgh_prep_filter_blocks(n) ints.
+ * This filter, efgh_prep_sweeps_filter and the last three launches of efgh_prep_*voxel_keep are ONE stable compaction (csrc/prep.hip:
+ * k_flag_count<Pred>, k_scan_blocks, k_compact<Pred>; the block scan itself is csrc/common.h's) under two predicates: the box (ego box
+ * and radius, over plain rows or a sweep set) and the voxel's first row.  The box is compared in float64 on every path; for plain
+ * float32 rows that decides every row as numpy's float32 compare does (the conversions and the product with +-1 are exact).
+ * The plain entry points are told no row count, so pre_idx / keep_idx are not checked against one: that check belongs to the
+ * sweep-set entry points below.                                                                                    */
 int32_t efgh_prep_filter_blocks(int32_t n);
 int efgh_prep_radius_filter(const float *pcd, const int32_t *pre_idx, int32_t n, int32_t flip_xy, float radius,
                             int32_t *block_scratch, int32_t *keep_idx, int32_t *count, void *stream);
@@ -977,7 +983,8 @@ int efgh_prep_gather_transform(const float *pcd, const int32_t *keep_idx, const 
  * q.y when flip_xy; radius <= 0: no radius test).  At least one of the two tests must be on.  keep_idx [n] receives the kept indices
  * in candidate order, *count their number; block_scratch has efgh_prep_filter_blocks(n) ints.
  * efgh_prep_sweeps_gather_transform: efgh_prep_gather_transform reading q of keep_idx[sel[j]] (sel NULL: j; an entry outside
- * [0, n_keep) gives the zero point).
+ * [0, n_keep) gives the zero point).  One kernel template serves both (k_gather_transform<SWEEPS>: the position of a row is
+ * row_position<SWEEPS>, (double)p for plain rows).
  * efgh_prep_sweeps_materialize: out [n][3] float64 = q of keep_idx[j] (NULL: j), the accumulated cloud itself.               */
 int efgh_prep_sweeps_filter(const float *pts, int32_t stride, const int32_t *sweep_off, const double *M34,
                             const int32_t *identity, int32_t K, int32_t n_total, const int32_t *pre_idx, int32_t n,
