@@ -5,7 +5,7 @@ import numpy as np
 import torch
 
 from .. import _C
-from .._C import c_int32, ptr
+from .._C import ptr
 
 
 class Err(object):
@@ -30,10 +30,8 @@ class Err(object):
             nb = torch.empty((2, self.capacity * 2), dtype=torch.float32, device=p.device)
             nb[:, :self.capacity] = self._buf
             self._buf, self.capacity = nb, self.capacity * 2
-        _C.check(_C.lib().efgh_pose_errors(ptr(g), ptr(p), c_int32(1), c_int32(self.mode),
-                                           _C.c_void_p(self._buf.data_ptr() + 4 * self._n),
-                                           _C.c_void_p(self._buf.data_ptr() + 4 * (self.capacity + self._n)),
-                                           _C.stream_ptr()))
+        _C.check(_C.lib().efgh_pose_errors(ptr(g), ptr(p), 1, self.mode, _C.c_void_p(self._buf.data_ptr() + 4 * self._n),
+                                           _C.c_void_p(self._buf.data_ptr() + 4 * (self.capacity + self._n)), _C.stream_ptr()))
         self._n += 1
 
     @property

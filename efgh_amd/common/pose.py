@@ -4,7 +4,6 @@ with .item()/.tolist() of common/torch_utils.py:105-146, 170-233, 256-296): one 
 device tensor expressions are kept below as the `USE_KERNELS = False` path (what the kernels are tested
 against).  Differentiability mirrors the reference: the skew matrix K is built from detached values,
 only (1-c)/s^2 carries gradient (torch_utils.py:184,194); translation matrices are detached (:229)."""
-import ctypes
 import math
 import os
 
@@ -38,9 +37,8 @@ class PoseHeadFn(torch.autograd.Function):
         g = torch.empty((B, nd), dtype=torch.float32, device=abs_logits.device)
         ga, gn, gR = (None if t is None else t.contiguous() for t in (ga, gn, gR))
         _C.check(_C.lib().efgh_pose_head_normal_bwd(
-            _C.ptr(abs_logits), ctypes.c_int64(abs_logits.stride(0)), _C.ptr(sgn_logits), ctypes.c_int64(sgn_logits.stride(0)),
-            ctypes.c_int32(B), ctypes.c_int32(nd), ctypes.c_float(d[0]), ctypes.c_float(d[1]), ctypes.c_float(d[2]),
-            _C.ptr(ga), _C.ptr(gn), _C.ptr(gR), _C.ptr(g), _C.stream_ptr()))
+            _C.ptr(abs_logits), abs_logits.stride(0), _C.ptr(sgn_logits), sgn_logits.stride(0), B, nd, d[0], d[1], d[2], _C.ptr(ga),
+            _C.ptr(gn), _C.ptr(gR), _C.ptr(g), _C.stream_ptr()))
         return g, None, None
 
 
@@ -66,10 +64,8 @@ def _head_normal_launch(abs_logits, sgn_logits, dest):
     a = torch.empty((B, nd, 1), dtype=torch.float32, device=dev)
     n = torch.empty((B, nd, 1), dtype=torch.float32, device=dev)
     R = torch.empty((B, 4, 4), dtype=torch.float32, device=dev)
-    _C.check(_C.lib().efgh_pose_head_normal(_C.ptr(abs_logits), ctypes.c_int64(abs_logits.stride(0)), _C.ptr(sgn_logits),
-                                            ctypes.c_int64(sgn_logits.stride(0)), ctypes.c_int32(B), ctypes.c_int32(nd),
-                                            ctypes.c_float(dest[0]), ctypes.c_float(dest[1]), ctypes.c_float(dest[2]),
-                                            _C.ptr(a), _C.ptr(n), _C.ptr(R), _C.stream_ptr()))
+    _C.check(_C.lib().efgh_pose_head_normal(_C.ptr(abs_logits), abs_logits.stride(0), _C.ptr(sgn_logits), sgn_logits.stride(0), B,
+                                            nd, dest[0], dest[1], dest[2], _C.ptr(a), _C.ptr(n), _C.ptr(R), _C.stream_ptr()))
     return a, n, R
 
 
@@ -156,8 +152,7 @@ class CamTVeloFn(torch.autograd.Function):
         B = l_T.shape[0]
         c, l, k, a = c_T.contiguous(), l_T.contiguous(), calib.contiguous(), A.contiguous()
         out = torch.empty((B, 3, 4), dtype=torch.float32, device=l_T.device)
-        _C.check(_C.lib().efgh_pose_cam_T_velo(_C.ptr(c), ctypes.c_int64(9), _C.ptr(l), _C.ptr(k), _C.ptr(a), ctypes.c_int32(B),
-                                               _C.ptr(out), _C.stream_ptr()))
+        _C.check(_C.lib().efgh_pose_cam_T_velo(_C.ptr(c), 9, _C.ptr(l), _C.ptr(k), _C.ptr(a), B, _C.ptr(out), _C.stream_ptr()))
         ctx.save_for_backward(c, l, k, a)
         return out
 
@@ -168,17 +163,15 @@ class CamTVeloFn(torch.autograd.Function):
         gc = torch.empty((B, 3, 3), dtype=torch.float32, device=l.device) if ctx.needs_input_grad[0] else None
         gl = torch.empty((B, 4, 4), dtype=torch.float32, device=l.device) if ctx.needs_input_grad[1] else None
         if gc is not None or gl is not None:
-            _C.check(_C.lib().efgh_pose_cam_T_velo_bwd(_C.ptr(c), ctypes.c_int64(9), _C.ptr(l), _C.ptr(k), _C.ptr(a),
-                                                       _C.ptr(g.contiguous()), ctypes.c_int32(B), _C.ptr(gc), _C.ptr(gl),
-                                                       _C.stream_ptr()))
+            _C.check(_C.lib().efgh_pose_cam_T_velo_bwd(_C.ptr(c), 9, _C.ptr(l), _C.ptr(k), _C.ptr(a), _C.ptr(g.contiguous()), B,
+                                                       _C.ptr(gc), _C.ptr(gl), _C.stream_ptr()))
         return gc, gl, None, None
 
 
 def _mat44(a, b, ta=0, tb=0):
     B = a.shape[0]
     out = torch.empty((B, 4, 4), dtype=torch.float32, device=a.device)
-    _C.check(_C.lib().efgh_pose_mat44_mul(_C.ptr(a), _C.ptr(b), ctypes.c_int32(B), ctypes.c_int32(ta), ctypes.c_int32(tb),
-                                          _C.ptr(out), _C.stream_ptr()))
+    _C.check(_C.lib().efgh_pose_mat44_mul(_C.ptr(a), _C.ptr(b), B, ta, tb, _C.ptr(out), _C.stream_ptr()))
     return out
 
 
@@ -227,8 +220,7 @@ def yaw_rotation_from_scores(f_score):
         _C.require_cuda(f_score)
         assert f_score.stride(1) == 1
         R = torch.empty((f_score.shape[0], 4, 4), dtype=torch.float32, device=f_score.device)
-        _C.check(_C.lib().efgh_pose_head_yaw(_C.ptr(f_score), ctypes.c_int64(f_score.stride(0)), ctypes.c_int32(f_score.shape[0]),
-                                             ctypes.c_int32(n), _C.ptr(R), _C.stream_ptr()))
+        _C.check(_C.lib().efgh_pose_head_yaw(_C.ptr(f_score), f_score.stride(0), f_score.shape[0], n, _C.ptr(R), _C.stream_ptr()))
         return R
     f_idx = torch.argmax(f_score, dim=1, keepdim=True).float()
     f_rad = -(f_idx / (n - 1)) * 2 * math.pi + math.pi

@@ -71,13 +71,13 @@ class _Painter:
             arr[k].inp, arr[k].out, arr[k].H, arr[k].W, arr[k].px = n.data_ptr(), out.data_ptr(), n.shape[0], n.shape[1], px
         dev = self.jobs[0][0].device
         jobs = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(dev)
-        _C.check(_L().efgh_sum_paint(_C.ptr(jobs), ctypes.c_int32(len(self.jobs)), _st()))
+        _C.check(_L().efgh_sum_paint(_C.ptr(jobs), len(self.jobs), _st()))
         res = []
         for n, out, _ in self.jobs:
             H, W = out.shape
             rgb = torch.empty((H, W, 3), dtype=torch.uint8, device=dev)
             mask = torch.empty((H, W), dtype=torch.uint8, device=dev)
-            _C.check(_L().efgh_sum_colorize(_C.ptr(out), ctypes.c_int64(H * W), _C.ptr(self.lut), _C.ptr(rgb), _C.ptr(mask), _st()))
+            _C.check(_L().efgh_sum_colorize(_C.ptr(out), H * W, _C.ptr(self.lut), _C.ptr(rgb), _C.ptr(mask), _st()))
             res.append((rgb, mask))
         return res
 
@@ -92,8 +92,8 @@ def depth_image_last(pc0, T34, raw_hw):
     dev = pc0.device
     ws = torch.empty(H * W, dtype=torch.int32, device=dev)
     out = torch.empty((H, W), dtype=torch.uint8, device=dev)
-    _C.check(_L().efgh_sum_depth_last(_C.ptr(pc0), ctypes.c_int64(pc0.stride(0)), ctypes.c_int32(pc0.shape[1]), _C.ptr(_T34(T34, dev)),
-                                      ctypes.c_int32(H), ctypes.c_int32(W), _C.ptr(ws), _C.ptr(out), _st()))
+    _C.check(_L().efgh_sum_depth_last(_C.ptr(pc0), pc0.stride(0), pc0.shape[1], _C.ptr(_T34(T34, dev)), H, W, _C.ptr(ws),
+                                      _C.ptr(out), _st()))
     return out
 
 
@@ -103,9 +103,8 @@ def range_image_last(pc0, T44, rng_hw, fov):
     dev = pc0.device
     ws = torch.empty(H * W, dtype=torch.int32, device=dev)
     out = torch.empty((H, W), dtype=torch.float64, device=dev)
-    _C.check(_L().efgh_sum_range_last(_C.ptr(pc0), ctypes.c_int64(pc0.stride(0)), ctypes.c_int32(pc0.shape[1]), _C.ptr(_T34(T44, dev)),
-                                      ctypes.c_int32(H), ctypes.c_int32(W), ctypes.c_double(fov[0] * math.pi),
-                                      ctypes.c_double(fov[1] * math.pi), _C.ptr(ws), _C.ptr(out), _st()))
+    _C.check(_L().efgh_sum_range_last(_C.ptr(pc0), pc0.stride(0), pc0.shape[1], _C.ptr(_T34(T44, dev)), H, W, fov[0] * math.pi,
+                                      fov[1] * math.pi, _C.ptr(ws), _C.ptr(out), _st()))
     return out
 
 

@@ -24,7 +24,7 @@ import numpy as np
 import torch
 
 from .. import _C
-from .._C import c_float, c_int32, ptr
+from .._C import ptr
 
 
 def _L():
@@ -170,7 +170,7 @@ def rotate_expand(img, angle_deg):
     (nw, nh), coef = rotate_plan(w, h, float(angle_deg))
     out = torch.empty((nh, nw, 3), dtype=torch.uint8, device=img.device)
     c6 = (ctypes.c_int64 * 6)(*coef)
-    _C.check(_L().efgh_prep_affine_nearest_u8(ptr(img), c_int32(h), c_int32(w), c6, ptr(out), c_int32(nh), c_int32(nw), _st()))
+    _C.check(_L().efgh_prep_affine_nearest_u8(ptr(img), h, w, c6, ptr(out), nh, nw, _st()))
     return out
 
 
@@ -182,8 +182,7 @@ def crop_image(img, target_hw, init=False):
     i0, j0 = int(math.floor((ph - h) / 2.)), int(math.floor((pw - w) / 2.))
     i, j = (0, 0) if init else (int(math.floor((ph - th) / 2.)), int(math.floor((pw - tw) / 2.)))
     out = torch.empty((th, tw, 3), dtype=torch.uint8, device=img.device)
-    _C.check(_L().efgh_prep_crop_pad_u8(ptr(img), c_int32(h), c_int32(w), c_int32(i - i0), c_int32(j - j0), ptr(out),
-                                        c_int32(th), c_int32(tw), _st()))
+    _C.check(_L().efgh_prep_crop_pad_u8(ptr(img), h, w, i - i0, j - j0, ptr(out), th, tw, _st()))
     return out
 
 
@@ -197,8 +196,7 @@ def resize_image(img, target_hw):
             continue
         bounds, kk, ksize = resample_tables(w if axis else h, size, img.device)
         out = torch.empty((h, size, 3) if axis else (size, w, 3), dtype=torch.uint8, device=img.device)
-        _C.check(_L().efgh_prep_resample_u8(ptr(cur), c_int32(h), c_int32(w), c_int32(axis), c_int32(size), ptr(bounds),
-                                            ptr(kk), c_int32(ksize), ptr(out), _st()))
+        _C.check(_L().efgh_prep_resample_u8(ptr(cur), h, w, axis, size, ptr(bounds), ptr(kk), ksize, ptr(out), _st()))
         cur = out
     return cur.clone() if cur is img else cur
 
@@ -207,7 +205,7 @@ def _chw_and_mask(img, want_chw=True, want_mask=False):
     h, w = img.shape[:2]
     chw = torch.empty((3, h, w), dtype=torch.uint8, device=img.device) if want_chw else None
     mask = torch.empty((1, h, w), dtype=torch.uint8, device=img.device) if want_mask else None
-    _C.check(_L().efgh_prep_hwc_to_chw_u8(ptr(img), c_int32(h), c_int32(w), ptr(chw), ptr(mask), _st()))
+    _C.check(_L().efgh_prep_hwc_to_chw_u8(ptr(img), h, w, ptr(chw), ptr(mask), _st()))
     return chw, mask
 
 
@@ -224,8 +222,7 @@ def preproc_img(img, gts, raw_cam_img_size, rellis=False, device='cuda'):
     th, tw = int(raw_hw[0] / 2), int(raw_hw[1] / 2)
     img_in = torch.empty((3, th, tw), dtype=torch.float32, device=img.device)
     oy, ox = int(math.floor((th - half[0]) / 2.)), int(math.floor((tw - half[1]) / 2.))
-    _C.check(_L().efgh_prep_u8_to_f32_chw_pad(ptr(small), c_int32(half[0]), c_int32(half[1]), c_int32(oy), c_int32(ox),
-                                              ptr(img_in), c_int32(th), c_int32(tw), _st()))
+    _C.check(_L().efgh_prep_u8_to_f32_chw_pad(ptr(small), half[0], half[1], oy, ox, ptr(img_in), th, tw, _st()))
     raw_chw, _ = _chw_and_mask(img_raw)
     rot_chw, mask = _chw_and_mask(img_rot, want_mask=True)
     return {'in': img_in, 'raw': raw_chw, 'rot': rot_chw, 'img_mask': mask}
@@ -292,7 +289,7 @@ class _Rows(object):
         else:
             self.set, self.pts, self.rows = None, src, int(src.shape[0])
             self.filter, self.gather = ('efgh_prep_radius_filter', (ptr(src),)), ('efgh_prep_gather_transform', (ptr(src),))
-            self.thin = ('efgh_prep_voxel_keep', (ptr(src), c_int32(int(src.shape[1])), c_int32(self.rows)))
+            self.thin = ('efgh_prep_voxel_keep', (ptr(src), int(src.shape[1]), self.rows))
         self.device = self.pts.device
 
     def call(self, step, *args):
@@ -304,13 +301,13 @@ def _voxel_thin(src, keep, n, n_dev, voxel_size):
     """of the candidates keep[0 .. n) (None: rows 0 .. n-1; `n_dev`: their count on the device, None: n) the first row of every
     occupied voxel, in order -> (int32 tensor, count).  `src` is a _Rows."""
     v = _check_voxel_size(voxel_size)
-    nbytes = _L().efgh_prep_voxel_workspace(c_int32(n))
+    nbytes = _L().efgh_prep_voxel_workspace(n)
     if nbytes < 0:
         raise _C.EfghError('voxel thinning: %d candidate rows, supported are fewer than 2^29' % n)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=src.device)
     out = torch.empty(n, dtype=torch.int32, device=src.device)
     counts = torch.empty(2, dtype=torch.int32, device=src.device)
-    src.call(src.thin, ptr(keep), c_int32(n), ptr(n_dev), ctypes.c_double(v), ptr(ws), ptr(out), ptr(counts))
+    src.call(src.thin, ptr(keep), n, ptr(n_dev), v, ptr(ws), ptr(out), ptr(counts))
     n_keep, exhausted = _read_counts(counts)
     if exhausted:
         raise _C.EfghError('voxel thinning: the hash table of %d candidate rows ran out of slots (a bug: it is sized at load <= 0.5)' % n)
@@ -486,7 +483,7 @@ class SweepSet(object):
 
     def _args(self, device):
         pts, _, off, M, ident = self._stage(device)
-        return pts, (ptr(pts), c_int32(self.stride), off, M, ident, c_int32(self.K), c_int32(self.n_total))
+        return pts, (ptr(pts), self.stride, off, M, ident, self.K, self.n_total)
 
     def kept_indices(self, radius=50., lidar_line=None, flip_xy=False, device='cuda', voxel_size=None):
         """rows of the concatenation (own sweep first, before the ego box) that `preproc_pcd` keeps, in its order: int32 on
@@ -505,7 +502,7 @@ class SweepSet(object):
             n = int(count.item())
         out = torch.empty((n, 3), dtype=torch.float64, device=pts.device)
         if n > 0:
-            _C.check(_L().efgh_prep_sweeps_materialize(*a, ptr(keep), c_int32(n), ptr(out), _st()))
+            _C.check(_L().efgh_prep_sweeps_materialize(*a, ptr(keep), n, ptr(out), _st()))
         return out
 
 
@@ -514,13 +511,13 @@ def _filter(src, pre, n, flip_xy, radius):
     -> (keep [n] int32, count [1] int32)"""
     keep = torch.empty(n, dtype=torch.int32, device=src.device)
     count = torch.zeros(1, dtype=torch.int32, device=src.device)
-    scratch = torch.empty(_L().efgh_prep_filter_blocks(c_int32(n)), dtype=torch.int32, device=src.device)
+    scratch = torch.empty(_L().efgh_prep_filter_blocks(n), dtype=torch.int32, device=src.device)
     if src.set is None:
-        box = (c_float(radius),)
+        box = (radius,)
     else:
         ex, ey = src.set.ego_box if src.set.ego_box is not None else (0., 0.)
-        box = (ctypes.c_double(0. if radius is None else radius), c_float(ex), c_float(ey))
-    src.call(src.filter, ptr(pre), c_int32(n), c_int32(1 if flip_xy else 0), *box, ptr(scratch), ptr(keep), ptr(count))
+        box = (0. if radius is None else radius, ex, ey)
+    src.call(src.filter, ptr(pre), n, 1 if flip_xy else 0, *box, ptr(scratch), ptr(keep), ptr(count))
     return keep, count
 
 
@@ -576,8 +573,8 @@ def preproc_pcd(pcd, gts, num_points, lidar_line=None, radius=50., sampled_indic
     T = _upload_T(gts, src.device, wait=voxel_size is None)
     out32 = torch.empty((3, num_points), dtype=torch.float32, device=src.device)
     out64 = torch.empty((3, num_points), dtype=torch.float64, device=src.device) if want_float64 else None
-    rows_kept = (c_int32(n_keep),) if src.set is not None else ()            # a sweep set checks `sel` against the kept rows
-    src.call(src.gather, ptr(keep), *rows_kept, ptr(sel), c_int32(n_sel), c_int32(1 if flip_xy else 0), ptr(T), c_int32(num_points),
+    rows_kept = (n_keep,) if src.set is not None else ()            # a sweep set checks `sel` against the kept rows
+    src.call(src.gather, ptr(keep), *rows_kept, ptr(sel), n_sel, 1 if flip_xy else 0, ptr(T), num_points,
              ptr(out32), ptr(out64))
     return (out32, out64) if want_float64 else out32
 

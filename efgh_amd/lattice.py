@@ -269,7 +269,7 @@ def _as_plan(mode):
 def _plan(L, n_cap, h_est, hashed=False, big=False):
     """the Plan of a level of n_cap points expecting ~h_est vertices (None: unknown).  hashed / big: the level's escalation state
     (_HASH_LEVELS / _BIG_LEVELS).  More points than the partitioned build's bucket limit (~2.8 M) take the hash build as well"""
-    nb = 0 if hashed else L.efgh_lattice_part_buckets(_C.c_int32(n_cap))
+    nb = 0 if hashed else L.efgh_lattice_part_buckets(n_cap)
     if nb:
         return Plan('part', nb, 2048 if h_est is None else min(2048, max(64, _pow2ceil(2.5 * h_est / nb + 64))), big)
     # hash table sized for the expected vertex count (load <= 1/2) instead of the worst case 4 * n_cap keys
@@ -314,7 +314,7 @@ def _relax(key):
 def _ctrl_bytes(L, n_cap, B, mode):
     """bytes of the zero-initialised control block of a level: info, and for the partitioned build its `zeroed` area"""
     info_b = (4 * (INFO_SEG + B) + 255) // 256 * 256
-    return info_b, (L.efgh_lattice_part_zeroed_bytes(_C.c_int32(n_cap)) if mode[0] == 'part' else 0)
+    return info_b, (L.efgh_lattice_part_zeroed_bytes(n_cap) if mode[0] == 'part' else 0)
 
 
 def _level_arrays(L, dev, n_cap, h_cap, B, mode=('hash', 0), ctrl=None, need_off=True):
@@ -349,21 +349,18 @@ def _level_arrays(L, dev, n_cap, h_cap, B, mode=('hash', 0), ctrl=None, need_off
 
 def _launch_build(L, lv, pts, cstride, n_dev, sid, pps, B, s, st):
     n_cap, h_cap = lv._caps
-    head = (_C.ptr(pts), _C.c_int64(cstride), _C.ptr(n_dev), _C.c_int32(n_cap), _C.ptr(sid), _C.c_int32(pps), _C.c_int32(B),
-            _C.c_float(np.float32(s)))
+    head = (_C.ptr(pts), cstride, _C.ptr(n_dev), n_cap, _C.ptr(sid), pps, B, s)
     lv._geom = (pts, cstride, n_dev, sid, pps, s)          # (kept alive for the neighbours call)
     lv._src = (pts, cstride, sid, pps, s)                  # (kept with the level: OutPoints.locate)
     plan = lv._mode
     if plan.kind == 'part':
-        _C.check(L.efgh_lattice_part_build(*head, _C.ptr(lv.bary_pm), _C.ptr(lv.emg_pm), _C.ptr(lv.list), _C.c_int32(h_cap),
-                                           _C.ptr(lv.info), _C.ptr(lv._ws), _C.ptr(lv._zeroed), _C.c_int32(plan.buckets),
-                                           _C.c_int32(plan.slots), _C.c_int32(0 if lv.off_pm is None else 1),
-                                           _C.c_int32(1 if plan.big else 0), st))
+        _C.check(L.efgh_lattice_part_build(*head, _C.ptr(lv.bary_pm), _C.ptr(lv.emg_pm), _C.ptr(lv.list), h_cap, _C.ptr(lv.info),
+                                           _C.ptr(lv._ws), _C.ptr(lv._zeroed), plan.buckets, plan.slots,
+                                           0 if lv.off_pm is None else 1, 1 if plan.big else 0, st))
     else:
-        _C.check(L.efgh_lattice_level_build(*head, _C.c_float(np.float32(EXPECTED_STD * s)), _C.ptr(lv.bary_pm), _C.ptr(lv.emg_pm),
-                                            _C.ptr(lv.off_pm), _C.ptr(lv.list), _C.c_int32(h_cap), _C.ptr(lv.vseg),
-                                            _C.ptr(lv.pts_next_buf), _C.ptr(lv.vsid), _C.ptr(lv.info), _C.ptr(lv._ws),
-                                            _C.c_int64(plan.slots), st))
+        _C.check(L.efgh_lattice_level_build(*head, EXPECTED_STD * s, _C.ptr(lv.bary_pm), _C.ptr(lv.emg_pm), _C.ptr(lv.off_pm),
+                                            _C.ptr(lv.list), h_cap, _C.ptr(lv.vseg), _C.ptr(lv.pts_next_buf), _C.ptr(lv.vsid),
+                                            _C.ptr(lv.info), _C.ptr(lv._ws), plan.slots, st))
 
 
 def _launch_neighbors(L, lv, B, h_rows, st):
@@ -376,17 +373,15 @@ def _launch_neighbors(L, lv, B, h_rows, st):
     if plan.kind == 'part':
         pts, cstride, n_dev, sid, pps, s = lv._geom
         _C.check(L.efgh_lattice_part_neighbors(
-            _C.ptr(lv._ws), _C.ptr(pts), _C.c_int64(cstride), _C.ptr(n_dev), _C.c_int32(n_cap), _C.ptr(sid), _C.c_int32(pps),
-            _C.c_int32(B), _C.c_float(np.float32(s)), _C.c_float(np.float32(EXPECTED_STD * s)), _C.c_int32(h_cap), _C.ptr(lv.info),
-            _C.c_int32(h_rows), _C.ptr(lv.nbr), _C.ptr(lv.alist), _C.c_int32(ALIAS_CAP), _C.ptr(lv.off_pm), _C.ptr(lv.vseg),
-            _C.ptr(lv.pts_next_buf), _C.ptr(lv.vsid), _C.c_int32(plan.buckets), _C.c_int32(plan.slots), st))
+            _C.ptr(lv._ws), _C.ptr(pts), cstride, _C.ptr(n_dev), n_cap, _C.ptr(sid), pps, B, s, EXPECTED_STD * s, h_cap,
+            _C.ptr(lv.info), h_rows, _C.ptr(lv.nbr), _C.ptr(lv.alist), ALIAS_CAP, _C.ptr(lv.off_pm), _C.ptr(lv.vseg),
+            _C.ptr(lv.pts_next_buf), _C.ptr(lv.vsid), plan.buckets, plan.slots, st))
         if lv.radius != 1:              # (that launch also emitted the vertex records the radius-r probes start from)
             _launch_neighbors_r(L, lv, B, h_rows, st)
             return
     else:
-        _C.check(L.efgh_lattice_level_neighbors(_C.ptr(lv._ws), _C.c_int32(n_cap), _C.c_int32(h_cap), _C.c_int32(B), _C.ptr(lv.info),
-                                                _C.ptr(lv.vsid), _C.c_int32(h_rows), _C.ptr(lv.nbr), _C.ptr(lv.alist),
-                                                _C.c_int32(ALIAS_CAP), _C.c_int64(plan.slots), st))
+        _C.check(L.efgh_lattice_level_neighbors(_C.ptr(lv._ws), n_cap, h_cap, B, _C.ptr(lv.info), _C.ptr(lv.vsid), h_rows,
+                                                _C.ptr(lv.nbr), _C.ptr(lv.alist), ALIAS_CAP, plan.slots, st))
     lv._geom = lv._zeroed = None
 
 
@@ -395,10 +390,9 @@ def _launch_neighbors_r(L, lv, B, h_rows, st):
     pts, cstride, n_dev, sid, pps, s = lv._geom
     dev = lv.info.device
     lv.nbr = torch.empty((h_rows, lv.ld), dtype=torch.int32, device=dev)
-    ws = torch.empty(L.efgh_lattice_neighbors_r_workspace(_C.c_int32(h_rows), _C.c_int32(B)), dtype=torch.uint8, device=dev)
-    _C.check(L.efgh_lattice_neighbors_r(_C.ptr(pts), _C.c_int64(cstride), _C.ptr(sid), _C.c_int32(pps), _C.c_int32(B),
-                                        _C.c_float(np.float32(s)), _C.ptr(lv.list), _C.ptr(lv.vseg), _C.ptr(lv.vsid), _C.ptr(lv.info),
-                                        _C.c_int32(h_rows), _C.ptr(_dev_offsets(lv.radius, dev)), _C.c_int32(lv.F), _C.c_int32(lv.ld),
+    ws = torch.empty(L.efgh_lattice_neighbors_r_workspace(h_rows, B), dtype=torch.uint8, device=dev)
+    _C.check(L.efgh_lattice_neighbors_r(_C.ptr(pts), cstride, _C.ptr(sid), pps, B, s, _C.ptr(lv.list), _C.ptr(lv.vseg),
+                                        _C.ptr(lv.vsid), _C.ptr(lv.info), h_rows, _C.ptr(_dev_offsets(lv.radius, dev)), lv.F, lv.ld,
                                         _C.ptr(lv.nbr), _C.ptr(ws), st))
     lv._geom = lv._zeroed = None
 

@@ -25,23 +25,14 @@ _GT = {'e_gn': (0, 3), 'e_l': (3, 19), 'h_hrzn': (19, 22), 'h_c': (22, 31), 'f_l
        'e_gn_abs': (66, 69), 'h_hrzn_abs': (69, 71)}          # columns of efgh_pose_loss_fwd's gt72 (include/efgh_hip.h)
 
 
-class _PoseLossDesc(ctypes.Structure):
-    _fields_ = [(n, ctypes.c_void_p) for n in ('e_gn_abs', 'e_gn_sgn', 'h_hrzn_abs', 'h_hrzn_sgn', 'f_score', 'g_trs', 'e_l', 'f_l')] + \
-               [(n, ctypes.c_int64) for n in ('ld_e_gn_sgn', 'ld_h_hrzn_sgn', 'ld_f_score')] + \
-               [(n, ctypes.c_void_p) for n in ('rand_init_l', 'rand_init_c', 'sensor2_T_sensor1')] + \
-               [(n, ctypes.c_int32) for n in ('rand_init_l_dim', 'rand_init_c_dim', 'B', 'W', 'fov_pos_num')] + \
-               [(n, ctypes.c_float) for n in ('fov_neg_ratio', 'lambda_e_gn', 'lambda_h_hrzn', 'lambda_fov', 'lambda_g_trs',
-                                              'lambda_g_depth', 'lambda_g_mask')]
-
-
 def _pose_desc(t, cfg):
     e_abs, e_sgn, h_abs, h_sgn, fs, g_trs, e_l, f_l, rl, rc, T4 = t
     lam, pos, neg = cfg
-    p = lambda x: ctypes.c_void_p(x.data_ptr())
-    return _PoseLossDesc(p(e_abs), p(e_sgn), p(h_abs), p(h_sgn), p(fs), p(g_trs), p(e_l), p(f_l), e_sgn.stride(0), h_sgn.stride(0),
-                         fs.stride(0), p(rl), p(rc), p(T4), rl.shape[-1], rc.shape[-1], fs.shape[0], fs.shape[1], int(pos), float(neg),
-                         lam['e_gn'],
-                         lam['h_hrzn'], lam['fov'], lam['g_trs'], lam['g_depth'], lam['g_mask'])
+    p = ops.ptr
+    return ops._C.PoseLossDesc(p(e_abs), p(e_sgn), p(h_abs), p(h_sgn), p(fs), p(g_trs), p(e_l), p(f_l), e_sgn.stride(0),
+                               h_sgn.stride(0), fs.stride(0), p(rl), p(rc), p(T4), rl.shape[-1], rc.shape[-1], fs.shape[0],
+                               fs.shape[1], int(pos), float(neg), lam['e_gn'], lam['h_hrzn'], lam['fov'], lam['g_trs'],
+                               lam['g_depth'], lam['g_mask'])
 
 
 class PoseLossFn(torch.autograd.Function):

@@ -8,7 +8,7 @@ import weakref
 import torch
 
 from . import _C
-from ._C import c_float, c_int32, c_int64, ptr
+from ._C import c_float, ptr
 
 ACT_NONE, ACT_RELU, ACT_LEAKY = 0, 1, 2
 
@@ -138,17 +138,10 @@ BATCH_PACK = True        # every stale packed layout of an owner in ONE launch (
 PACK_TILED = True        # ... through LDS tiles, coalesced on both sides (False: the flat one-lane-per-element kernel)
 
 
-class _PackJob(ctypes.Structure):
-    """mirror of efgh_pack_job (include/efgh_hip.h)"""
-    _fields_ = [('W', ctypes.c_void_p), ('Wp', ctypes.c_void_p), ('N', c_int32), ('T', c_int32), ('C', c_int32), ('Np', c_int32),
-                ('Cp', c_int32), ('pad', c_int32), ('sn', c_int64), ('sc', c_int64), ('st', c_int64), ('taps', c_int32 * 16)]
-
-
 def _pack_one(w, buf, prm):
     N, T, C, Np, Cp, sn, sc, st, taps = prm
     tp = (ctypes.c_int32 * 16)(*([int(t) for t in taps] + [0] * (16 - len(taps)))) if taps is not None else None
-    _C.check(_L().efgh_pack_weight_padded(ptr(w), ptr(buf), c_int32(N), c_int32(T), c_int32(C), c_int32(Np), c_int32(Cp),
-                                          c_int64(sn), c_int64(sc), c_int64(st), tp, _st()))
+    _C.check(_L().efgh_pack_weight_padded(ptr(w), ptr(buf), N, T, C, Np, Cp, sn, sc, st, tp, _st()))
     buf._efgh_gen = getattr(buf, '_efgh_gen', 0) + 1
 
 
@@ -182,7 +175,7 @@ def _repack_all(device, holder):
         sig = (PACK_TILED,) + tuple((w.data_ptr(), buf.data_ptr(), key) for w, key, buf, _ in jobs)
         tab = holder.tables.get(device.index)
         if tab is None or tab[0] != sig:
-            arr = (_PackJob * len(jobs))()
+            arr = (_C.PackJob * len(jobs))()
             prefix, total = [], 0
             for i, (w, key, buf, _) in enumerate(jobs):
                 N, T, C, Np, Cp, sn, sc, st, taps = buf._efgh_pack
@@ -197,19 +190,13 @@ def _repack_all(device, holder):
             pre = torch.tensor(prefix, dtype=torch.int64).to(device)
             tab = holder.tables[device.index] = (sig, raw, pre, total)
         if PACK_TILED:      # (prefix over LDS tiles of 8 rows x 32 channels)
-            _C.check(_L().efgh_pack_weight_batched_tiled(ptr(tab[1]), ptr(tab[2]), c_int32(len(jobs)), c_int64(tab[3]), _st()))
+            _C.check(_L().efgh_pack_weight_batched_tiled(ptr(tab[1]), ptr(tab[2]), len(jobs), tab[3], _st()))
         else:
-            _C.check(_L().efgh_pack_weight_batched(ptr(tab[1]), ptr(tab[2]), c_int32(len(jobs)), c_int64(tab[3]), _st()))
+            _C.check(_L().efgh_pack_weight_batched(ptr(tab[1]), ptr(tab[2]), len(jobs), tab[3], _st()))
         for w, key, buf, cur in jobs:
             buf._efgh_gen = getattr(buf, '_efgh_gen', 0) + 1
             w.__dict__['_efgh_cache'][key] = (cur, buf)
         _rewino_all(device, holder, [buf for _, _, buf, _ in jobs])
-
-
-class _WinoJob(ctypes.Structure):
-    """mirror of efgh_wino_pack_job (include/efgh_hip.h)"""
-    _fields_ = [('Wp', ctypes.c_void_p), ('U', ctypes.c_void_p), ('N', c_int32), ('C', c_int32), ('kind', c_int32), ('pad', c_int32),
-                ('first_block', c_int64)]
 
 
 BATCH_WINO = True        # the Winograd-domain weights of the re-packed layouts in one launch as well (tests flip it)
@@ -234,7 +221,7 @@ def _rewino_all(device, holder, bufs):
     sig = tuple((buf.data_ptr(), U.data_ptr(), kind) for buf, _, kind, U in derived)
     tab = holder.tables.get(('wino', device.index))
     if tab is None or tab[0] != sig:
-        arr = (_WinoJob * len(derived))()
+        arr = (_C.WinoPackJob * len(derived))()
         nb = 0
         for i, (buf, _, kind, U) in enumerate(derived):
             N, C = (U.shape[2], U.shape[0] // 3 * 16) if kind == 0 else (U.shape[1], U.shape[2])
@@ -243,7 +230,7 @@ def _rewino_all(device, holder, bufs):
             nb += ((3 * C * N if kind == 0 else N * C) + 255) // 256
         raw = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(device)
         tab = holder.tables[('wino', device.index)] = (sig, raw, nb)
-    _C.check(_L().efgh_wino_pack_batched(ptr(tab[1]), c_int32(len(derived)), c_int64(tab[2]), _st()))
+    _C.check(_L().efgh_wino_pack_batched(ptr(tab[1]), len(derived), tab[2], _st()))
     for buf, key, _, U in derived:
         buf.__dict__['_efgh_cache'][key] = (_ver(buf), U)
 
@@ -365,7 +352,7 @@ def pad_vec(v, Np, fill=0.0):
         out[:v.numel()] = v
         return out
     out = torch.empty((Np,), dtype=torch.float32, device=v.device)
-    _C.check(_L().efgh_pad_vec(ptr(v), c_int32(v.numel()), ptr(out), c_int32(Np), c_float(fill), _st()))
+    _C.check(_L().efgh_pad_vec(ptr(v), v.numel(), ptr(out), Np, fill, _st()))
     return out
 
 
@@ -373,7 +360,7 @@ def pad_vec(v, Np, fill=0.0):
 # gather-GEMM
 # ----------------------------------------------------------------------------------------------
 def gemm_grid_m(M, N):
-    return _L().efgh_gather_gemm_grid_m(c_int64(M), c_int32(N))
+    return _L().efgh_gather_gemm_grid_m(M, N)
 
 
 USE_WINO = True  # Winograd F(4,3) kernel for the "same" 3x3 convolutions
@@ -418,7 +405,7 @@ def wino2d_weight(Wp, N, C):
     """U = G w G^T of a packed [N][9][C] weight (efgh_wino2d_pack), cached on the packed tensor"""
     def make():
         U = torch.empty((36, N, C), dtype=torch.float32, device=Wp.device)
-        _C.check(_L().efgh_wino2d_pack(ptr(Wp), ptr(U), c_int32(N), c_int32(C), _st()))
+        _C.check(_L().efgh_wino2d_pack(ptr(Wp), ptr(U), N, C, _st()))
         return U
     return _cached(Wp, ('wino2d',), _ver(Wp), make)
 
@@ -475,7 +462,7 @@ def wino_weight(Wp, N, C):
     """U = G w of a packed [N][9][C] weight (efgh_wino_pack), cached on the packed tensor"""
     def make():
         U = torch.empty((3 * C // 16, 6, N, 16), dtype=torch.float32, device=Wp.device)
-        _C.check(_L().efgh_wino_pack(ptr(Wp), ptr(U), c_int32(N), c_int32(C), _st()))
+        _C.check(_L().efgh_wino_pack(ptr(Wp), ptr(U), N, C, _st()))
         return U
     return _cached(Wp, ('wino',), _ver(Wp), make)
 
@@ -571,13 +558,13 @@ def stats_rows(mode, C, N, geom, M):
     """rows of the per-tile BatchNorm statistics buffer the GEMM launch for this layer writes"""
     route = gemm_route(mode, C, N, 1 if geom is None else len(geom[7]), geom, M, stats=True)
     if route == 'sc':
-        return _L().efgh_sc_stats_rows(c_int32(geom[0]), c_int32(geom[1]), c_int32(geom[2]))
+        return _L().efgh_sc_stats_rows(geom[0], geom[1], geom[2])
     if route == 'c4':
-        return _L().efgh_c4_stats_rows(c_int32(geom[0]), c_int32(geom[9]), c_int32(geom[10]))
+        return _L().efgh_c4_stats_rows(geom[0], geom[9], geom[10])
     if route == 'wino2d':
-        return _L().efgh_wino2d_stats_rows(c_int32(geom[0]), c_int32(geom[1]), c_int32(geom[2]), c_int32(N))
+        return _L().efgh_wino2d_stats_rows(geom[0], geom[1], geom[2], N)
     if route == 'wino':
-        return _L().efgh_wino_grid_m(c_int32(geom[0]), c_int32(geom[1]), c_int32(geom[2]))
+        return _L().efgh_wino_grid_m(geom[0], geom[1], geom[2])
     return gemm_grid_m(M, N)
 
 
@@ -670,8 +657,7 @@ def _blur_gemm_ksplit(A, lda, C, Wp, N, M, out, ldo, table, bias, act, slope, a_
     if bias is not None:
         b = bias if bias.numel() == N else None
         assert b is not None
-    _C.check(_L().efgh_fold_planes(ptr(part), c_int32(S), c_int64(M), c_int32(N), ptr(b), c_int32(act), c_float(slope),
-                                   _C.c_void_p(out.data_ptr() + 4 * out_off), c_int64(ldo), _st()))
+    _C.check(_L().efgh_fold_planes(ptr(part), S, M, N, ptr(b), act, slope, out.data_ptr() + 4 * out_off, ldo, _st()))
 
 
 def gather_gemm(A, lda, C, T, Wp, N, M, out, ldo, mode=0, geom=None, table=None, bias=None, scale=None,
@@ -721,14 +707,14 @@ def gather_gemm(A, lda, C, T, Wp, N, M, out, ldo, mode=0, geom=None, table=None,
                 and bn_bwd.y is None and bn_bwd.raw.stride(-2) % 4 == 0):
             # the BatchNorm-backward sums of the layer whose activation gradient this launch writes, in its output transform: that
             # layer's reduction pass (a read of dy and of raw) is not run
-            rows = _L().efgh_wino2d_stats_rows(c_int32(geom[0]), c_int32(geom[1]), c_int32(geom[2]), c_int32(N))
+            rows = _L().efgh_wino2d_stats_rows(geom[0], geom[1], geom[2], N)
             bn_stats = _bn_bwd_sums(d, bn_bwd, rows, N, out.device)
         _wino2d_forward(d, A, a_off, lda, C, N, geom, Wp, pool=pool, lazy=lazy, pre_v=pre_v)
     elif route == 'wino_hpool':
         _C.check(_L().efgh_wino_conv3x3_hpool(ctypes.byref(d), ptr(wino_weight(Wp, N, C)), _st()))
     elif route == 'wino':
         if bn_bwd is not None and stats is None and BN_BWD_FUSED and out_off == 0 and bn_bwd.fits(M, N):
-            rows = _L().efgh_wino_grid_m(c_int32(geom[0]), c_int32(geom[1]), c_int32(geom[2]))
+            rows = _L().efgh_wino_grid_m(geom[0], geom[1], geom[2])
             bn_stats = _bn_bwd_sums(d, bn_bwd, rows, N, out.device)
         _C.check(_L().efgh_wino_conv3x3(ctypes.byref(d), ptr(wino_weight(Wp, N, C)), _st()))
     else:
@@ -759,7 +745,7 @@ GEMM_DMA = True                 # eligible efgh_gather_gemm launches on the LDS-
 
 def apply_switches():
     """push the switches that live inside the library (bench.py --set, tools): call after changing GEMM_DMA"""
-    _L().efgh_gather_gemm_set_dma(c_int32(1 if GEMM_DMA else 0))
+    _L().efgh_gather_gemm_set_dma(1 if GEMM_DMA else 0)
 
 
 PLANE_DMA = True                # the 36 planes of a 2-D Winograd layer on the LDS-DMA staged kernels (planes.hip); False: k_gather_gemm / k_gather_wgrad
@@ -793,9 +779,9 @@ def _batched_plain_gemm(A3, W3, out3, rows, C, N):
     if PLANE_DMA and _L().efgh_plane_gemm_supported(ctypes.byref(g)):
         if _planes_split_now():
             PLANE_SPLIT_HITS[0] += 1
-            _C.check(_L().efgh_plane_gemm_x6(ctypes.byref(g), c_int32(PLANE_DMA_NBUF), _st()))
+            _C.check(_L().efgh_plane_gemm_x6(ctypes.byref(g), PLANE_DMA_NBUF, _st()))
         else:
-            _C.check(_L().efgh_plane_gemm(ctypes.byref(g), c_int32(PLANE_DMA_NBUF), _st()))      # LDS-DMA staged (planes.hip)
+            _C.check(_L().efgh_plane_gemm(ctypes.byref(g), PLANE_DMA_NBUF, _st()))      # LDS-DMA staged (planes.hip)
     else:
         _C.check(_L().efgh_gather_gemm(ctypes.byref(g), _st()))
     _prof_end(ev, 'planes', (0, rows, N, 36, C), 2.0 * 36 * rows * C * N, PROFILE_WINO2D_GEMM)
@@ -858,33 +844,31 @@ def lazy_capable(mode, C, N, geom):
 
 def wino2d_input(A, a_off, lda, C, B, H, W, V, lazy=None):
     if lazy is None:
-        _C.check(_L().efgh_wino2d_input(_C.c_void_p(A.data_ptr() + 4 * a_off), c_int64(lda), c_int32(C), c_int32(B), c_int32(H),
-                                        c_int32(W), ptr(V), _st()))
+        _C.check(_L().efgh_wino2d_input(A.data_ptr() + 4 * a_off, lda, C, B, H, W, ptr(V), _st()))
     else:
         LAZY_HITS[0] += 1
-        _C.check(_L().efgh_wino2d_input_act(_C.c_void_p(A.data_ptr() + 4 * a_off), c_int64(lda), c_int32(C), c_int32(B), c_int32(H),
-                                            c_int32(W), ptr(lazy.scale), ptr(lazy.shift), c_int32(lazy.act), c_float(lazy.slope),
-                                            ptr(V), _st()))
+        _C.check(_L().efgh_wino2d_input_act(A.data_ptr() + 4 * a_off, lda, C, B, H, W, ptr(lazy.scale), ptr(lazy.shift), lazy.act,
+                                            lazy.slope, ptr(V), _st()))
 
 
 def wino2d_bwd_transforms(dy, lddy, raw, ldraw, ybits, psc, psh, mean, invstd, coef, m1, m2, N, B, H, W, act, slope, want_dres):
     """-> (Vd, Gy, dres | None): see efgh_wino2d_bwd_transforms (include/efgh_hip.h)"""
-    T2 = _L().efgh_wino2d_tiles(c_int32(B), c_int32(H), c_int32(W))
+    T2 = _L().efgh_wino2d_tiles(B, H, W)
     dev = raw.device
     Vd = torch.empty((T2, 36, N), dtype=torch.float32, device=dev)
     Gy = torch.empty((T2, 36, N), dtype=torch.float32, device=dev)
     dres = torch.empty((B, H, W, N), dtype=torch.float32, device=dev) if want_dres else None
     LAZY_HITS[1] += 1
-    _C.check(_L().efgh_wino2d_bwd_transforms(ptr(dy), c_int64(lddy), ptr(raw), c_int64(ldraw), ptr(ybits), ptr(psc), ptr(psh), ptr(mean),
-                                             ptr(invstd), ptr(coef), ptr(m1), ptr(m2), c_int32(N), c_int32(B), c_int32(H), c_int32(W),
-                                             c_int32(act), c_float(slope), ptr(Vd), ptr(Gy), ptr(dres), c_int64(N), _st()))
+    _C.check(_L().efgh_wino2d_bwd_transforms(ptr(dy), lddy, ptr(raw), ldraw, ptr(ybits), ptr(psc), ptr(psh), ptr(mean), ptr(invstd),
+                                             ptr(coef), ptr(m1), ptr(m2), N, B, H, W, act, slope, ptr(Vd), ptr(Gy), ptr(dres), N,
+                                             _st()))
     return Vd, Gy, dres
 
 
 def _wino2d_forward(d, A, a_off, lda, C, N, geom, Wp, pool=False, lazy=None, pre_v=None):
     """input transform -> 36 batched GEMMs -> output transform with the layer's epilogue (descriptor d)"""
     B, H, W = geom[0], geom[1], geom[2]
-    T = _L().efgh_wino2d_tiles(c_int32(B), c_int32(H), c_int32(W))
+    T = _L().efgh_wino2d_tiles(B, H, W)
     dev = A.device if A is not None else pre_v.device
     Mb = torch.empty((T, 36, N), dtype=torch.float32, device=dev)
     if pre_v is not None:
@@ -915,17 +899,15 @@ def bn_finalize(stats, G, C, count, gamma, beta, rmean, rvar, momentum, eps, sav
     shift = torch.empty(C, dtype=torch.float32, device=dev)
     sm = torch.empty(C, dtype=torch.float32, device=dev) if save else None
     si = torch.empty(C, dtype=torch.float32, device=dev) if save else None
-    _C.check(_L().efgh_bn_finalize(ptr(stats), c_int32(G), c_int32(C), ctypes.c_double(count), ptr(gamma), ptr(beta),
-                                   ptr(rmean), ptr(rvar), c_float(momentum), c_float(eps), ptr(scale), ptr(shift),
-                                   ptr(sm), ptr(si), _st()))
+    _C.check(_L().efgh_bn_finalize(ptr(stats), G, C, count, ptr(gamma), ptr(beta), ptr(rmean), ptr(rvar), momentum, eps, ptr(scale),
+                                   ptr(shift), ptr(sm), ptr(si), _st()))
     return scale, shift, sm, si
 
 
 def col_stats(x, M, C, ld, x_off=0):
-    G = _L().efgh_col_stats_groups(c_int64(M))
+    G = _L().efgh_col_stats_groups(M)
     stats = torch.empty((G, 2, C), dtype=torch.float32, device=x.device)
-    _C.check(_L().efgh_col_stats(_C.c_void_p(x.data_ptr() + 4 * x_off), c_int64(M), c_int32(C), c_int64(ld),
-                                 ptr(stats), _st()))
+    _C.check(_L().efgh_col_stats(x.data_ptr() + 4 * x_off, M, C, ld, ptr(stats), _st()))
     return stats, G
 
 
@@ -934,22 +916,18 @@ def scale_shift_act(x, ldx, scale, shift, y, ldy, M, C, act=ACT_NONE, slope=0.0,
     """bits: an int32 tensor of M*C/32 words that receives the sign bits of y (efgh_scale_shift_act_bits; C % 32 == 0)"""
     if bits is not None:
         _C.check(_L().efgh_scale_shift_act_bits(
-            _C.c_void_p(x.data_ptr() + 4 * x_off), c_int64(ldx), ptr(scale), ptr(shift),
-            _C.c_void_p(0 if res is None else res.data_ptr() + 4 * res_off), c_int64(ldr),
-            _C.c_void_p(y.data_ptr() + 4 * y_off), c_int64(ldy), ptr(bits), c_int64(M), c_int32(C), c_int32(act), c_float(slope),
-            _st()))
+            x.data_ptr() + 4 * x_off, ldx, ptr(scale), ptr(shift), 0 if res is None else res.data_ptr() + 4 * res_off, ldr,
+            y.data_ptr() + 4 * y_off, ldy, ptr(bits), M, C, act, slope, _st()))
         return
     _C.check(_L().efgh_scale_shift_act(
-        _C.c_void_p(x.data_ptr() + 4 * x_off), c_int64(ldx), ptr(scale), ptr(shift),
-        _C.c_void_p(0 if res is None else res.data_ptr() + 4 * res_off), c_int64(ldr),
-        _C.c_void_p(y.data_ptr() + 4 * y_off), c_int64(ldy), c_int64(M), c_int32(C), c_int32(act), c_float(slope),
-        _st()))
+        x.data_ptr() + 4 * x_off, ldx, ptr(scale), ptr(shift), 0 if res is None else res.data_ptr() + 4 * res_off, ldr,
+        y.data_ptr() + 4 * y_off, ldy, M, C, act, slope, _st()))
 
 
 def maxpool2(x):
     B, H, W, C = x.shape
     y = torch.empty((B, H // 2, W // 2, C), dtype=torch.float32, device=x.device)
-    _C.check(_L().efgh_maxpool2(ptr(x), ptr(y), c_int32(B), c_int32(H), c_int32(W), c_int32(C), _st()))
+    _C.check(_L().efgh_maxpool2(ptr(x), ptr(y), B, H, W, C, _st()))
     return y
 
 
@@ -957,7 +935,7 @@ def maxpool_v2(x):
     """the vertical half of MaxPool2d(2,2): [B][H][W][C] -> [B][H/2][W][C]"""
     B, H, W, C = x.shape
     y = torch.empty((B, H // 2, W, C), dtype=torch.float32, device=x.device)
-    _C.check(_L().efgh_maxpool_v2(ptr(x), ptr(y), c_int32(B), c_int32(H), c_int32(W), c_int32(C), _st()))
+    _C.check(_L().efgh_maxpool_v2(ptr(x), ptr(y), B, H, W, C, _st()))
     return y
 
 
@@ -965,16 +943,14 @@ def maxpool2_affine(raw, scale, shift, act, slope=0.0):
     """max pool of act(raw*scale + shift) without materialising the activation; raw [B][H][W][C]"""
     B, H, W, C = raw.shape
     y = torch.empty((B, H // 2, W // 2, C), dtype=torch.float32, device=raw.device)
-    _C.check(_L().efgh_maxpool2_affine(ptr(raw), ptr(scale), ptr(shift), c_int32(act), c_float(slope), ptr(y), c_int32(B),
-                                       c_int32(H), c_int32(W), c_int32(C), _st()))
+    _C.check(_L().efgh_maxpool2_affine(ptr(raw), ptr(scale), ptr(shift), act, slope, ptr(y), B, H, W, C, _st()))
     return y
 
 
 def maxpool2_bwd_affine(raw, scale, shift, act, slope, dy):
     B, H, W, C = raw.shape
     dx = torch.zeros_like(raw) if (H % 2 or W % 2) else torch.empty_like(raw)
-    _C.check(_L().efgh_maxpool2_bwd_affine(ptr(raw), ptr(scale), ptr(shift), c_int32(act), c_float(slope), ptr(dy), ptr(dx),
-                                           c_int32(B), c_int32(H), c_int32(W), c_int32(C), _st()))
+    _C.check(_L().efgh_maxpool2_bwd_affine(ptr(raw), ptr(scale), ptr(shift), act, slope, ptr(dy), ptr(dx), B, H, W, C, _st()))
     return dx
 
 
@@ -988,7 +964,7 @@ def nchw_to_nhwc(x, Cd=None):
         HW *= s
     Cd = Cd or Cs
     y = torch.empty((B,) + sp + (Cd,), dtype=torch.float32, device=x.device)
-    _C.check(_L().efgh_nchw_to_nhwc(ptr(x), ptr(y), c_int32(B), c_int32(Cs), c_int64(HW), c_int32(Cd), _st()))
+    _C.check(_L().efgh_nchw_to_nhwc(ptr(x), ptr(y), B, Cs, HW, Cd, _st()))
     return y
 
 
@@ -1000,7 +976,7 @@ def nhwc_to_nchw(x, Cs=None):
         HW *= s
     Cs = Cs or ld
     y = torch.empty((B, Cs) + sp, dtype=torch.float32, device=x.device)
-    _C.check(_L().efgh_nhwc_to_nchw(ptr(x), c_int64(ld), ptr(y), c_int32(B), c_int32(Cs), c_int64(HW), _st()))
+    _C.check(_L().efgh_nhwc_to_nchw(ptr(x), ld, ptr(y), B, Cs, HW, _st()))
     return y
 
 
@@ -1008,7 +984,7 @@ SEGMENT_TWO_STAGE = True        # the per-sample reductions of E / H / G's heads
 
 
 def _segment_ws(C, nseg, device):
-    return _scratch((_L().efgh_segment_workspace(c_int32(C), c_int32(nseg)) + 3) // 4, device)
+    return _scratch((_L().efgh_segment_workspace(C, nseg) + 3) // 4, device)
 
 
 def segment_colmax(x, ld, C, seg, nseg, want_arg=False):
@@ -1016,20 +992,20 @@ def segment_colmax(x, ld, C, seg, nseg, want_arg=False):
     arg = torch.empty((nseg, C), dtype=torch.int32, device=x.device) if want_arg else None
     rows = x.numel() // ld
     if SEGMENT_TWO_STAGE and rows >= 2048:
-        _C.check(_L().efgh_segment_colmax_ws(ptr(x), c_int64(ld), c_int32(C), ptr(seg), c_int32(nseg), c_int64(rows), ptr(y), ptr(arg),
+        _C.check(_L().efgh_segment_colmax_ws(ptr(x), ld, C, ptr(seg), nseg, rows, ptr(y), ptr(arg),
                                              ptr(_segment_ws(C, nseg, x.device)), _st()))
     else:
-        _C.check(_L().efgh_segment_colmax(ptr(x), c_int64(ld), c_int32(C), ptr(seg), c_int32(nseg), ptr(y), ptr(arg), _st()))
+        _C.check(_L().efgh_segment_colmax(ptr(x), ld, C, ptr(seg), nseg, ptr(y), ptr(arg), _st()))
     return y, arg
 
 
 def segment_colmean(x, ld, C, rows_per_seg, nseg):
     y = torch.empty((nseg, C), dtype=torch.float32, device=x.device)
     if SEGMENT_TWO_STAGE and rows_per_seg >= 512:
-        _C.check(_L().efgh_segment_colmean_ws(ptr(x), c_int64(ld), c_int32(C), c_int32(rows_per_seg), c_int32(nseg), ptr(y),
-                                              ptr(_segment_ws(C, nseg, x.device)), _st()))
+        _C.check(_L().efgh_segment_colmean_ws(ptr(x), ld, C, rows_per_seg, nseg, ptr(y), ptr(_segment_ws(C, nseg, x.device)),
+                                              _st()))
     else:
-        _C.check(_L().efgh_segment_colmean(ptr(x), c_int64(ld), c_int32(C), c_int32(rows_per_seg), c_int32(nseg), ptr(y), _st()))
+        _C.check(_L().efgh_segment_colmean(ptr(x), ld, C, rows_per_seg, nseg, ptr(y), _st()))
     return y
 
 
@@ -1039,7 +1015,7 @@ def heads_to_nchw(x):
     assert ld == 4 and x.is_contiguous()
     depth = torch.empty((B, 1, H, W), dtype=torch.float32, device=x.device)
     mask = torch.empty((B, 2, H, W), dtype=torch.float32, device=x.device)
-    _C.check(_L().efgh_heads_to_nchw(ptr(x), ptr(depth), ptr(mask), c_int32(B), c_int64(H * W), _st()))
+    _C.check(_L().efgh_heads_to_nchw(ptr(x), ptr(depth), ptr(mask), B, H * W, _st()))
     return depth, mask
 
 
@@ -1047,14 +1023,14 @@ def heads_bwd(mask, dmask, ddepth):
     B, _, H, W = mask.shape
     dx = torch.empty((B, H, W, 4), dtype=torch.float32, device=mask.device)
     _C.check(_L().efgh_heads_bwd(ptr(mask), ptr(dmask) if dmask is not None else None, ptr(ddepth) if ddepth is not None else None,
-                                 c_int32(B), c_int64(H * W), ptr(dx), _st()))
+                                 B, H * W, ptr(dx), _st()))
     return dx
 
 
 def softmax2_to_nchw(x):
     B, H, W, ld = x.shape
     y = torch.empty((B, 2, H, W), dtype=torch.float32, device=x.device)
-    _C.check(_L().efgh_softmax2_to_nchw(ptr(x), c_int64(ld), ptr(y), c_int32(B), c_int64(H * W), _st()))
+    _C.check(_L().efgh_softmax2_to_nchw(ptr(x), ld, ptr(y), B, H * W, _st()))
     return y
 
 
@@ -1091,9 +1067,9 @@ def splat_fwd(lv, feat, Cf, use_emg=True, normalize=True):
     splat = torch.empty((H, C), dtype=torch.float32, device=feat.device)
     wsum = torch.empty((H,), dtype=torch.float32, device=feat.device)
     with _bcl_prof('splat', float(n) * (4 * C + 48) + float(H) * (4 * C + 4)):                 # SURVEY 8d bytes
-        _C.check(_L().efgh_splat_gather(ptr(lv.emg_pm if use_emg else None), ptr(feat), c_int64(feat.stride(0)), c_int32(Cf),
-                                        ptr(lv.bary_pm), ptr(lv.list), ptr(lv.vseg), c_int32(H), c_int32(max(1, 4 * n // max(H, 1))), c_int32(SPLAT_LANES), c_int32(1 if normalize else 0), ptr(splat),
-                                        ptr(wsum), _st()))
+        _C.check(_L().efgh_splat_gather(ptr(lv.emg_pm if use_emg else None), ptr(feat), feat.stride(0), Cf, ptr(lv.bary_pm),
+                                        ptr(lv.list), ptr(lv.vseg), H, max(1, 4 * n // max(H, 1)), SPLAT_LANES,
+                                        1 if normalize else 0, ptr(splat), ptr(wsum), _st()))
     return splat, wsum
 
 
@@ -1101,8 +1077,8 @@ def splat_bwd(lv, gsplat, wsum, Cf, gfeat, use_emg=True, normalize=True):
     """gradient of splat_fwd w.r.t. feat[:, :Cf] (el_minus_gr carries none) -> gfeat [n][ld]"""
     C = gsplat.shape[1]
     with _bcl_prof('splat bwd', float(lv.n_in) * (4 * C + 48) + float(lv.H) * (4 * C + 4)):
-        _C.check(_L().efgh_splat_bwd(ptr(gsplat), c_int32(C), c_int32(4 if use_emg else 0), ptr(wsum), c_int32(Cf), ptr(lv.bary_pm),
-                                     ptr(lv.off_pm), c_int32(lv.n_in), ptr(gfeat), c_int64(gfeat.stride(0)), c_int32(1 if normalize else 0), _st()))
+        _C.check(_L().efgh_splat_bwd(ptr(gsplat), C, 4 if use_emg else 0, ptr(wsum), Cf, ptr(lv.bary_pm), ptr(lv.off_pm), lv.n_in,
+                                     ptr(gfeat), gfeat.stride(0), 1 if normalize else 0, _st()))
 
 
 def neighbor_gather_adjoint(lv, src, C):
@@ -1110,9 +1086,8 @@ def neighbor_gather_adjoint(lv, src, C):
     from .lattice import ALIAS_CAP, INFO_ALIAS
     dst = torch.empty((lv.H, C), dtype=torch.float32, device=src.device)
     with _bcl_prof('gather bwd', float(lv.H) * (4 * C + 15 * 8 + 4 * C)):
-        _C.check(_L().efgh_table_gather_transposed(ptr(src), ptr(lv.nbr), c_int32(lv.H), c_int32(C), ptr(lv.alist),
-                                                   _C.c_void_p(lv.info.data_ptr() + 4 * INFO_ALIAS), c_int32(ALIAS_CAP), ptr(dst),
-                                                   _st()))
+        _C.check(_L().efgh_table_gather_transposed(ptr(src), ptr(lv.nbr), lv.H, C, ptr(lv.alist),
+                                                   lv.info.data_ptr() + 4 * INFO_ALIAS, ALIAS_CAP, ptr(dst), _st()))
     return dst
 
 
@@ -1146,8 +1121,8 @@ def slice_fwd(pts, feat, C, bias=None, out=None):
             raise _C.EfghError('slice: out = ([>= %d][ldo] float32 buffer, column offset) with %d columns from a multiple of 4 expected'
                                % (pts.n_out, C))
     with _bcl_prof('slice', _slice_bytes(pts.n_out, pts.H, C)):
-        _C.check(_L().efgh_slice(ptr(feat), c_int64(feat.stride(0)), c_int32(pts.H), ptr(pts.bary), ptr(pts.off), c_int32(pts.n_out),
-                                 c_int32(C), ptr(bias), ptr(buf), c_int64(buf.stride(0)), c_int32(ooff), _st()))
+        _C.check(_L().efgh_slice(ptr(feat), feat.stride(0), pts.H, ptr(pts.bary), ptr(pts.off), pts.n_out, C, ptr(bias), ptr(buf),
+                                 buf.stride(0), ooff, _st()))
     return buf
 
 
@@ -1163,9 +1138,9 @@ def offsets_invert(off, H):
     vseg = torch.empty((H, 2), dtype=torch.int32, device=dev)
     lst = torch.empty(4 * n_out, dtype=torch.int32, device=dev)
     err = torch.empty(1, dtype=torch.int32, device=dev)
-    ws = torch.empty(L.efgh_offsets_invert_workspace(c_int32(n_out), c_int32(H)), dtype=torch.uint8, device=dev)
+    ws = torch.empty(L.efgh_offsets_invert_workspace(n_out, H), dtype=torch.uint8, device=dev)
     with _bcl_prof('offsets invert', float(n_out) * 16 * 5 + float(H) * 24):      # off x3, scratch list w + r, list w; counts, vseg
-        _C.check(L.efgh_offsets_invert(ptr(off), c_int32(n_out), c_int32(H), ptr(vseg), ptr(lst), ptr(err), ptr(ws), _st()))
+        _C.check(L.efgh_offsets_invert(ptr(off), n_out, H, ptr(vseg), ptr(lst), ptr(err), ptr(ws), _st()))
     return vseg, lst, err
 
 
@@ -1173,10 +1148,10 @@ def lattice_index(pts, cstride, sid, pps, B, scale, lst, vseg, vsid, info, H):
     """the persistent vertex index of a finished lattice level (efgh_lattice_index_build): pts [3][cstride] / sid / pps / scale as the
     level was built from them, lst / vseg / vsid / info as the build left them, H vertex rows, B samples -> the index (uint8)"""
     L = _L()
-    index = torch.empty(L.efgh_lattice_index_bytes(c_int32(H), c_int32(B)), dtype=torch.uint8, device=info.device)
+    index = torch.empty(L.efgh_lattice_index_bytes(H, B), dtype=torch.uint8, device=info.device)
     with _bcl_prof('lattice index', float(H) * (12 + 16 * 2 + 24 + 16)):      # point + vertex records, vkeys w + r, table (2 slots), mm
-        _C.check(L.efgh_lattice_index_build(ptr(pts), c_int64(cstride), ptr(sid), c_int32(pps), c_int32(B), c_float(scale), ptr(lst),
-                                            ptr(vseg), ptr(vsid), ptr(info), c_int32(H), ptr(index), _st()))
+        _C.check(L.efgh_lattice_index_build(ptr(pts), cstride, ptr(sid), pps, B, scale, ptr(lst), ptr(vseg), ptr(vsid), ptr(info),
+                                            H, ptr(index), _st()))
     return index
 
 
@@ -1191,8 +1166,8 @@ def lattice_locate(index, q, cstride, qsid, qpps, n_q, scale, B, H, info):
     off = torch.empty((n_q, 4), dtype=torch.int32, device=dev)
     counters = torch.zeros(2, dtype=torch.int32, device=dev)
     with _bcl_prof('lattice locate', float(n_q) * (12 + 32 + 4 * 12)):        # point, bary + off, four probes (key + value)
-        _C.check(_L().efgh_lattice_locate(ptr(q), c_int64(cstride), ptr(qsid), c_int32(qpps), c_int32(n_q), c_float(scale), ptr(index),
-                                          c_int32(B), c_int32(H), ptr(info), ptr(bary), ptr(off), ptr(counters), _st()))
+        _C.check(_L().efgh_lattice_locate(ptr(q), cstride, ptr(qsid), qpps, n_q, scale, ptr(index), B, H, ptr(info), ptr(bary),
+                                          ptr(off), ptr(counters), _st()))
     return bary, off, counters
 
 
@@ -1216,11 +1191,10 @@ def slice_bwd(pts, gout, C, ooff=0, want_bias=False, gfeat=None):
     gbias = ws = None
     if want_bias:
         gbias = torch.empty(C, dtype=torch.float32, device=dev)
-        ws = torch.empty(_L().efgh_slice_bwd_workspace(c_int32(C)), dtype=torch.uint8, device=dev)
+        ws = torch.empty(_L().efgh_slice_bwd_workspace(C), dtype=torch.uint8, device=dev)
     with _bcl_prof('slice bwd', _slice_bytes(pts.n_out, pts.H, C) + (4.0 * C * pts.n_out if want_bias else 0.0)):
-        _C.check(_L().efgh_slice_bwd(ptr(gout), c_int64(gout.stride(0)), c_int32(ooff), c_int32(C), ptr(pts.bary), ptr(lst), ptr(vseg),
-                                     c_int32(pts.H), c_int32(pts.n_out), c_int32(SPLAT_LANES), ptr(gfeat), c_int64(gfeat.stride(0)),
-                                     ptr(gbias), ptr(ws), _st()))
+        _C.check(_L().efgh_slice_bwd(ptr(gout), gout.stride(0), ooff, C, ptr(pts.bary), ptr(lst), ptr(vseg), pts.H, pts.n_out,
+                                     SPLAT_LANES, ptr(gfeat), gfeat.stride(0), ptr(gbias), ptr(ws), _st()))
     return gfeat, gbias
 
 
@@ -1239,8 +1213,7 @@ def bwd_finalize_f32(stats, C, count):
     s2 = torch.empty(C, dtype=torch.float32, device=dev)
     m1 = torch.empty(C, dtype=torch.float64, device=dev)
     m2 = torch.empty(C, dtype=torch.float64, device=dev)
-    _C.check(_L().efgh_bwd_finalize_f32(ptr(stats), c_int32(stats.shape[0]), c_int32(C), ctypes.c_double(count), ptr(s1), ptr(s2),
-                                        ptr(m1), ptr(m2), _st()))
+    _C.check(_L().efgh_bwd_finalize_f32(ptr(stats), stats.shape[0], C, count, ptr(s1), ptr(s2), ptr(m1), ptr(m2), _st()))
     return s1, s2, m1, m2
 
 
@@ -1266,9 +1239,8 @@ def blur_dgrad(lv, draw, C0, w, C):
         return dx
     wd = w.detach()
     assert wd.is_contiguous() and wd.numel() == C0 * C * 15
-    _C.check(_L().efgh_blur_dgrad_alias(ptr(draw), c_int64(draw.stride(0)), c_int32(C0), ptr(wd), c_int32(C), ptr(lv.alist),
-                                        _C.c_void_p(lv.info.data_ptr() + 4 * INFO_ALIAS), c_int32(ALIAS_CAP), ptr(dx), c_int64(C),
-                                        _st()))
+    _C.check(_L().efgh_blur_dgrad_alias(ptr(draw), draw.stride(0), C0, ptr(wd), C, ptr(lv.alist),
+                                        lv.info.data_ptr() + 4 * INFO_ALIAS, ALIAS_CAP, ptr(dx), C, _st()))
     return dx
 
 
@@ -1291,7 +1263,7 @@ def blur_r_gemm(A, lda, C, F, Wp, N, M, out, ldo, table, bias=None, act=ACT_NONE
     (efgh_blur_r_gemm; a missing neighbour reads zeros).  hit: which BLUR_R_HITS counter the launch counts in"""
     d, ld = _blur_r_desc(A, lda, C, F, N, M, table, a_off=a_off, Wp=Wp, out=out, ldo=ldo, out_off=out_off, bias=bias, act=act, slope=slope)
     ev = _prof_start(PROFILE)
-    _C.check(_L().efgh_blur_r_gemm(ctypes.byref(d), c_int32(ld), _st()))
+    _C.check(_L().efgh_blur_r_gemm(ctypes.byref(d), ld, _st()))
     BLUR_R_HITS[hit] += 1
     _prof_end(ev, 'blur_r', (MODE_BLUR_R, M, N, F, C), float(flops) if flops is not None else 2.0 * M * N * F * C, PROFILE)
 
@@ -1300,7 +1272,7 @@ def blur_r_wgrad(A, lda, C, F, N, M, G, ldg, dWp, table):
     """dWp[n][t*C + c] = sum_m G[m][n] * A[table[m][t]][c]   (efgh_blur_r_wgrad; dWp [N][F][C], N % 4 == 0)"""
     d, ld = _blur_r_desc(A, lda, C, F, N, M, table)
     ev = _prof_start(PROFILE_WGRAD)
-    _C.check(_L().efgh_blur_r_wgrad(ctypes.byref(d), c_int32(ld), ptr(G), c_int64(ldg), ptr(dWp),
+    _C.check(_L().efgh_blur_r_wgrad(ctypes.byref(d), ld, ptr(G), ldg, ptr(dWp),
                                     ptr(_scratch(_L().efgh_gather_wgrad_workspace(ctypes.byref(d)), dWp.device)), _st()))
     BLUR_R_HITS[2] += 1
     _prof_end(ev, 'blur_r', (MODE_BLUR_R, M, N, F, C), 2.0 * M * N * F * C, PROFILE_WGRAD)
@@ -1353,9 +1325,7 @@ def range_image(pc, e_l, H, W, fov_up, fov_down):
     vals = torch.empty((B, N, 4), dtype=torch.float32, device=dev)
     win = torch.empty((B, H * W), dtype=torch.int32, device=dev)
     img = torch.empty((B, H, W, 4), dtype=torch.float32, device=dev)
-    _C.check(_L().efgh_range_image(ptr(pc), ptr(e_l), c_int32(B), c_int32(N), c_int32(H), c_int32(W),
-                                   ctypes.c_double(fov_up), ctypes.c_double(fov_down), ptr(pix), ptr(vals),
-                                   ptr(win), ptr(img), _st()))
+    _C.check(_L().efgh_range_image(ptr(pc), ptr(e_l), B, N, H, W, fov_up, fov_down, ptr(pix), ptr(vals), ptr(win), ptr(img), _st()))
     return img, pix
 
 
@@ -1368,8 +1338,7 @@ def depth_image(pc, cam_T_velo, H, W):
     vals = torch.empty((B, N, 4), dtype=torch.float32, device=dev)
     win = torch.empty((B, H * W), dtype=torch.int32, device=dev)
     img = torch.empty((B, H, W, 4), dtype=torch.float32, device=dev)
-    _C.check(_L().efgh_depth_image(ptr(pc), ptr(P), c_int32(B), c_int32(N), c_int32(H), c_int32(W), ptr(pix),
-                                   ptr(vals), ptr(win), ptr(img), _st()))
+    _C.check(_L().efgh_depth_image(ptr(pc), ptr(P), B, N, H, W, ptr(pix), ptr(vals), ptr(win), ptr(img), _st()))
     return img, pix
 
 
@@ -1379,8 +1348,7 @@ def rotate_nearest_u8(img, rot_deg, want_nchw=True, want_nhwc4=True):
     B, _, H, W = img.shape
     o1 = torch.empty((B, 3, H, W), dtype=torch.float32, device=img.device) if want_nchw else None
     o2 = torch.empty((B, H, W, 4), dtype=torch.float32, device=img.device) if want_nhwc4 else None
-    _C.check(_L().efgh_rotate_nearest_u8(ptr(img), ptr(rot_deg.detach().contiguous().float()), c_int32(B), c_int32(H),
-                                         c_int32(W), ptr(o1), ptr(o2), _st()))
+    _C.check(_L().efgh_rotate_nearest_u8(ptr(img), ptr(rot_deg.detach().contiguous().float()), B, H, W, ptr(o1), ptr(o2), _st()))
     return o1, o2
 
 
@@ -1391,10 +1359,10 @@ def minmax(x):
     """x [B][...] -> (B,2) per-sample (min,max)"""
     B = x.shape[0]
     n = x.numel() // B
-    G = _L().efgh_minmax_groups(c_int64(n))
+    G = _L().efgh_minmax_groups(n)
     part = torch.empty((B, G, 2), dtype=torch.float32, device=x.device)
     mm = torch.empty((B, 2), dtype=torch.float32, device=x.device)
-    _C.check(_L().efgh_minmax(ptr(x), c_int32(B), c_int64(n), ptr(part), ptr(mm), _st()))
+    _C.check(_L().efgh_minmax(ptr(x), B, n, ptr(part), ptr(mm), _st()))
     return mm
 
 
@@ -1419,28 +1387,24 @@ def corr_head(cam, rng, want_logit=False, want_aux=False):
     mfma = USE_MFMA_CORR and (not want_aux or h * 16 >= 128) and h * segw * 16 < 65536 and nseg <= 32
     wpitch = wp + segw if mfma else wp
     rp = torch.empty((B, h, wpitch, C), dtype=torch.float32, device=dev)
-    _C.check(_L().efgh_corr_pad(ptr(rng), ptr(rng_mm), c_int32(B), c_int32(h), c_int32(wr), c_int32(C),
-                                c_int32(off), c_int32(wpitch), ptr(rp), _st()))
+    _C.check(_L().efgh_corr_pad(ptr(rng), ptr(rng_mm), B, h, wr, C, off, wpitch, ptr(rp), _st()))
     if mfma:
         # MFMA formulation: camera-row segments become the N dimension, groups of image rows the batch (split-K)
         nsplit = max(d for d in range(1, 17) if h % d == 0)
         T = h // nsplit
         nseg_real = (wc + segw - 1) // segw
         Wc = torch.empty((B, nsplit, nseg, T, segw * 16), dtype=torch.float32, device=dev)
-        _C.check(_L().efgh_corr_pack_cam(ptr(cam), ptr(cam_mm), c_int32(B), c_int32(h), c_int32(wc), c_int32(segw),
-                                         c_int32(nseg), c_int32(nsplit), ptr(Wc), _st()))
+        _C.check(_L().efgh_corr_pack_cam(ptr(cam), ptr(cam_mm), B, h, wc, segw, nseg, nsplit, ptr(Wc), _st()))
         P = torch.empty((B, nsplit, wp, nseg), dtype=torch.float32, device=dev)
         geom = (1, T, wpitch, 1, wp, 1, 1, [], [], 1, wp, 1, 1, 0, 0)
         gather_gemm(rp, 16, segw * 16, T, Wc, nseg, wp, P, nseg, mode=3, geom=geom, flops=2.0 * B * nj * h * wc * 16,
                     batch=(B * nsplit, T * wpitch * 16, nseg * T * segw * 16, wp * nseg))
-        _C.check(_L().efgh_corr_fold(ptr(P), c_int32(B), c_int32(nsplit), c_int64(wp), c_int32(nseg),
-                                     c_int32(nseg_real), c_int32(segw), c_int32(nj), ptr(logit), ptr(score), _st()))
+        _C.check(_L().efgh_corr_fold(ptr(P), B, nsplit, wp, nseg, nseg_real, segw, nj, ptr(logit), ptr(score), _st()))
         if want_aux:
             return score, logit, rp, cam_mm, rng_mm
         return score, logit
     part = torch.empty((B, h, nj), dtype=torch.float32, device=dev)
-    _C.check(_L().efgh_corr1d(ptr(rp), ptr(cam), ptr(cam_mm), c_int32(B), c_int32(h), c_int32(wc), c_int32(wp),
-                              ptr(part), ptr(logit), ptr(score), _st()))
+    _C.check(_L().efgh_corr1d(ptr(rp), ptr(cam), ptr(cam_mm), B, h, wc, wp, ptr(part), ptr(logit), ptr(score), _st()))
     if want_aux:
         return score, logit, rp, cam_mm, rng_mm
     return score, logit
@@ -1506,7 +1470,7 @@ def _scratch(nfloats, device):
     nfloats = int(nfloats)
     if nfloats <= 0:
         return None
-    key = (device.index, _C.stream_ptr().value, threading.get_ident())      # (autograd's device thread is its own)
+    key = (device.index, _C.stream_ptr(), threading.get_ident())      # (autograd's device thread is its own)
     t = _SCRATCH.get(key)
     if t is None or t.numel() < nfloats:
         t = _SCRATCH[key] = torch.empty(max(nfloats, 1 << 22), dtype=torch.float32, device=device)
@@ -1565,7 +1529,7 @@ def gather_wgrad(A, lda, C, T, N, M, G, ldg, dWp, mode=0, geom=None, table=None,
     # default, and EFGH_DETERMINISTIC has nothing left to switch)
     if route == 'wino2d':
         B, H, W = geom[0], geom[1], geom[2]
-        T2 = _L().efgh_wino2d_tiles(c_int32(B), c_int32(H), c_int32(W))
+        T2 = _L().efgh_wino2d_tiles(B, H, W)
         dev = dWp.device
         with _LOCK:
             kept = W2V_CACHE.pop((A.data_ptr(), lda, C, B, H, W), None)
@@ -1582,28 +1546,28 @@ def gather_wgrad(A, lda, C, T, N, M, G, ldg, dWp, mode=0, geom=None, table=None,
             Gy = pre_gy
         else:
             Gy = torch.empty((T2, 36, N), dtype=torch.float32, device=dev)
-            _C.check(_L().efgh_wino2d_dy(ptr(G), c_int64(ldg), c_int32(N), c_int32(B), c_int32(H), c_int32(W), ptr(Gy), _st()))
+            _C.check(_L().efgh_wino2d_dy(ptr(G), ldg, N, B, H, W, ptr(Gy), _st()))
         g = _desc(V, 36 * C, C, 1, 0, N, T2, batch=(36, C, 0, 0))
         pv = _prof_start(PROFILE_WINO2D_GEMM)
-        if PLANE_DMA and _L().efgh_plane_wgrad_supported(ctypes.byref(g), c_int64(36 * N)):
+        if PLANE_DMA and _L().efgh_plane_wgrad_supported(ctypes.byref(g), 36 * N):
             split = _planes_split_now()
             if split:
                 PLANE_SPLIT_HITS[1] += 1
-            fn = _L().efgh_plane_wgrad_x6_batched if split else _L().efgh_plane_wgrad_batched
-            _C.check(fn(ctypes.byref(g), ptr(Gy), c_int64(36 * N), c_int64(N), ptr(S), c_int64(N * C),
-                        ptr(_scratch(_L().efgh_plane_wgrad_workspace(ctypes.byref(g)), dev)), c_int32(PLANE_DMA_NBUF), _st()))
+            _C.check((_L().efgh_plane_wgrad_x6_batched if split else _L().efgh_plane_wgrad_batched)(
+                ctypes.byref(g), ptr(Gy), 36 * N, N, ptr(S), N * C,
+                ptr(_scratch(_L().efgh_plane_wgrad_workspace(ctypes.byref(g)), dev)), PLANE_DMA_NBUF, _st()))
         else:
-            _C.check(_L().efgh_gather_wgrad_batched(ctypes.byref(g), ptr(Gy), c_int64(36 * N), c_int64(N), ptr(S), c_int64(N * C),
+            _C.check(_L().efgh_gather_wgrad_batched(ctypes.byref(g), ptr(Gy), 36 * N, N, ptr(S), N * C,
                                                     ptr(_scratch(_L().efgh_gather_wgrad_workspace(ctypes.byref(g)), dev)), _st()))
         _prof_end(pv, 'planes', (0, T2, N, 36, C), 2.0 * 36 * T2 * C * N, PROFILE_WINO2D_GEMM)
-        done = _C.check_wrote(_L().efgh_wino2d_wfinish(ptr(S), ptr(dWp), c_int32(N), c_int32(C), odp, _st()))      # (only the finish kernel may write the reference layout)
+        done = _C.check_wrote(_L().efgh_wino2d_wfinish(ptr(S), ptr(dWp), N, C, odp, _st()))      # (only the finish kernel may write the reference layout)
     elif route == 'wino':
         S = _scratch(_L().efgh_wino_wgrad_workspace(ctypes.byref(d)), dWp.device)    # per-tile-range partials
-        done = _C.check_wrote(_L().efgh_wino_wgrad(ctypes.byref(d), ptr(G), c_int64(ldg), ptr(S), ptr(dWp), odp, _st()))
+        done = _C.check_wrote(_L().efgh_wino_wgrad(ctypes.byref(d), ptr(G), ldg, ptr(S), ptr(dWp), odp, _st()))
     else:
         entry, workspace = _WGRAD_ENTRY[route]
         S = _scratch(getattr(_L(), workspace)(ctypes.byref(d)), dWp.device)          # partial planes, folded in a fixed order
-        done = _C.check_wrote(getattr(_L(), entry)(ctypes.byref(d), ptr(G), c_int64(ldg), ptr(dWp), ptr(S), odp, _st()))
+        done = _C.check_wrote(getattr(_L(), entry)(ctypes.byref(d), ptr(G), ldg, ptr(dWp), ptr(S), odp, _st()))
     if done:
         FOLD_UNPACK_HITS[0] += 1
     if ev is not None:
@@ -1613,25 +1577,22 @@ def gather_wgrad(A, lda, C, T, N, M, G, ldg, dWp, mode=0, geom=None, table=None,
 
 def unpack_weight(Wp, W, N, T, C, Cp, sn, sc, st, taps, accumulate=False):
     tp = (ctypes.c_int32 * 16)(*([int(t) for t in taps] + [0] * (16 - len(taps))))
-    _C.check(_L().efgh_unpack_weight(ptr(Wp), ptr(W), c_int32(N), c_int32(T), c_int32(C), c_int32(Cp), c_int64(sn),
-                                     c_int64(sc), c_int64(st), tp, c_int32(1 if accumulate else 0), _st()))
+    _C.check(_L().efgh_unpack_weight(ptr(Wp), ptr(W), N, T, C, Cp, sn, sc, st, tp, 1 if accumulate else 0, _st()))
 
 
 def table_scatter_add(src, table, M, T, C, dst):
     """dst[table[m][t]][c] += src[m][t*C+c] (atomic form; the BCL uses neighbor_gather_adjoint)"""
-    _C.check(_L().efgh_table_scatter_add(ptr(src), ptr(table), c_int64(M), c_int32(T), c_int32(C), ptr(dst), _st()))
+    _C.check(_L().efgh_table_scatter_add(ptr(src), ptr(table), M, T, C, ptr(dst), _st()))
 
 
 def bwd_groups(M):
-    return _L().efgh_bwd_groups(c_int64(M))
+    return _L().efgh_bwd_groups(M)
 
 
 def act_bn_bwd_reduce(dy, lddy, y, ldy, raw, ldraw, mean, invstd, M, C, act, slope, part, s1, s2, m1, m2,
                       pscale=None, pshift=None):
-    _C.check(_L().efgh_act_bn_bwd_reduce(ptr(dy), c_int64(lddy), ptr(y), c_int64(ldy), ptr(raw), c_int64(ldraw),
-                                         ptr(mean), ptr(invstd), ptr(pscale), ptr(pshift), c_int64(M), c_int32(C),
-                                         c_int32(act),
-                                         c_float(slope), ptr(part), ptr(s1), ptr(s2), ptr(m1), ptr(m2), _st()))
+    _C.check(_L().efgh_act_bn_bwd_reduce(ptr(dy), lddy, ptr(y), ldy, ptr(raw), ldraw, ptr(mean), ptr(invstd), ptr(pscale),
+                                         ptr(pshift), M, C, act, slope, ptr(part), ptr(s1), ptr(s2), ptr(m1), ptr(m2), _st()))
 
 
 POOL_REDUCE_FROM_Y = True       # ReLU layers: the pooled BatchNorm-backward sums from the pooled gradient and the pooled activation only
@@ -1650,40 +1611,35 @@ def pool_bn_bwd(dy_pool, raw, mean, invstd, coef, pscale, pshift, act, slope, s1
     if (POOL_REDUCE_FROM_Y and y_pool is not None and act == ACT_RELU and y_pool.is_contiguous()
             and tuple(y_pool.shape) == (B, H // 2, W // 2, C)):
         # (y_pool: the layer's own output - the next layer's backward keeps it alive; the full-resolution raw map is not read)
-        G = _L().efgh_bwd_groups(c_int64(B * (H // 2) * (W // 2)))
+        G = _L().efgh_bwd_groups(B * (H // 2) * (W // 2))
         part = torch.empty((G, 2, C), dtype=torch.float64, device=dev)
-        _C.check(_L().efgh_pool_bn_bwd_reduce_pooled(ptr(dy_pool), ptr(y_pool), ptr(raw), ptr(mean), ptr(invstd), ptr(pscale), ptr(pshift),
-                                                     c_int32(B), c_int32(H), c_int32(W), c_int32(C), ptr(part), ptr(s1), ptr(s2), ptr(m1),
-                                                     ptr(m2), _st()))
+        _C.check(_L().efgh_pool_bn_bwd_reduce_pooled(ptr(dy_pool), ptr(y_pool), ptr(raw), ptr(mean), ptr(invstd), ptr(pscale),
+                                                     ptr(pshift), B, H, W, C, ptr(part), ptr(s1), ptr(s2), ptr(m1), ptr(m2), _st()))
     else:
-        G = _L().efgh_pool_bwd_groups(c_int32(B), c_int32(H), c_int32(W))
+        G = _L().efgh_pool_bwd_groups(B, H, W)
         part = torch.empty((G, 2, C), dtype=torch.float64, device=dev)
-        _C.check(_L().efgh_pool_bn_bwd_reduce(ptr(dy_pool), ptr(raw), ptr(mean), ptr(invstd), ptr(pscale), ptr(pshift), c_int32(B),
-                                              c_int32(H), c_int32(W), c_int32(C), c_int32(act), c_float(slope), ptr(part), ptr(s1),
-                                              ptr(s2), ptr(m1), ptr(m2), _st()))
+        _C.check(_L().efgh_pool_bn_bwd_reduce(ptr(dy_pool), ptr(raw), ptr(mean), ptr(invstd), ptr(pscale), ptr(pshift), B, H, W, C,
+                                              act, slope, ptr(part), ptr(s1), ptr(s2), ptr(m1), ptr(m2), _st()))
     if transforms:
-        T2 = _L().efgh_wino2d_tiles(c_int32(B), c_int32(H), c_int32(W))
+        T2 = _L().efgh_wino2d_tiles(B, H, W)
         Vd = torch.empty((T2, 36, C), dtype=torch.float32, device=dev)
         Gy = torch.empty((T2, 36, C), dtype=torch.float32, device=dev)
         LAZY_HITS[1] += 1
-        _C.check(_L().efgh_wino2d_bwd_transforms_pooled(ptr(dy_pool), c_int64(C), ptr(raw), c_int64(C), ptr(pscale), ptr(pshift), ptr(mean),
-                                                        ptr(invstd), ptr(coef), ptr(m1), ptr(m2), c_int32(C), c_int32(B), c_int32(H),
-                                                        c_int32(W), c_int32(act), c_float(slope), ptr(Vd), ptr(Gy), _st()))
+        _C.check(_L().efgh_wino2d_bwd_transforms_pooled(ptr(dy_pool), C, ptr(raw), C, ptr(pscale), ptr(pshift), ptr(mean),
+                                                        ptr(invstd), ptr(coef), ptr(m1), ptr(m2), C, B, H, W, act, slope, ptr(Vd),
+                                                        ptr(Gy), _st()))
         return (Vd, Gy), s1, s2
     draw = torch.empty_like(raw)
     _C.check(_L().efgh_pool_bn_bwd_apply(ptr(dy_pool), ptr(raw), ptr(mean), ptr(invstd), ptr(coef), ptr(m1), ptr(m2), ptr(pscale),
-                                         ptr(pshift), c_int32(B), c_int32(H), c_int32(W), c_int32(C), c_int32(act),
-                                         c_float(slope), ptr(draw), _st()))
+                                         ptr(pshift), B, H, W, C, act, slope, ptr(draw), _st()))
     return draw, s1, s2
 
 
 def act_bn_bwd_apply(dy, lddy, y, ldy, raw, ldraw, mean, invstd, coef, m1, m2, M, C, act, slope, draw, lddraw,
                      dres, lddres, pscale=None, pshift=None):
-    _C.check(_L().efgh_act_bn_bwd_apply(ptr(dy), c_int64(lddy), ptr(y), c_int64(ldy), ptr(raw), c_int64(ldraw),
-                                        ptr(mean), ptr(invstd), ptr(coef), ptr(m1), ptr(m2), ptr(pscale), ptr(pshift),
-                                        c_int64(M), c_int32(C),
-                                        c_int32(act), c_float(slope), ptr(draw), c_int64(lddraw), ptr(dres),
-                                        c_int64(lddres), _st()))
+    _C.check(_L().efgh_act_bn_bwd_apply(ptr(dy), lddy, ptr(y), ldy, ptr(raw), ldraw, ptr(mean), ptr(invstd), ptr(coef), ptr(m1),
+                                        ptr(m2), ptr(pscale), ptr(pshift), M, C, act, slope, ptr(draw), lddraw, ptr(dres), lddres,
+                                        _st()))
 
 
 def col_sum(x, M, C):
@@ -1693,27 +1649,25 @@ def col_sum(x, M, C):
 
 def maxpool2_bwd(x, dy, dx):
     B, H, W, C = x.shape
-    _C.check(_L().efgh_maxpool2_bwd(ptr(x), ptr(dy), ptr(dx), c_int32(B), c_int32(H), c_int32(W), c_int32(C), _st()))
+    _C.check(_L().efgh_maxpool2_bwd(ptr(x), ptr(dy), ptr(dx), B, H, W, C, _st()))
 
 
 def segment_colmax_bwd(dy, arg, nseg, C, dx, ld):
-    _C.check(_L().efgh_segment_colmax_bwd(ptr(dy), ptr(arg), c_int32(nseg), c_int32(C), ptr(dx), c_int64(ld), _st()))
+    _C.check(_L().efgh_segment_colmax_bwd(ptr(dy), ptr(arg), nseg, C, ptr(dx), ld, _st()))
 
 
 def segment_colmean_bwd(dy, P, nseg, C, dx, ld):
-    _C.check(_L().efgh_segment_colmean_bwd(ptr(dy), c_int32(P), c_int32(nseg), c_int32(C), ptr(dx), c_int64(ld),
-                                           _st()))
+    _C.check(_L().efgh_segment_colmean_bwd(ptr(dy), P, nseg, C, ptr(dx), ld, _st()))
 
 
 def softmax2_bwd(y, dy, dx):
     B, _, H, W = y.shape
-    _C.check(_L().efgh_softmax2_bwd(ptr(y), ptr(dy), c_int32(B), c_int64(H * W), ptr(dx), c_int64(dx.shape[-1]),
-                                    _st()))
+    _C.check(_L().efgh_softmax2_bwd(ptr(y), ptr(dy), B, H * W, ptr(dx), dx.shape[-1], _st()))
 
 
 def raster_bwd(pix, gimg, B, N, HW):
     gv = torch.empty((B, N, 4), dtype=torch.float32, device=gimg.device)
-    _C.check(_L().efgh_raster_bwd(ptr(pix), ptr(gimg), c_int32(B), c_int32(N), c_int64(HW), ptr(gv), _st()))
+    _C.check(_L().efgh_raster_bwd(ptr(pix), ptr(gimg), B, N, HW, ptr(gv), _st()))
     return gv
 
 
@@ -1723,8 +1677,8 @@ def raster_pose_bwd(pix, gimg, pc, e_l, B, N, HW, mode):
     pc = pc.contiguous()
     part = torch.empty((B, 64, 16), dtype=torch.float64, device=gimg.device)
     out = torch.empty((B, 16 if mode == 0 else 12), dtype=torch.float32, device=gimg.device)
-    _C.check(_L().efgh_raster_pose_bwd(ptr(pix), ptr(gimg), ptr(pc), ptr(None if e_l is None else e_l.contiguous()), c_int32(B),
-                                       c_int32(N), c_int64(HW), c_int32(mode), ptr(part), ptr(out), _st()))
+    _C.check(_L().efgh_raster_pose_bwd(ptr(pix), ptr(gimg), ptr(pc), ptr(None if e_l is None else e_l.contiguous()), B, N, HW, mode,
+                                       ptr(part), ptr(out), _st()))
     return out
 
 
@@ -1736,15 +1690,11 @@ def corr1d_bwd_mfma(rp, cam, cam_mm, dl, B, h, wc, wp, rp_pitch=None):
     wpP, wcP = ceil4(wp), ceil4(wc)
     f = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
     rpT, camT = f(B, h * 16, wpP), f(B, h * 16, wcP)
-    _C.check(_L().efgh_corr_planes(ptr(rp), None, c_int32(B), c_int32(h), c_int32(wp), c_int32(rp_pitch), c_int32(wpP),
-                                   ptr(rpT), _st()))
-    _C.check(_L().efgh_corr_planes(ptr(cam), ptr(cam_mm), c_int32(B), c_int32(h), c_int32(wc), c_int32(wc), c_int32(wcP),
-                                   ptr(camT), _st()))
+    _C.check(_L().efgh_corr_planes(ptr(rp), None, B, h, wp, rp_pitch, wpP, ptr(rpT), _st()))
+    _C.check(_L().efgh_corr_planes(ptr(cam), ptr(cam_mm), B, h, wc, wc, wcP, ptr(camT), _st()))
     T, TT = f(B, wc, wpP), f(B, wp, wcP)
-    _C.check(_L().efgh_corr_toeplitz(ptr(dl), c_int32(B), c_int32(nj), c_int32(wc), c_int32(wp), c_int32(wpP), c_int32(0),
-                                     ptr(T), _st()))
-    _C.check(_L().efgh_corr_toeplitz(ptr(dl), c_int32(B), c_int32(nj), c_int32(wp), c_int32(wc), c_int32(wcP), c_int32(1),
-                                     ptr(TT), _st()))
+    _C.check(_L().efgh_corr_toeplitz(ptr(dl), B, nj, wc, wp, wpP, 0, ptr(T), _st()))
+    _C.check(_L().efgh_corr_toeplitz(ptr(dl), B, nj, wp, wc, wcP, 1, ptr(TT), _st()))
     dcamT, drpT = f(B, h * 16, wc), f(B, h * 16, wp)
     M = h * 16
     gather_gemm(rpT, wpP, wpP, 1, T, wc, M, dcamT, wc, mode=0, flops=2.0 * B * h * wc * 16 * nj,
@@ -1752,8 +1702,8 @@ def corr1d_bwd_mfma(rp, cam, cam_mm, dl, B, h, wc, wp, rp_pitch=None):
     gather_gemm(camT, wcP, wcP, 1, TT, wp, M, drpT, wp, mode=0, flops=2.0 * B * h * wc * 16 * nj,
                 batch=(B, M * wcP, wp * wcP, M * wp))
     dcam, drp = f(B, h, wc, 16), f(B, h, wp, 16)
-    _C.check(_L().efgh_corr_unplanes(ptr(dcamT), c_int32(B), c_int32(h), c_int32(wc), c_int32(wc), ptr(dcam), _st()))
-    _C.check(_L().efgh_corr_unplanes(ptr(drpT), c_int32(B), c_int32(h), c_int32(wp), c_int32(wp), ptr(drp), _st()))
+    _C.check(_L().efgh_corr_unplanes(ptr(dcamT), B, h, wc, wc, ptr(dcam), _st()))
+    _C.check(_L().efgh_corr_unplanes(ptr(drpT), B, h, wp, wp, ptr(drp), _st()))
     return dcam, drp
 
 
@@ -1764,8 +1714,7 @@ def corr1d_bwd(rp, cam, cam_mm, dl, B, h, wc, wp):
         return corr1d_bwd_mfma(rp, cam, cam_mm, dl, B, h, wc, wp, rp_pitch=pitch)
     dcam = torch.empty_like(cam)
     drp = torch.empty_like(rp)
-    _C.check(_L().efgh_corr1d_bwd(ptr(rp), ptr(cam), ptr(cam_mm), ptr(dl), c_int32(B), c_int32(h), c_int32(wc),
-                                  c_int32(wp), ptr(dcam), ptr(drp), _st()))
+    _C.check(_L().efgh_corr1d_bwd(ptr(rp), ptr(cam), ptr(cam_mm), ptr(dl), B, h, wc, wp, ptr(dcam), ptr(drp), _st()))
     return dcam, drp
 
 
@@ -1773,29 +1722,26 @@ def norm_bwd(x, dxn, mm):
     """gradient of x / (max(x) - min(x)) per sample given d/d(x_n); x, dxn [B][...] contiguous"""
     B = x.shape[0]
     n = x.numel() // B
-    G = _L().efgh_minmax_groups(c_int64(n))
+    G = _L().efgh_minmax_groups(n)
     part = torch.empty((B, G, 3), dtype=torch.float32, device=x.device)
     dx = torch.empty_like(x)
-    _C.check(_L().efgh_norm_bwd(ptr(x), ptr(dxn), ptr(mm), c_int32(B), c_int64(n), ptr(part), ptr(dx), _st()))
+    _C.check(_L().efgh_norm_bwd(ptr(x), ptr(dxn), ptr(mm), B, n, ptr(part), ptr(dx), _st()))
     return dx
 
 
 def corr_unpad(drp, B, h, w, C, off):
     dx = torch.empty((B, h, w, C), dtype=torch.float32, device=drp.device)
-    _C.check(_L().efgh_corr_unpad(ptr(drp), c_int32(B), c_int32(h), c_int32(w), c_int32(C), c_int32(off), ptr(dx),
-                                  _st()))
+    _C.check(_L().efgh_corr_unpad(ptr(drp), B, h, w, C, off, ptr(dx), _st()))
     return dx
 
 
 def convt_col2im(Y, B, Hin, Win, Ho, Wo, O, pad, scale, shift, act, slope, out):
-    _C.check(_L().efgh_convt_col2im(ptr(Y), c_int64(Y.shape[-1]), c_int32(B), c_int32(Hin), c_int32(Win), c_int32(Ho),
-                                    c_int32(Wo), c_int32(O), c_int32(pad), ptr(scale), ptr(shift), c_int32(act),
-                                    c_float(slope), ptr(out), c_int64(out.shape[-1]), _st()))
+    _C.check(_L().efgh_convt_col2im(ptr(Y), Y.shape[-1], B, Hin, Win, Ho, Wo, O, pad, ptr(scale), ptr(shift), act, slope, ptr(out),
+                                    out.shape[-1], _st()))
 
 
 def convt_im2col(G, B, Hin, Win, Ho, Wo, O, pad, Ycol):
-    _C.check(_L().efgh_convt_im2col(ptr(G), c_int64(G.shape[-1]), c_int32(B), c_int32(Hin), c_int32(Win), c_int32(Ho),
-                                    c_int32(Wo), c_int32(O), c_int32(pad), ptr(Ycol), c_int64(Ycol.shape[-1]), _st()))
+    _C.check(_L().efgh_convt_im2col(ptr(G), G.shape[-1], B, Hin, Win, Ho, Wo, O, pad, ptr(Ycol), Ycol.shape[-1], _st()))
 
 
 # ----------------------------------------------------------------------------------------------
@@ -1808,11 +1754,11 @@ def gimg_loss_fwd(pred_depth, pred_mask, gdep4, img_mask):
     gdep4, img_mask = gdep4.contiguous(), img_mask.contiguous()          # the kernel reads both densely
     gt_depth = torch.empty((B, 1, H, W), dtype=torch.float32, device=dev)
     gt_mask = torch.empty((B, 1, H, W), dtype=torch.float32, device=dev)
-    G = _L().efgh_gimg_loss_groups(c_int64(B * H * W))
+    G = _L().efgh_gimg_loss_groups(B * H * W)
     part = torch.empty((G, 3), dtype=torch.float64, device=dev)
     out3 = torch.empty(3, dtype=torch.float32, device=dev)
-    _C.check(_L().efgh_gimg_loss_fwd(ptr(pred_depth), ptr(pred_mask), c_int64(pred_mask.stride(0)), ptr(gdep4), ptr(img_mask),
-                                     c_int32(B), c_int64(H * W), ptr(gt_depth), ptr(gt_mask), ptr(part), ptr(out3), _st()))
+    _C.check(_L().efgh_gimg_loss_fwd(ptr(pred_depth), ptr(pred_mask), pred_mask.stride(0), ptr(gdep4), ptr(img_mask), B, H * W,
+                                     ptr(gt_depth), ptr(gt_mask), ptr(part), ptr(out3), _st()))
     return out3, gt_depth, gt_mask
 
 
@@ -1827,7 +1773,7 @@ def gimg_valid_count(gdep4, img_mask, count):
     B, H, W, _ = gdep4.shape
     if img_mask.numel() != B * H * W:
         raise _C.EfghError('gimg_valid_count: img_mask has %d elements, the depth image %d pixels' % (img_mask.numel(), B * H * W))
-    _C.check(_L().efgh_gimg_valid_count(ptr(gdep4), ptr(img_mask), c_int32(B), c_int64(H * W), ptr(count), _st()))
+    _C.check(_L().efgh_gimg_valid_count(ptr(gdep4), ptr(img_mask), B, H * W, ptr(count), _st()))
 
 
 def grad_drain(acc, g, first):
@@ -1836,7 +1782,7 @@ def grad_drain(acc, g, first):
     _C.require_f32(acc, g)
     if acc.numel() != g.numel() or not (acc.is_contiguous() and g.is_contiguous()):
         raise _C.EfghError('grad_drain: acc and g must be contiguous and of equal size')
-    _C.check(_L().efgh_grad_drain(ptr(acc), ptr(g), c_int64(g.numel()), c_int32(1 if first else 0), _st()))
+    _C.check(_L().efgh_grad_drain(ptr(acc), ptr(g), g.numel(), 1 if first else 0, _st()))
 
 
 def _ema_pair(name, a, b):
@@ -1942,7 +1888,6 @@ def gimg_loss_bwd(pred_depth, pred_mask, gt_depth, img_mask, out3, g_depth, g_ma
     gt_depth, img_mask = gt_depth.contiguous(), img_mask.contiguous()    # the kernel reads both densely
     d_depth = torch.empty_like(pred_depth)
     d_mask = torch.zeros_like(pred_mask)                   # channel 1 receives no gradient from this loss
-    _C.check(_L().efgh_gimg_loss_bwd(ptr(pred_depth), ptr(pred_mask), c_int64(pred_mask.stride(0)), ptr(gt_depth), ptr(img_mask),
-                                     c_int32(B), c_int64(H * W), ptr(out3), ptr(g_depth), ptr(g_mask), ptr(d_depth), ptr(d_mask),
-                                     c_int64(d_mask.stride(0)), _st()))
+    _C.check(_L().efgh_gimg_loss_bwd(ptr(pred_depth), ptr(pred_mask), pred_mask.stride(0), ptr(gt_depth), ptr(img_mask), B, H * W,
+                                     ptr(out3), ptr(g_depth), ptr(g_mask), ptr(d_depth), ptr(d_mask), d_mask.stride(0), _st()))
     return d_depth, d_mask

@@ -702,10 +702,8 @@ class FusedAdam:
             _C.check(lib.efgh_adam_step_guarded(f.w.data_ptr(), g.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), f.n, self.lr,
                                                 self.betas[0], self.betas[1], self.eps, self.wd, state.data_ptr(), _C.stream_ptr()))
         else:
-            _C.check(lib.efgh_adam_step(_C.ptr(f.w), _C.ptr(g), _C.ptr(self.m), _C.ptr(self.v), _C.c_int64(f.n),
-                                        _C.c_float(self.lr), _C.c_float(self.betas[0]), _C.c_float(self.betas[1]),
-                                        _C.c_float(self.eps), _C.c_float(self.wd), _C.c_int32(self.t),
-                                        _C.c_float(grad_scale), _C.stream_ptr()))
+            _C.check(lib.efgh_adam_step(_C.ptr(f.w), _C.ptr(g), _C.ptr(self.m), _C.ptr(self.v), f.n, self.lr, self.betas[0],
+                                        self.betas[1], self.eps, self.wd, self.t, grad_scale, _C.stream_ptr()))
         # packed-weight / folded-BN caches are stale now (also after a skipped step: the host does not know, a repack is harmless)
         ops.bump_epoch(f.epoch)
 

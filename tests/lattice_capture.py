@@ -16,6 +16,7 @@ import ctypes
 import hashlib
 import json
 import logging
+import numbers
 import os
 import struct
 import sys
@@ -45,6 +46,15 @@ def plan_of(mode):
     return [mode[0], int(mode[1]), int(mode[2]), bool(len(mode) > 3 and mode[3])]
 
 
+def typed_args(fn, args):
+    """the arguments of a library call as its argtypes (from include/efgh_hip.h) convert them: a plain number or None becomes the
+    instance of the declared scalar or void-pointer type, so a record tells a pointer from a size and a float by its fp32 bits;
+    a value the declared type refuses raises here as it would in the call"""
+    assert len(fn.argtypes) == len(args), (fn.__name__, len(args))
+    return [t(a) if issubclass(t, ctypes._SimpleCData) and (a is None or isinstance(a, numbers.Real)) else a
+            for t, a in zip(fn.argtypes, args)]
+
+
 class Capture(logging.Handler):
     """the stand-ins, installed for the life of a `with` block"""
 
@@ -66,6 +76,7 @@ class Capture(logging.Handler):
             return getattr(self.real, name)
 
         def entry(*args):
+            args = typed_args(getattr(self.real, name), args)
             self.calls.append([name[len('efgh_lattice_'):]] + [self._arg(a) for a in args])
             if name in ('efgh_lattice_part_build', 'efgh_lattice_level_build'):
                 self._counts(args)
@@ -118,7 +129,7 @@ class Capture(logging.Handler):
             return lv
         _C.lib = lambda: self
         _C.require_cuda = lambda *t: None
-        _C.stream_ptr = lambda: ctypes.c_void_p(0)
+        _C.stream_ptr = lambda: 0
         lat._level_arrays = level_arrays
         torch.cuda.Event = _Ev
         lat._log.addHandler(self)

@@ -19,6 +19,8 @@ import sys
 
 import torch
 
+from lattice_capture import typed_args
+
 QUERIES = ('_supported', '_workspace', '_tiles', '_stats_rows', '_grid_m', '_groups', 'efgh_last_error', 'efgh_version')
 LISTS = ('PROFILE', 'PROFILE_WGRAD', 'PROFILE_WINO', 'PROFILE_WINO_WGRAD', 'PROFILE_WINO2D', 'PROFILE_WINO2D_GEMM', 'PROFILE_THIN',
          'PROFILE_DED')
@@ -66,6 +68,7 @@ class Capture:
             return getattr(self.real, name)
 
         def entry(*args):
+            args = typed_args(getattr(self.real, name), args)
             self.calls.append(name)
             self.digest.append([name] + [self._arg(a) for a in args])
             return 1 if any(isinstance(getattr(a, '_obj', None), self._C.WgradOutDesc) for a in args) else 0
@@ -100,7 +103,7 @@ class Capture:
         self.saved += [(ops, k, getattr(ops, k)) for k in LISTS + OFF_IN_TURN + THRESHOLDS
                        + ('PLANES_SPLIT', 'KSPLIT_MAX_ROWS', 'BN_BWD_FUSED', 'BN_BWD_FUSED_2D', 'FOLD_UNPACK', 'W2V_KEEP')]
         ops._L = lambda: self
-        ops._st = _C.stream_ptr = lambda: ctypes.c_void_p(0)
+        ops._st = _C.stream_ptr = lambda: 0
         torch.cuda.Event = _Ev
         torch.cuda.current_stream = lambda *a: None
         torch.Tensor.record_stream = lambda t, s: None

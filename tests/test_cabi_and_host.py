@@ -60,17 +60,27 @@ def test_corr1d_bwd_checks_its_lds_size_before_the_first_launch(so_path):
 
 
 def test_gemm_desc_layout_matches_header():
+    """every struct of the header against its ctypes mirror: one C probe, generated from the mirrors' _fields_, prints sizeof and
+    each field's offsetof and size under the header's own field names (LP64).  A renamed, missing or reordered field fails to
+    compile or to match"""
     from efgh_amd import _C
-    # sizeof(efgh_gemm_desc) as the C compiler lays it out (LP64): checked against a tiny C probe
-    import subprocess, tempfile
-    src = '#include <stdio.h>\n#include "efgh_hip.h"\nint main(){printf("%zu %zu %zu",sizeof(efgh_gemm_desc),' \
-          '__builtin_offsetof(efgh_gemm_desc,table),__builtin_offsetof(efgh_gemm_desc,stats));return 0;}'
+    import re, subprocess, tempfile
+    hdr = re.sub(r'/\*.*?\*/', ' ', open(os.path.join(ROOT, 'include', 'efgh_hip.h')).read(), flags=re.S)
+    assert sorted(_C.STRUCTS) == sorted(re.findall(r'\}\s*(efgh_\w+)\s*;', hdr)) and len(_C.STRUCTS) == 8
+    lines = []
+    for cname, mirror in _C.STRUCTS.items():
+        lines.append('printf("%%zu\\n", sizeof(%s));' % cname)
+        lines += ['printf("%%zu %%zu\\n", offsetof(%s, %s), sizeof(((%s *)0)->%s));' % (cname, f[0], cname, f[0]) for f in mirror._fields_]
+    src = '#include <stdio.h>\n#include <stddef.h>\n#include "efgh_hip.h"\nint main(void){\n%s\nreturn 0;}\n' % '\n'.join(lines)
     with tempfile.TemporaryDirectory() as d:
         open(os.path.join(d, 'p.c'), 'w').write(src)
-        subprocess.check_call(['gcc', '-I', os.path.join(ROOT, 'include'), os.path.join(d, 'p.c'), '-o', os.path.join(d, 'p')])
-        size, off_table, off_stats = map(int, subprocess.check_output([os.path.join(d, 'p')]).split())
-    assert ctypes.sizeof(_C.GemmDesc) == size
-    assert _C.GemmDesc.table.offset == off_table and _C.GemmDesc.stats.offset == off_stats
+        subprocess.check_call(['gcc', '-std=c99', '-I', os.path.join(ROOT, 'include'), os.path.join(d, 'p.c'), '-o', os.path.join(d, 'p')])
+        got = [tuple(map(int, l.split())) for l in subprocess.check_output([os.path.join(d, 'p')]).decode().splitlines()]
+    want = []
+    for cname, mirror in _C.STRUCTS.items():
+        want.append((ctypes.sizeof(mirror),))
+        want += [(getattr(mirror, f[0]).offset, getattr(mirror, f[0]).size) for f in mirror._fields_]
+    assert got == want
 
 
 def test_module_api_matches_reference_manifest(manifest):
