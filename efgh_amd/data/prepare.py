@@ -209,10 +209,123 @@ def _chw_and_mask(img, want_chw=True, want_mask=False):
     return chw, mask
 
 
-def preproc_img(img, gts, raw_cam_img_size, rellis=False, device='cuda'):
-    """loader_utils.py:104-130 (KITTI) / :132-158 (`rellis=True`: the raw view is a resize, not a crop)"""
+# ------------------------------------------------------------------------------------------------
+# photometric jitter (not in the reference): torchvision's ColorJitter on PIL images, byte for byte (csrc/jitter.hip)
+# ------------------------------------------------------------------------------------------------
+JITTER_OPS = ('brightness', 'contrast', 'saturation', 'hue')          # EFGH_JITTER_* of include/efgh_hip.h, in this order
+
+
+class JitterParams(object):
+    """One drawn jitter, for `color_jitter` / `preproc_img(jitter=...)`, for tests and for replay.
+    order      the op names (of JITTER_OPS, each at most once) in the order they are applied
+    factors    one float per op: the blend factor of brightness / contrast / saturation (>= 0), the hue value in [-0.5, 0.5]
+    hue_shift  what is added to H (mod 256): int(hue * 255), truncated toward zero; 0 without hue"""
+    __slots__ = ('order', 'factors', 'hue_shift')
+
+    def __init__(self, order=(), factors=()):
+        order, factors = tuple(order), tuple(factors)
+        if len(order) != len(factors):
+            raise _C.EfghError('JitterParams: %d ops with %d factors' % (len(order), len(factors)))
+        for op in order:
+            if op not in JITTER_OPS or order.count(op) != 1:
+                raise _C.EfghError('JitterParams: op %r is not one of %s, or appears twice' % (op, ', '.join(JITTER_OPS)))
+        self.order, self.factors, self.hue_shift = order, tuple(_jitter_value(op, f) for op, f in zip(order, factors)), 0
+        if 'hue' in order:
+            self.hue_shift = int(self.factors[order.index('hue')] * 255)
+
+    def __repr__(self):
+        return 'JitterParams(order=%r, factors=%r)' % (self.order, self.factors)
+
+
+def _jitter_value(op, f):
+    try:
+        v = float(f)
+    except (TypeError, ValueError):
+        raise _C.EfghError('%s: expected a number, got %r' % (op, f))
+    ok = -0.5 <= v <= 0.5 if op == 'hue' else (v >= 0. and math.isfinite(v))
+    if not ok:
+        raise _C.EfghError('%s: %r is outside %s' % (op, f, '[-0.5, 0.5]' if op == 'hue' else '[0, inf)'))
+    return v
+
+
+class ColorJitter(object):
+    """torchvision's `ColorJitter(brightness, contrast, saturation, hue)`: a float x is the range [max(0, 1 - x), 1 + x] (hue:
+    [-x, x], 0 <= x <= 0.5), a pair is the range itself; a component that is 0 or None is left out.
+    `.sample()` draws with Python's `random`, and the sequence of draws is part of the contract: with n ops present, first the order,
+    a Fisher-Yates shuffle of the present ops taken in JITTER_OPS order (for i = n-1 down to 1: j = int(random.random() * (i + 1)),
+    swap entries i and j), then one factor lo + (hi - lo) * random.random() per present op, in JITTER_OPS order.  No op: no draw."""
+
+    def __init__(self, brightness=0, contrast=0, saturation=0, hue=0):
+        self.ranges = {}
+        for op, v in zip(JITTER_OPS, (brightness, contrast, saturation, hue)):
+            r = self._range(op, v)
+            if r is not None:
+                self.ranges[op] = r
+
+    @staticmethod
+    def _range(op, v):
+        is_hue = op == 'hue'
+        if v is None:
+            return None
+        if isinstance(v, (tuple, list)):
+            if len(v) != 2:
+                raise _C.EfghError('%s: a range is a pair (lo, hi), got %r' % (op, v))
+            lo, hi = _jitter_value(op, v[0]), _jitter_value(op, v[1])
+            if lo > hi:
+                raise _C.EfghError('%s: the range %r is empty' % (op, v))
+            return lo, hi
+        x = _jitter_value(op, v)
+        if x < 0.:
+            raise _C.EfghError('%s: %r is negative (a single number x means the range [-x, x])' % (op, v))
+        if x == 0.:
+            return None
+        return (-x, x) if is_hue else (max(0., 1. - x), 1. + x)
+
+    def sample(self):
+        order = [op for op in JITTER_OPS if op in self.ranges]
+        present = list(order)
+        for i in range(len(order) - 1, 0, -1):
+            j = int(random.random() * (i + 1))
+            order[i], order[j] = order[j], order[i]
+        drawn = {}
+        for op in present:
+            lo, hi = self.ranges[op]
+            drawn[op] = lo + (hi - lo) * random.random()
+        return JitterParams(order, [drawn[op] for op in order])
+
+
+def color_jitter(img, params, device='cuda'):
+    """`params` (a JitterParams) applied to a uint8 RGB image, (H,W,3) or (3,H,W), array or tensor -> uint8 (H,W,3) on the device.
+    Two launches at most (the sum of L for contrast's mean, then every op per pixel); the result is a new tensor, the input is
+    never written.  With no ops nothing is launched and the image itself (on the device, (H,W,3)) is returned."""
+    if not isinstance(params, JitterParams):
+        raise _C.EfghError('color_jitter: params is a JitterParams (ColorJitter(...).sample()), got %r' % (params,))
+    img = _as_dev_u8(img, device)
+    n_ops = len(params.order)
+    if n_ops == 0:
+        return img
+    if img.dim() != 3 or img.shape[2] != 3 or img.numel() == 0:
+        raise _C.EfghError('color_jitter: image of shape %s, expected (H, W, 3) or (3, H, W), not empty' % (tuple(img.shape),))
+    n = int(img.shape[0]) * int(img.shape[1])
+    ops = (ctypes.c_int32 * n_ops)(*[JITTER_OPS.index(op) for op in params.order])
+    fac = (ctypes.c_float * n_ops)(*params.factors)
+    out = torch.empty_like(img)
+    partials = None
+    if 'contrast' in params.order:
+        partials = torch.empty(_L().efgh_prep_jitter_partials(n), dtype=torch.int64, device=img.device)
+        _C.check(_L().efgh_prep_jitter_sum(ptr(img), n, ops, fac, n_ops, params.hue_shift, ptr(partials), _st()))
+    _C.check(_L().efgh_prep_jitter_apply(ptr(img), n, ops, fac, n_ops, params.hue_shift, ptr(partials), ptr(out), _st()))
+    return out
+
+
+def preproc_img(img, gts, raw_cam_img_size, rellis=False, device='cuda', jitter=None):
+    """loader_utils.py:104-130 (KITTI) / :132-158 (`rellis=True`: the raw view is a resize, not a crop).
+    `jitter` (not in the reference; None: off, and nothing runs differently): a JitterParams applied once to the decoded image, in
+    front of the raw view, the rotation and the resize, so 'in', 'raw' and 'rot' agree and the borders stay black."""
     raw_hw = (int(raw_cam_img_size[0]), int(raw_cam_img_size[1]))
     img = _as_dev_u8(img, device)
+    if jitter is not None:
+        img = color_jitter(img, jitter, device)
     img_raw = resize_image(img, raw_hw) if rellis else crop_image(img, raw_hw, init=True)
     rc = gts['rand_init_c']
     rot_deg = math.degrees(np.arctan2(rc[1, 0], rc[0, 0]))                       # numpy_utils.py:436
@@ -594,10 +707,16 @@ class _Process(object):
         self.voxel_size = args.get('voxel_size')         # optional (not in the reference): thin on a voxel grid, see preproc_pcd
         if self.voxel_size is not None:
             _check_voxel_size(self.voxel_size)
+        self.color_jitter = None                         # optional (not in the reference): training only, see ColorJitter
         if args['test'] is False:
             self.l_rot_range = args['dclb']['l_rot_range']
             self.l_trs_range = args['dclb']['l_trs_range']
             self.c_rot_range = args['dclb']['c_rot_range']
+            if args.get('color_jitter') is not None:
+                try:
+                    self.color_jitter = ColorJitter(**args['color_jitter'])
+                except TypeError:
+                    raise _C.EfghError("args['color_jitter']: expected a dict with keys of %s, got %r" % (JITTER_OPS, args['color_jitter']))
         else:
             self.l_rot_range, self.l_trs_range, self.c_rot_range = None, None, None
 
@@ -608,7 +727,8 @@ class _Process(object):
         """the body all four callables share; `pcd` is an array or a SweepSet, `calib` the camera matrix as it is returned"""
         rr, rp, ry, tx, ty, tz, rt = rand_init_params(rand_init, self.l_rot_range, self.l_trs_range, self.c_rot_range)
         gts = preproc_gt(rr, rp, ry, tx, ty, tz, rt, posej_T_posei)
-        imgs = preproc_img(img, gts, self.raw_cam_img_size, self.rellis, self.device)
+        jitter = self.color_jitter.sample() if self.color_jitter is not None else None       # (after rand_init_params's seven draws)
+        imgs = preproc_img(img, gts, self.raw_cam_img_size, self.rellis, self.device, jitter)
         pc = preproc_pcd(pcd, gts, self.num_points, self.lidar_line, sampled_indices=sampled_indices,
                          flip_xy=self.rellis, device=self.device, voxel_size=self.voxel_size)
         gts['img_raw'], gts['img_rot'], gts['img_mask'] = imgs['raw'], imgs['rot'], imgs['img_mask']

@@ -9,6 +9,7 @@ loop of the reference's iterater.py:25-60 with nothing on the CPU between the de
     python examples/train_synthetic.py --iters 3 --groups                        # parameter groups: G at a tenth of the rate, no decay on 1-D parameters
     python examples/train_synthetic.py --iters 3 --accumulate-sweeps 2           # 2 neighbouring sweeps on either side, merged on the GPU
     python examples/train_synthetic.py --iters 3 --accumulate-sweeps 2 --voxel 0.2   # ... thinned on a 0.2 grid before the sub-sampling
+    python examples/train_synthetic.py --iters 3 --jitter 0.4 0.4 0.4 0.1        # brightness, contrast, saturation, hue of every frame, on the GPU
 """
 import argparse
 import os
@@ -70,6 +71,9 @@ def main(argv=None):
     ap.add_argument('--voxel', type=float, default=None, metavar='SIZE',
                     help='thin every cloud on a voxel grid of edge SIZE before it is sub-sampled (first point of a voxel wins, the '
                          'own sweep first); goes together with --accumulate-sweeps')
+    ap.add_argument('--jitter', type=float, nargs=4, default=None, metavar=('B', 'C', 'S', 'H'),
+                    help='photometric jitter of every frame (torchvision\'s ColorJitter(B, C, S, H), Pillow-exact, on the GPU); 0 leaves '
+                         'a component out')
     a = ap.parse_args(argv)
     a.skip_nonfinite = a.skip_nonfinite or a.transactional
     raw = tuple(a.raw)
@@ -78,6 +82,8 @@ def main(argv=None):
                  'dclb': {'l_rot_range': 1 / 12., 'l_trs_range': 1.0, 'c_rot_range': 1 / 12.}})
     if a.voxel is not None:
         args['voxel_size'] = a.voxel
+    if a.jitter is not None:
+        args['color_jitter'] = dict(zip(('brightness', 'contrast', 'saturation', 'hue'), a.jitter))
     torch.manual_seed(0)
     model = EFGHBackbone(args).cuda()
     groups = None

@@ -65,7 +65,8 @@ const char *efgh_last_error(void);
  *      efgh_adam_step_groups and the struct efgh_adam_groups (the fused optimizer step with torch.optim's parameter groups);
  *      efgh_prep_sweeps_filter, efgh_prep_sweeps_gather_transform, efgh_prep_sweeps_materialize (multi-sweep accumulation and
  *      stride-3 rows in sample preparation);
- *      efgh_prep_voxel_workspace, efgh_prep_voxel_keep, efgh_prep_sweeps_voxel_keep (thinning on a voxel grid in sample preparation). */
+ *      efgh_prep_voxel_workspace, efgh_prep_voxel_keep, efgh_prep_sweeps_voxel_keep (thinning on a voxel grid in sample preparation);
+ *      efgh_prep_jitter_partials, efgh_prep_jitter_sum, efgh_prep_jitter_apply (photometric jitter of the image in sample preparation). */
 #define EFGH_ABI_VERSION 4
 int efgh_version(void);
 
@@ -1027,6 +1028,29 @@ int efgh_prep_sweeps_voxel_keep(const float *pts, int32_t stride, const int32_t 
                                 const int32_t *identity, int32_t K, int32_t n_total, const int32_t *keep_in, int32_t n_cap,
                                 const int32_t *n_dev, double voxel, void *workspace, int32_t *keep_out, int32_t *count,
                                 void *stream);
+/* Photometric jitter of an RGB image of n_pixels (uint8, 3 bytes a pixel, contiguous): torchvision's ColorJitter on PIL images, i.e.
+ * Pillow's arithmetic byte for byte (csrc/jitter.hip; tests/jitter_contract.py spells it out).  ops_host / factors_host are HOST arrays
+ * of n_ops entries (1 .. EFGH_JITTER_MAX_OPS, each op at most once), applied in that order:
+ *   brightness  Image.blend(0, img, f)            saturation  Image.blend((L,L,L), img, f), L = (19595 R + 38470 G + 7471 B + 2^15) >> 16
+ *   contrast    Image.blend((m,m,m), img, f), m = (int)(sum L / n_pixels + 0.5) in float64, L of the image as the ops in front left it
+ *   hue         RGB -> HSV, H' = (H + hue_shift) & 255 (-255 <= hue_shift <= 255; its factor is not read), HSV -> RGB
+ * blend is t = deg + f * (img - deg) in float32 with the multiply and the add apart: f == 0 copies deg, f == 1 copies img,
+ * 0 < f < 1 truncates t, any other f clips t to 0 .. 255 first.
+ * Two launches: efgh_prep_jitter_sum, only with contrast among the ops, applies the ops in front of contrast and leaves one uint64
+ * sum of L per workgroup in partials (efgh_prep_jitter_partials(n_pixels) <= 1024 entries, 8-byte aligned, plain stores);
+ * efgh_prep_jitter_apply folds them in every workgroup and writes out (partials: NULL exactly when there is no contrast).  out must
+ * not overlap in.  Images whose address is a multiple of 4 are read and written four pixels (three dwords) a thread.  No host read,
+ * no atomic.  EFGH_E_INVALID with a message, and nothing launched, for anything outside the above.                          */
+#define EFGH_JITTER_MAX_OPS 4
+#define EFGH_JITTER_BRIGHTNESS 0
+#define EFGH_JITTER_CONTRAST 1
+#define EFGH_JITTER_SATURATION 2
+#define EFGH_JITTER_HUE 3
+int32_t efgh_prep_jitter_partials(int64_t n_pixels);
+int efgh_prep_jitter_sum(const uint8_t *in, int64_t n_pixels, const int32_t *ops_host, const float *factors_host, int32_t n_ops,
+                         int32_t hue_shift, void *partials, void *stream);
+int efgh_prep_jitter_apply(const uint8_t *in, int64_t n_pixels, const int32_t *ops_host, const float *factors_host, int32_t n_ops,
+                           int32_t hue_shift, const void *partials, uint8_t *out, void *stream);
 
 /* ------------------------------------------------------------------ evaluation metrics --
  * Err.calc_error_odom_np (mode 0: arccos((tr(pred_R^T gt_R)-1)/2) in degrees, |pred_t - gt_t|_2; common/helper.py:198-207)
