@@ -244,11 +244,10 @@ k_pool_bn_bwd_reduce(const float *__restrict__ dyp, const float *__restrict__ ra
 // rounding of beta itself is common to all terms of a channel.  Measured (4x32x32x64, one-signed pooled gradient): the mean of
 // dpre*xhat is 1.5 x 2^-24 of mean |dpre||xhat| off at |beta|/|gamma| = 1, 1.9 at 2, 2.9 at 3, 3.9 at 4, 50 at 64, 301 at 1000 - the
 // very error of the two means that the comment in k_act_bn_bwd_reduce warns about; from raw it is below 1.6 throughout.  The bound 2
-// keeps both means within the 3 x 2^-24 that tests/bn_contract.py allows them.
-#ifndef EFGH_POOLED_BETA_GAMMA
-#define EFGH_POOLED_BETA_GAMMA 2.0f
-#endif
-template <bool NT>
+// keeps both means within the 3 x 2^-24 that tests/bn_contract.py allows them.  (The predicate is common.h's pooled_xhat_from_raw.)
+// WIN = true: `raw` is raw_win [B][H/2][W/2][C], the winner's raw value itself, left by the train-mode pooled 4-channel convolution
+// (c4conv.hip) for exactly the channels that take this route: one read at the pooled index, no window to search.
+template <bool NT, bool WIN>
 __global__ void __launch_bounds__(TPB)
 k_pool_bn_bwd_reduce_y(const float *__restrict__ dyp, const float *__restrict__ y, const float *__restrict__ raw,
                        const float *__restrict__ mean, const float *__restrict__ invstd, const float *__restrict__ pscale,
@@ -272,7 +271,7 @@ k_pool_bn_bwd_reduce_y(const float *__restrict__ dyp, const float *__restrict__ 
         for (int q = 0; q < 4; ++q) {
             bet[q] = fmaf(muv[q], scv[q], shv[q]);
             // (gamma = pscale / invstd: |beta| > K |gamma|  <=>  |beta| |invstd| > K |pscale|; gamma == 0 included)
-            fr[q] = scv[q] == 0.f || fabsf(bet[q]) * fabsf(isv[q]) > EFGH_POOLED_BETA_GAMMA * fabsf(scv[q]);
+            fr[q] = pooled_xhat_from_raw(muv[q], isv[q], scv[q], shv[q]);
             rg[q] = fr[q] ? 0.f : isv[q] / scv[q];
             flat |= fr[q];
         }
@@ -280,7 +279,10 @@ k_pool_bn_bwd_reduce_y(const float *__restrict__ dyp, const float *__restrict__ 
             const float4 g4 = ld_stream<NT>(dyp + r * C + c), y4 = ld_stream<NT>(y + r * C + c);
             const float gv[4] = {g4.x, g4.y, g4.z, g4.w}, yv[4] = {y4.x, y4.y, y4.z, y4.w};
             float rw0[4] = {0.f, 0.f, 0.f, 0.f};
-            if (flat) {          // (a channel of this quad takes xhat from raw: the window's first maximum, as the forward pass found it)
+            if (flat && WIN) {
+                const float4 w = *reinterpret_cast<const float4 *>(raw + r * C + c);
+                rw0[0] = w.x; rw0[1] = w.y; rw0[2] = w.z; rw0[3] = w.w;
+            } else if (flat) {   // (a channel of this quad takes xhat from raw: the window's first maximum, as the forward pass found it)
                 const int j = (int)(r % Wo); const long long t = r / Wo;
                 const int i = (int)(t % Ho); const long long b = t / Ho;
                 const float *pw = raw + (((b * H + 2 * i) * W) + 2 * j) * (long long)C + c;
@@ -778,12 +780,11 @@ extern "C" int efgh_pool_bn_bwd_reduce(const float *dy_pool, const float *raw, c
 }
 
 /* the same sums from the POOLED gradient and the POOLED activation y [B][H/2][W/2][C] (ReLU layers; see k_pool_bn_bwd_reduce_y);
- * `part` has efgh_bwd_groups(B * (H/2) * (W/2)) rows */
-extern "C" int efgh_pool_bn_bwd_reduce_pooled(const float *dy_pool, const float *y_pool, const float *raw, const float *mean,
-                                              const float *invstd, const float *pscale, const float *pshift, int32_t B, int32_t H,
-                                              int32_t W, int32_t C, double *part, float *sum_dpre, float *sum_dpre_xhat,
-                                              double *mean_dpre, double *mean_dpre_xhat, void *stream_) {
-    hipStream_t st = (hipStream_t)stream_;
+ * `part` has efgh_bwd_groups(B * (H/2) * (W/2)) rows.  win: `raw` is the pooled-size raw_win */
+static int pool_reduce_pooled(bool win, const float *dy_pool, const float *y_pool, const float *raw, const float *mean,
+                              const float *invstd, const float *pscale, const float *pshift, int32_t B, int32_t H, int32_t W,
+                              int32_t C, double *part, float *sum_dpre, float *sum_dpre_xhat, double *mean_dpre,
+                              double *mean_dpre_xhat, hipStream_t st) {
     EFGH_CHECK_ARG(dy_pool && y_pool && raw && mean && invstd && pscale && pshift && part && sum_dpre && sum_dpre_xhat && mean_dpre &&
                    mean_dpre_xhat);
     EFGH_CHECK_ARG(B > 0 && H >= 2 && W >= 2 && C > 0 && C % 4 == 0);
@@ -791,14 +792,33 @@ extern "C" int efgh_pool_bn_bwd_reduce_pooled(const float *dy_pool, const float 
     const int G = efgh_bwd_groups(Mp);
     int CL = 1;
     while (CL < 64 && CL * 4 < C) CL <<= 1;
-    if (efgh_stream_nt(Mp * C * 4)) k_pool_bn_bwd_reduce_y<true><<<dim3(cdiv(C / 4, CL), G), TPB, 0, st>>>(dy_pool, y_pool, raw, mean, invstd, pscale, pshift, H, W, C, Mp,
-                                                                  (int)bwd_rows_per_block(Mp), CL, part);
-    else k_pool_bn_bwd_reduce_y<false><<<dim3(cdiv(C / 4, CL), G), TPB, 0, st>>>(dy_pool, y_pool, raw, mean, invstd, pscale, pshift, H, W, C, Mp,
-                                                                  (int)bwd_rows_per_block(Mp), CL, part);
+    const dim3 grid(cdiv(C / 4, CL), G);
+    const int rows = (int)bwd_rows_per_block(Mp);
+    const bool nt = efgh_stream_nt(Mp * C * 4);
+#define EFGH_GO(NT_, WIN_) k_pool_bn_bwd_reduce_y<NT_, WIN_><<<grid, TPB, 0, st>>>(dy_pool, y_pool, raw, mean, invstd, pscale, pshift, H, W, C, Mp, rows, CL, part)
+    if (win) { if (nt) EFGH_GO(true, true); else EFGH_GO(false, true); }
+    else { if (nt) EFGH_GO(true, false); else EFGH_GO(false, false); }
+#undef EFGH_GO
     k_bwd_finalize<<<cdiv(C, 32), dim3(32, 32), 0, st>>>(part, G, C, (double)B * H * W, sum_dpre, sum_dpre_xhat, mean_dpre,
                                                          mean_dpre_xhat);
     EFGH_CHECK_LAUNCH();
     return EFGH_OK;
+}
+
+extern "C" int efgh_pool_bn_bwd_reduce_pooled(const float *dy_pool, const float *y_pool, const float *raw, const float *mean,
+                                              const float *invstd, const float *pscale, const float *pshift, int32_t B, int32_t H,
+                                              int32_t W, int32_t C, double *part, float *sum_dpre, float *sum_dpre_xhat,
+                                              double *mean_dpre, double *mean_dpre_xhat, void *stream_) {
+    return pool_reduce_pooled(false, dy_pool, y_pool, raw, mean, invstd, pscale, pshift, B, H, W, C, part, sum_dpre, sum_dpre_xhat,
+                              mean_dpre, mean_dpre_xhat, (hipStream_t)stream_);
+}
+
+extern "C" int efgh_pool_bn_bwd_reduce_pooled_win(const float *dy_pool, const float *y_pool, const float *raw_win, const float *mean,
+                                                  const float *invstd, const float *pscale, const float *pshift, int32_t B,
+                                                  int32_t H, int32_t W, int32_t C, double *part, float *sum_dpre,
+                                                  float *sum_dpre_xhat, double *mean_dpre, double *mean_dpre_xhat, void *stream_) {
+    return pool_reduce_pooled(true, dy_pool, y_pool, raw_win, mean, invstd, pscale, pshift, B, H, W, C, part, sum_dpre,
+                              sum_dpre_xhat, mean_dpre, mean_dpre_xhat, (hipStream_t)stream_);
 }
 
 extern "C" int efgh_pool_bn_bwd_apply(const float *dy_pool, const float *raw, const float *mean, const float *invstd,

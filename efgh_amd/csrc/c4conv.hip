@@ -33,6 +33,9 @@ struct C4Args {
     float *stats;
     long long units; int jblocks;
     const float *G; long long ldg; float *dW;       // wgrad
+    // train-mode pooled layer (k_c4_conv_pool<.., true>, k_c4_pool_bwd_draw): BatchNorm's per-channel vectors, the pooled gradient
+    const float *mean, *invstd, *coef; const double *m1, *m2;
+    const float *dyp; float *raw_win, *draw;
 };
 
 __device__ __forceinline__ void unit_coords(const C4Args &p, long long unit, long long &row, int &i, long long &b, int &j0) {
@@ -58,12 +61,16 @@ __device__ __forceinline__ void wave_lds_sync() {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-template <int NT, bool RES>
+// STORE = false: the statistics-only pass of a train-mode pooled layer (efgh_c4_conv3x3_stats).  Same units, same MFMA order, same
+// order of the column sums - the statistics rows have the bits of the storing launch; the transpose tile and the output stores are
+// compiled out.
+template <int NT, bool RES, bool STORE = true>
 __global__ void __launch_bounds__(64 * WAVES, 2) k_c4_conv(const C4Args p) {
+    static_assert(STORE || !RES, "the statistics-only pass has no residual");
     __shared__ float2 Pw[WAVES][3][2][LWMAX + 1];
     __shared__ float red[2][WAVES][NT * 32];
     constexpr int TPITCH = 40;                       // floats per row of the transpose tile (h = 0 / 1 rows land on disjoint banks)
-    __shared__ __attribute__((aligned(16))) float Tw[WAVES][32 * TPITCH];
+    __shared__ __attribute__((aligned(16))) float Tw[WAVES][STORE ? 32 * TPITCH : 4];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 31, h = lane >> 5;
     const int LW = (TP - 1) * p.s + 3;
     float2 (*P)[2][LWMAX + 1] = Pw[wave];
@@ -166,16 +173,18 @@ __global__ void __launch_bounds__(64 * WAVES, 2) k_c4_conv(const C4Args p) {
                                    : make_float4(0.f, 0.f, 0.f, 0.f);
                 }
             }
-            wave_lds_sync();                         // the tile's previous readers are done
+            if (STORE) wave_lds_sync();              // the tile's previous readers are done
 #pragma unroll
             for (int q = 0; q < 16; ++q) {
                 const int pl = (q & 3) + 8 * (q >> 2) + 4 * h;
                 const bool ok = full || oj0 + pl < p.Wo;
                 float v = acc[j][q] + bi[j];
                 if (ok) { s1[j] += v; s2[j] = fmaf(v, v, s2[j]); }
+                if (!STORE) continue;
                 v = fmaf(v, sc[j], sf[j]);
                 T[pl * TPITCH + r] = RES ? v : act_neg(v, neg);
             }
+            if (!STORE) continue;
             wave_lds_sync();
 #pragma unroll
             for (int pass = 0; pass < 4; ++pass) {
@@ -226,7 +235,23 @@ __device__ __forceinline__ float4 load_px4(const C4Args &p, int idx, int ip, lon
     return make_float4(0.f, 0.f, 0.f, 0.f);
 }
 
-template <int NT>
+// ReLU as the training path's pooling pass writes it (k_maxpool2_affine's act_f), and the first maximum in scan order of a window's
+// four activated values under a strict `>` (pool_cell_dpre, k_pool_bn_bwd_reduce_y)
+__device__ __forceinline__ float relu_sel(float t) { return t > 0.f ? t : 0.f; }
+__device__ __forceinline__ int first_max4(const float e[4]) {
+    int best = 0;
+#pragma unroll
+    for (int k = 1; k < 4; ++k) if (e[k] > e[best]) best = k;
+    return best;
+}
+
+// TRAIN = true: the forward of a train-mode BatchNorm + ReLU layer (efgh_c4_conv3x3_pooled_train), after the statistics-only pass
+// has given scale / shift.  The pooled value is that of k_c4_conv followed by k_maxpool2_affine, bit for bit: the affine map is ONE
+// fused multiply-add there (the library is built with the compiler's default contraction, and k_maxpool2_affine's `v*scale + shift`
+// compiles to v_fma_f32), so it is written as fmaf here, and the ReLU is act_f's select.  For the channels whose BatchNorm backward
+// takes xhat from raw (pooled_xhat_from_raw) the raw value of the window's first maximum goes to raw_win [B][Ho/2][Wo/2][N]; the
+// other channels store nothing there.
+template <int NT, bool TRAIN = false>
 __global__ void __launch_bounds__(64 * WAVES, 2) k_c4_conv_pool(const C4Args p) {
     __shared__ float2 Pw[WAVES][4][2][LW1 + 1];
     constexpr int TPITCH = 40;
@@ -238,6 +263,7 @@ __global__ void __launch_bounds__(64 * WAVES, 2) k_c4_conv_pool(const C4Args p) 
 
     float2 bw[9][NT];
     float bi[NT], sc[NT], sf[NT];
+    bool win[NT];                                    // TRAIN: this lane's channel of tile j leaves raw_win
 #pragma unroll
     for (int j = 0; j < NT; ++j) {
         const int n = 32 * j + r;
@@ -246,6 +272,7 @@ __global__ void __launch_bounds__(64 * WAVES, 2) k_c4_conv_pool(const C4Args p) 
         bi[j] = p.bias ? p.bias[n] : 0.f;
         sc[j] = p.scale ? p.scale[n] : 1.f;
         sf[j] = p.shift ? p.shift[n] : 0.f;
+        win[j] = TRAIN && pooled_xhat_from_raw(p.mean[n], p.invstd[n], sc[j], sf[j]);
     }
     const float neg = p.act == 1 ? 0.f : (p.act == 2 ? p.slope : 1.f);
 #pragma unroll
@@ -316,9 +343,25 @@ __global__ void __launch_bounds__(64 * WAVES, 2) k_c4_conv_pool(const C4Args p) 
 #pragma unroll
             for (int q = 0; q < 16; ++q) {
                 const int pl = (q & 3) + 8 * (q >> 2) + 4 * h;
-                const float v0 = act_neg(fmaf(acc[0][j][q] + bi[j], sc[j], sf[j]), neg);
-                const float v1 = act_neg(fmaf(acc[1][j][q] + bi[j], sc[j], sf[j]), neg);
+                const float t0 = fmaf(acc[0][j][q] + bi[j], sc[j], sf[j]), t1 = fmaf(acc[1][j][q] + bi[j], sc[j], sf[j]);
+                const float v0 = TRAIN ? relu_sel(t0) : act_neg(t0, neg);
+                const float v1 = TRAIN ? relu_sel(t1) : act_neg(t1, neg);
                 T[pl * TPITCH + r] = fmaxf(v0, v1);
+            }
+            if (TRAIN && win[j]) {
+                // a window's four values sit in ONE lane: accumulator elements q, q + 1 (q even) are the pixels pl, pl + 1 of both rows
+#pragma unroll
+                for (int q = 0; q < 16; q += 2) {
+                    const int pp = ((q & 3) >> 1) + 4 * (q >> 2) + 2 * h;
+                    const float rw[4] = {acc[0][j][q] + bi[j], acc[0][j][q + 1] + bi[j], acc[1][j][q] + bi[j], acc[1][j][q + 1] + bi[j]};
+                    float e[4];
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) e[k] = relu_sel(fmaf(rw[k], sc[j], sf[j]));
+                    const int best = first_max4(e);
+                    if ((oj0 >> 1) + pp < Wp)
+                        p.raw_win[(orow0 * Wp + (oj0 >> 1) + pp) * (long long)p.N + 32 * j + r] =
+                            best == 0 ? rw[0] : (best == 1 ? rw[1] : (best == 2 ? rw[2] : rw[3]));
+                }
             }
             wave_lds_sync();
 #pragma unroll
@@ -330,6 +373,153 @@ __global__ void __launch_bounds__(64 * WAVES, 2) k_c4_conv_pool(const C4Args p) 
                 v.x = fmaxf(a.x, c.x); v.y = fmaxf(a.y, c.y); v.z = fmaxf(a.z, c.z); v.w = fmaxf(a.w, c.w);
                 if ((oj0 >> 1) + pp < Wp)
                     *reinterpret_cast<float4 *>(p.out + (orow0 * Wp + (oj0 >> 1) + pp) * p.ldo + 32 * j + c4) = v;
+            }
+        }
+    }
+#undef EFGH_FETCH
+#undef EFGH_PUT
+#undef EFGH_STAGE
+}
+
+// ---- BatchNorm backward "apply" of the train-mode pooled layer, raw RECOMPUTED (efgh_c4_pool_bwd_draw) ---------------------------
+// What k_pool_bn_bwd_apply (backward.hip) makes of the stored raw map, from the layer's input instead: the row-pair unit of
+// k_c4_conv_pool (a last pair of an odd map has one row), raw = acc + bias in the same MFMA order, and then per 2x2 cell - whose four
+// values sit in one lane, see k_c4_conv_pool - pool_cell_dpre's rule for a ReLU: the pooled gradient times act' goes to the first
+// maximum of relu(raw*pscale + pshift), every other element and every cell of an odd last row / column has dpre = 0; draw =
+// bn_draw_f64.  The full-resolution draw leaves through the transpose tile as 16-byte stores, one image row at a time.  No atomics.
+template <int NT, bool NTS>
+__global__ void __launch_bounds__(64 * WAVES, 2) k_c4_pool_bwd_draw(const C4Args p) {
+    __shared__ float2 Pw[WAVES][4][2][LW1 + 1];
+    constexpr int TPITCH = 40;
+    __shared__ __attribute__((aligned(16))) float Tw[WAVES][32 * TPITCH];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 31, h = lane >> 5;
+    float2 (*P)[2][LW1 + 1] = Pw[wave];
+    float *T = Tw[wave];
+    const int Hp = p.Ho >> 1, Wp = p.Wo >> 1, Hc = (p.Ho + 1) >> 1;
+
+    float2 bw[9][NT];
+    float bi[NT], sc[NT], sf[NT];
+    double mu[NT], is[NT], cf[NT], m1[NT], m2[NT], zm1[NT];      // (zm1: dpre - m1 of an element that is no winner)
+#pragma unroll
+    for (int j = 0; j < NT; ++j) {
+        const int n = 32 * j + r;
+#pragma unroll
+        for (int t = 0; t < 9; ++t) bw[t][j] = *reinterpret_cast<const float2 *>(p.W + ((long long)n * 9 + t) * 4 + 2 * h);
+        bi[j] = p.bias ? p.bias[n] : 0.f;
+        sc[j] = p.scale[n]; sf[j] = p.shift[n];
+        mu[j] = (double)p.mean[n]; is[j] = (double)p.invstd[n]; cf[j] = (double)p.coef[n];
+        m1[j] = p.m1[n]; m2[j] = p.m2[n];
+        zm1[j] = bn_draw_dpre_m1(0.f, m1[j]);
+    }
+#pragma unroll
+    for (int j = 0; j < NT; ++j)
+#pragma unroll
+        for (int t = 0; t < 9; ++t) asm volatile("" ::"v"(bw[t][j].x), "v"(bw[t][j].y));
+
+    const long long nwaves = (long long)gridDim.x * WAVES;
+    long long unit = (long long)blockIdx.x * WAVES + wave;
+    long long rowc = 0, b = 0; int ip = 0, j0 = 0;   // coordinates of the unit whose pixels are in pf0..2 (rowc = b * Hc + ip)
+    long long crow = 0; int cj0 = 0;                 // ... of the unit staged in LDS
+    float4 pf0, pf1, pf2;
+#define EFGH_FETCH(u)                                                                    \
+    {                                                                                   \
+        const int jb = (int)((u) % p.jblocks);                                          \
+        rowc = (u) / p.jblocks; ip = (int)(rowc % Hc); b = rowc / Hc; j0 = jb * TP;     \
+        pf0 = load_px4(p, lane, ip, b, j0); pf1 = load_px4(p, lane + 64, ip, b, j0);    \
+        pf2 = load_px4(p, lane + 128, ip, b, j0);                                       \
+    }
+#define EFGH_PUT(q, v)                                                                   \
+    {                                                                                   \
+        const int idx = lane + 64 * q;                                                  \
+        if (idx < 4 * LW1) {                                                            \
+            const int kh = idx / LW1, x = idx - kh * LW1;                               \
+            P[kh][0][x] = make_float2(v.x, v.y); P[kh][1][x] = make_float2(v.z, v.w);   \
+        }                                                                               \
+    }
+#define EFGH_STAGE()                                                                     \
+    {                                                                                   \
+        crow = rowc; cj0 = j0;                                                          \
+        EFGH_PUT(0, pf0) EFGH_PUT(1, pf1) EFGH_PUT(2, pf2)                              \
+    }
+    if (unit < p.units) {
+        EFGH_FETCH(unit)
+        EFGH_STAGE()
+        if (unit + nwaves < p.units) EFGH_FETCH(unit + nwaves)
+    }
+    for (; unit < p.units; unit += nwaves) {
+        const int oj0 = cj0, oip = (int)(crow % Hc);
+        const long long ob = crow / Hc;
+        const bool row1 = 2 * oip + 1 < p.Ho;        // (wave-uniform) the pair's second row exists
+        // the pooled gradient of this lane's eight cells, per channel tile: in flight during the MFMAs
+        float g[NT][8];
+#pragma unroll
+        for (int q = 0; q < 16; q += 2) {
+            const int pc = (oj0 >> 1) + ((q & 3) >> 1) + 4 * (q >> 2) + 2 * h;
+            const bool pooled = oip < Hp && pc < Wp;
+#pragma unroll
+            for (int j = 0; j < NT; ++j)
+                g[j][q >> 1] = pooled ? p.dyp[((ob * Hp + oip) * Wp + pc) * (long long)p.N + 32 * j + r] : 0.f;
+        }
+        wave_lds_sync();
+        f32x16 acc[2][NT];
+#pragma unroll
+        for (int half = 0; half < 2; ++half) {
+#pragma unroll
+            for (int j = 0; j < NT; ++j)
+#pragma unroll
+                for (int q = 0; q < 16; ++q) acc[half][j][q] = 0.f;
+            float2 af[9];
+#pragma unroll
+            for (int t = 0; t < 9; ++t) af[t] = P[t / 3 + half][h][r + t % 3];
+#pragma unroll
+            for (int t = 0; t < 9; ++t) {
+#pragma unroll
+                for (int j = 0; j < NT; ++j) {
+                    acc[half][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[t].x, bw[t][j].x, acc[half][j], 0, 0, 0);
+                    acc[half][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[t].y, bw[t][j].y, acc[half][j], 0, 0, 0);
+                }
+            }
+        }
+        wave_lds_sync();
+        if (unit + nwaves < p.units) {
+            EFGH_STAGE()
+            if (unit + 2 * nwaves < p.units) EFGH_FETCH(unit + 2 * nwaves)
+        }
+#pragma unroll
+        for (int j = 0; j < NT; ++j) {
+            // acc[half][j][q] <- draw of (row 2 oip + half, pixel pl(q)), cell by cell
+#pragma unroll
+            for (int q = 0; q < 16; q += 2) {
+                const int pc = (oj0 >> 1) + ((q & 3) >> 1) + 4 * (q >> 2) + 2 * h;
+                const bool pooled = oip < Hp && pc < Wp;
+                const float rw[4] = {acc[0][j][q] + bi[j], acc[0][j][q + 1] + bi[j], acc[1][j][q] + bi[j], acc[1][j][q + 1] + bi[j]};
+                float e[4];
+#pragma unroll
+                for (int k = 0; k < 4; ++k) e[k] = relu_sel(fmaf(rw[k], sc[j], sf[j]));
+                const int best = first_max4(e);
+                // ReLU: act' at the winner is 1 where its activated value - the window's maximum - is positive, else 0
+                const float emax = fmaxf(fmaxf(e[0], e[1]), fmaxf(e[2], e[3]));
+                const float dwin = pooled ? g[j][q >> 1] * (emax > 0.f ? 1.f : 0.f) : 0.f;
+                const double twin = bn_draw_dpre_m1(dwin, m1[j]);
+                float o[4];
+#pragma unroll
+                for (int k = 0; k < 4; ++k) o[k] = bn_draw_f64(rw[k], k == best ? twin : zm1[j], mu[j], is[j], cf[j], m2[j]);
+                acc[0][j][q] = o[0]; acc[0][j][q + 1] = o[1]; acc[1][j][q] = o[2]; acc[1][j][q + 1] = o[3];
+            }
+#pragma unroll
+            for (int half = 0; half < 2; ++half) {
+                if (half == 1 && !row1) break;
+                wave_lds_sync();                     // the tile's previous readers are done
+#pragma unroll
+                for (int q = 0; q < 16; ++q) T[((q & 3) + 8 * (q >> 2) + 4 * h) * TPITCH + r] = acc[half][j][q];
+                wave_lds_sync();
+                float *drow = p.draw + (((ob * p.Ho + 2 * oip + half) * p.Wo) + oj0) * (long long)p.N + 32 * j;
+#pragma unroll
+                for (int pass = 0; pass < 4; ++pass) {
+                    const int pl = 8 * pass + (lane >> 3), c4 = (lane & 7) * 4;
+                    const float4 v = *reinterpret_cast<const float4 *>(&T[pl * TPITCH + c4]);
+                    if (oj0 + pl < p.Wo) st_stream<NTS>(drow + (long long)pl * p.N + c4, v);
+                }
             }
         }
     }
@@ -443,6 +633,7 @@ void fill(C4Args &a, const efgh_gemm_desc *d) {
     a.jblocks = (d->Wo + TP - 1) / TP;
     a.units = (long long)d->B * d->Ho * a.jblocks;
     a.G = nullptr; a.ldg = 0; a.dW = nullptr;
+    a.mean = a.invstd = a.coef = a.dyp = nullptr; a.m1 = a.m2 = nullptr; a.raw_win = a.draw = nullptr;
 }
 
 int grid_of(long long units) {                     // persistent: 3 workgroups of 4 waves per CU
@@ -494,6 +685,62 @@ extern "C" int efgh_c4_conv3x3_pooled(const efgh_gemm_desc *d, void *stream_) {
     if (d->N == 32) k_c4_conv_pool<1><<<grid, 64 * WAVES, 0, st>>>(a);
     else if (d->N == 64) k_c4_conv_pool<2><<<grid, 64 * WAVES, 0, st>>>(a);
     else k_c4_conv_pool<4><<<grid, 64 * WAVES, 0, st>>>(a);
+    EFGH_CHECK_LAUNCH();
+    return EFGH_OK;
+}
+
+// ---- the train-mode pooled layer without its full-resolution map: statistics pass, pooled forward, recomputing apply ----
+extern "C" int efgh_c4_conv3x3_stats(const efgh_gemm_desc *d, void *stream_) {
+    hipStream_t st = (hipStream_t)stream_;
+    EFGH_CHECK_ARG(efgh_c4_supported(d) && d->W && d->stats && !d->residual && (((uintptr_t)d->W) & 7) == 0);
+    C4Args a;
+    fill(a, d);
+    a.out = nullptr;
+    const int grid = grid_of(a.units);               // the grid of efgh_c4_conv3x3: one statistics row per workgroup
+    if (d->N == 32) k_c4_conv<1, false, false><<<grid, 64 * WAVES, 0, st>>>(a);
+    else if (d->N == 64) k_c4_conv<2, false, false><<<grid, 64 * WAVES, 0, st>>>(a);
+    else k_c4_conv<4, false, false><<<grid, 64 * WAVES, 0, st>>>(a);
+    EFGH_CHECK_LAUNCH();
+    return EFGH_OK;
+}
+
+extern "C" int efgh_c4_conv3x3_pooled_train(const efgh_gemm_desc *d, const float *mean, const float *invstd, float *raw_win,
+                                            void *stream_) {
+    hipStream_t st = (hipStream_t)stream_;
+    EFGH_CHECK_ARG(efgh_c4_pooled_supported(d) && d->W && d->out && (((uintptr_t)d->W) & 7) == 0);
+    EFGH_CHECK_ARG(d->ldo % 4 == 0 && (((uintptr_t)d->out) & 15) == 0);
+    EFGH_CHECK_ARG(d->act == 1 && d->scale && d->shift && mean && invstd && raw_win);
+    C4Args a;
+    fill(a, d);
+    a.units = (long long)d->B * (d->Ho / 2) * a.jblocks;
+    a.mean = mean; a.invstd = invstd; a.raw_win = raw_win;
+    const int grid = grid_of(a.units);
+    if (d->N == 32) k_c4_conv_pool<1, true><<<grid, 64 * WAVES, 0, st>>>(a);
+    else if (d->N == 64) k_c4_conv_pool<2, true><<<grid, 64 * WAVES, 0, st>>>(a);
+    else k_c4_conv_pool<4, true><<<grid, 64 * WAVES, 0, st>>>(a);
+    EFGH_CHECK_LAUNCH();
+    return EFGH_OK;
+}
+
+extern "C" int efgh_c4_pool_bwd_draw(const efgh_gemm_desc *d, const float *dy_pool, const float *mean, const float *invstd,
+                                     const float *coef, const double *m1, const double *m2, float *draw, void *stream_) {
+    hipStream_t st = (hipStream_t)stream_;
+    EFGH_CHECK_ARG(efgh_c4_pooled_supported(d) && d->W && (((uintptr_t)d->W) & 7) == 0 && d->scale && d->shift);
+    EFGH_CHECK_ARG(d->act == 1 && dy_pool && mean && invstd && coef && m1 && m2 && draw && (((uintptr_t)draw) & 15) == 0);
+    C4Args a;
+    fill(a, d);
+    a.out = nullptr;
+    a.units = (long long)d->B * ((d->Ho + 1) / 2) * a.jblocks;     // row pairs (the last one of an odd map has one row) x 32-pixel blocks
+    a.mean = mean; a.invstd = invstd; a.coef = coef; a.m1 = m1; a.m2 = m2; a.dyp = dy_pool; a.draw = draw;
+    const int grid = grid_of(a.units);
+    const bool nt = efgh_stream_nt((long long)d->M * d->N * 4);
+#define EFGH_GO(NT)                                                                  \
+    {                                                                               \
+        if (nt) k_c4_pool_bwd_draw<NT, true><<<grid, 64 * WAVES, 0, st>>>(a);       \
+        else k_c4_pool_bwd_draw<NT, false><<<grid, 64 * WAVES, 0, st>>>(a);         \
+    }
+    if (d->N == 32) EFGH_GO(1) else if (d->N == 64) EFGH_GO(2) else EFGH_GO(4)
+#undef EFGH_GO
     EFGH_CHECK_LAUNCH();
     return EFGH_OK;
 }

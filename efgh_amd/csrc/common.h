@@ -119,6 +119,33 @@ static inline efgh_bias_corr efgh_bias_corrections(float beta1, float beta2, int
 // that form (neg * v + 0: a clamped value is +0, never -0).
 __device__ __forceinline__ float act_neg(float v, float neg) { return v > 0.f ? v : fmaf(neg, v, 0.f); }
 
+// ---- BatchNorm backward of a ReLU layer whose activation went straight into MaxPool2d(2,2), from pooled tensors (backward.hip's
+// k_pool_bn_bwd_reduce_y; c4conv.hip's train-mode pooled convolution, which stores raw_win for the same channels) ----
+// does a channel take xhat from raw at the window's winner instead of (y - beta) / gamma?  gamma == 0 (pscale == 0), or
+// |beta| > EFGH_POOLED_BETA_GAMMA |gamma| with beta = mean*pscale + pshift, gamma = pscale / invstd (k_pool_bn_bwd_reduce_y says why)
+#ifndef EFGH_POOLED_BETA_GAMMA
+#define EFGH_POOLED_BETA_GAMMA 2.0f
+#endif
+__device__ __forceinline__ bool pooled_xhat_from_raw(float mean, float invstd, float pscale, float pshift) {
+    const float beta = fmaf(mean, pscale, pshift);
+    return pscale == 0.f || fabsf(beta) * fabsf(invstd) > EFGH_POOLED_BETA_GAMMA * fabsf(pscale);
+}
+
+// draw of one element in a train-mode BatchNorm backward's apply pass, float64 per element: coef * (dpre - m1 - xhat * m2) with
+// xhat = (raw - mean) * invstd.  The operations are WRITTEN OUT as k_pool_bn_bwd_apply's expression compiles (the product xhat * m2
+// and the subtraction are one v_fma_f64), so that a kernel that recomputes raw gives the bits of the one that reads it.  In two
+// steps, because dpre - m1 has one value for every element of a channel that is not a window's winner (dpre = 0).
+__device__ __forceinline__ double bn_draw_dpre_m1(float dpre, double m1) {
+#pragma clang fp contract(off)
+    return (double)dpre - m1;
+}
+__device__ __forceinline__ float bn_draw_f64(float raw, double dpre_m1, double mean, double invstd, double coef, double m2) {
+#pragma clang fp contract(off)
+    const double d = (double)raw - mean;
+    const double xh = d * invstd;
+    return (float)(coef * fma(-xh, m2, dpre_m1));
+}
+
 // streaming accesses of the HBM-bound passes (an activation that is read or written exactly once by the kernel).  NT = true: with
 // the non-temporal hint (the line is not kept in L2 / MALL) - measured +5-10 % on the BatchNorm passes over tensors that do not
 // fit the 256-MB MALL anyway (tools/bench_elementwise.py: reduce 5.25 -> 5.64 TB/s, normalise 5.02 -> 5.26 at 1 GB), and a LOSS

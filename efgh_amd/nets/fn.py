@@ -217,19 +217,35 @@ class GemmLayerFn(torch.autograd.Function):
         M = spec.M
         bn = spec.bn
         b = None if bias is None else ops.pad_vec(bias.detach(), Np)
-        out = torch.empty(tuple(spec.out_shape) + (Np,), dtype=torch.float32, device=dev)
         res = None if residual is None else as_rows(residual)
         mean = invstd = raw = None
         need_stats = bn is not None and spec.train
         assert spec.custom_forward is None or (bn is not None and bias is None)
+        # a pooled 4-channel input layer (train-mode BatchNorm + ReLU, stride 1, no residual) under a recording tape: the
+        # full-resolution raw map is neither written nor saved - statistics pass, batch statistics, pooled pass; the backward
+        # recomputes raw (ops.C4_POOL_RECOMPUTE).  Its sums are those of ops.pool_bn_bwd's pooled reduction, so it follows that switch
+        c4 = raw_win = None
+        if (ops.C4_POOL_RECOMPUTE and ops.POOL_REDUCE_FROM_Y and spec.pool and need_stats and spec.act == ops.ACT_RELU and res is None
+                and Np == N and lazy is None and spec.custom_forward is None and len(spec.launches) == 1
+                and x.shape[-1] == spec.C and any(ctx.needs_input_grad)):
+            c4 = ops.C4PoolLayer(x, ld_of(x), spec.layouts[0].pack(weight), Np, spec.launches[0][0], spec.launches[0][1], b)
+            if not ops.c4_pool_recompute_ok(c4, spec.mode, spec.C):
+                c4 = None
+        ctx.c4 = c4 is not None
+        out = None if c4 is not None else torch.empty(tuple(spec.out_shape) + (Np,), dtype=torch.float32, device=dev)
         w2v = bool(ctx.needs_input_grad[1])
-        if bn is None:                      # bias (+residual) (+act) straight in the epilogue
+        if c4 is not None:
+            stats = ops.c4_pool_stats(c4)
+            scale, shift, mean, invstd = bn_batch_stats(bn, stats, Np, float(M), save=True)
+            y, raw_win = ops.c4_pool_forward(c4, scale, shift, mean, invstd)
+        elif bn is None:                    # bias (+residual) (+act) straight in the epilogue
             run_launches(spec, x, ld_of(x), weight, out, Np, b, False, lazy=lazy, w2v=w2v, residual=res,
                          ldr=0 if res is None else ld_of(res), act=spec.act, slope=spec.slope)
         else:
             stats = run_launches(spec, x, ld_of(x), weight, out, Np, b, need_stats, lazy=lazy, w2v=w2v)
-        y = out
-        if bn is not None:
+        if c4 is None:
+            y = out
+        if bn is not None and c4 is None:
             raw = out
             if need_stats:
                 scale, shift, mean, invstd = bn_batch_stats(bn, stats, Np, float(M), save=True)
@@ -289,7 +305,9 @@ class GemmLayerFn(torch.autograd.Function):
         # layers without a residual re-derive the activation mask from raw*scale+shift in backward
         psc, psh = (scale, shift) if (bn is not None and residual is None) else (None, None)
         # coef = gamma * invstd of the BatchNorm backward is the forward's `scale`
-        ctx.save_for_backward(x, weight, y, raw, mean, invstd, scale if bn is not None else None, psc, psh)
+        # (the recompute path saves raw_win - pooled size - and the padded bias its convolution re-runs with; raw is None there)
+        ctx.save_for_backward(x, weight, y, raw, mean, invstd, scale if bn is not None else None, psc, psh, raw_win,
+                              b if c4 is not None else None)
         if spec.passthrough:
             return y, x.view_as(x)
         return y
@@ -312,7 +330,7 @@ class GemmLayerFn(torch.autograd.Function):
             sums = None
         if dy is None:                        # (only the alias was used downstream)
             dy = torch.zeros(tuple(spec.out_shape) + (ceil4(spec.N),), dtype=torch.float32, device=ctx.saved_tensors[0].device)
-        x, weight, y, raw, mean, invstd, coef, psc, psh = ctx.saved_tensors
+        x, weight, y, raw, mean, invstd, coef, psc, psh, raw_win, c4_bias = ctx.saved_tensors
         ymask = None if psc is not None else y
         ybits = ctx.ybits
         has_bias, has_bn, has_res = ctx.has
@@ -351,7 +369,16 @@ class GemmLayerFn(torch.autograd.Function):
         fuse_bwd = (ops.W2_BWD_FUSED and spec.bwd_fusable and has_bn and spec.train and Np == N
                     and ctx.needs_input_grad[0] and own_wgrad and (ybits is not None or (psc is not None and not has_res))
                     and len(spec.out_shape) == 3 and ((fused_pool and ops.W2_BWD_FUSED_POOL) or not spec.pool))
-        if fused_pool:
+        if fused_pool and ctx.c4:
+            # ... and without the raw map: the sums from the pooled tensors and raw_win, draw from the recomputed convolution
+            assert not fuse_bwd
+            c4 = ops.C4PoolLayer(x, ld_of(x), spec.layouts[0].pack(weight), Np, spec.launches[0][0], spec.launches[0][1], c4_bias)
+            draw, s1, s2 = ops.c4_pool_bn_bwd(c4, dy.contiguous(), y, raw_win, mean, invstd, coef, psc, psh, s1=gs1, s2=gs2)
+            if gs1 is None:
+                dbeta, dgamma = s1, s2
+            if has_bias:
+                dbias = _bias_grad_behind_bn(ctx, p_bias, draw, M, Np, N, True, delivered)
+        elif fused_pool:
             # BatchNorm backward straight from the pooled gradient (no full-resolution dy is ever written)
             draw, s1, s2 = ops.pool_bn_bwd(dy.contiguous(), raw, mean, invstd, coef, psc, psh, spec.act, spec.slope,
                                            s1=gs1, s2=gs2, transforms=fuse_bwd, y_pool=y)

@@ -1635,6 +1635,86 @@ def pool_bn_bwd(dy_pool, raw, mean, invstd, coef, pscale, pshift, act, slope, s1
     return draw, s1, s2
 
 
+C4_POOL_RECOMPUTE = True        # training: the pooled 4-channel input layers (conv + BatchNorm + ReLU + MaxPool2d(2,2)) never store their
+#                                 full-resolution raw map - the forward takes statistics and pooled output in two passes over the input,
+#                                 the backward recomputes raw inside its apply pass (c4conv.hip); bit-identical to the stored-raw path
+C4_POOL_RECOMPUTE_MIN_BYTES = 384 << 20      # ... where the raw map has at least this many bytes (efgh_stream_nt's bound: beyond the
+#                                 256-MB MALL).  What the path removes is HBM traffic and resident memory; a map that stays in the
+#                                 caches has neither to give, and keeps the launches it has always had.  0: every qualifying layer (tests)
+
+
+class C4PoolLayer:
+    """one pooled 4-channel layer on the recompute path: its input, packed weight, bias and geometry, as the three launches that
+    re-run its convolution take them (nets/fn.py builds it in the forward and keeps it for the backward)"""
+    __slots__ = ('x', 'lda', 'Wp', 'N', 'geom', 'M', 'bias')
+
+    def __init__(self, x, lda, Wp, N, geom, M, bias):
+        self.x, self.lda, self.Wp, self.N, self.geom, self.M, self.bias = x, lda, Wp, N, geom, M, bias
+
+    def desc(self, **kw):
+        return _desc(self.x, self.lda, 4, 9, 1, self.N, self.M, self.geom, None, 0, self.Wp, bias=self.bias, **kw)
+
+    @property
+    def full_shape(self):
+        return (self.geom[0], self.geom[9], self.geom[10], self.N)
+
+    @property
+    def pooled_shape(self):
+        return (self.geom[0], self.geom[9] // 2, self.geom[10] // 2, self.N)
+
+
+def c4_pool_recompute_ok(layer, mode, C):
+    """does the recompute path serve this launch?  The switch, the 4-channel route at stride 1, a raw map of at least
+    C4_POOL_RECOMPUTE_MIN_BYTES, and the library's own answer"""
+    if not (C4_POOL_RECOMPUTE and layer.geom is not None and c4_eligible(mode, C, layer.N, layer.geom) and layer.geom[5] == 1):
+        return False
+    if 4 * layer.M * layer.N < C4_POOL_RECOMPUTE_MIN_BYTES:
+        return False
+    return bool(_L().efgh_c4_pooled_supported(ctypes.byref(layer.desc())))
+
+
+def c4_pool_stats(layer):
+    """the statistics rows of the layer's raw output [efgh_c4_stats_rows][2][N], the map itself not written"""
+    B, Ho, Wo, N = layer.full_shape
+    stats = torch.empty((_L().efgh_c4_stats_rows(B, Ho, Wo), 2, N), dtype=torch.float32, device=layer.x.device)
+    ev = _prof_start(PROFILE)
+    _C.check(_L().efgh_c4_conv3x3_stats(ctypes.byref(layer.desc(stats=stats)), _st()))
+    _prof_end(ev, 'c4', (1, layer.M, N, 9, 4), 2.0 * layer.M * N * 36, PROFILE)
+    return stats
+
+
+def c4_pool_forward(layer, scale, shift, mean, invstd):
+    """-> (y [B][Ho/2][Wo/2][N] = maxpool(relu(raw*scale + shift)), raw_win of the same shape: the winner's raw value, written only for
+    the channels whose backward sums need it)"""
+    dev = layer.x.device
+    y = torch.empty(layer.pooled_shape, dtype=torch.float32, device=dev)
+    raw_win = torch.empty(layer.pooled_shape, dtype=torch.float32, device=dev)
+    d = layer.desc(out=y, ldo=layer.N, scale=scale, shift=shift, act=ACT_RELU)
+    ev = _prof_start(PROFILE)
+    _C.check(_L().efgh_c4_conv3x3_pooled_train(ctypes.byref(d), ptr(mean), ptr(invstd), ptr(raw_win), _st()))
+    _prof_end(ev, 'c4', (1, layer.M, layer.N, 9, 4), 2.0 * layer.M * layer.N * 36, PROFILE)
+    return y, raw_win
+
+
+def c4_pool_bn_bwd(layer, dy_pool, y_pool, raw_win, mean, invstd, coef, pscale, pshift, s1=None, s2=None):
+    """pool_bn_bwd of such a layer: the sums from the pooled tensors and raw_win, draw from the recomputed raw
+    -> (draw [B][Ho][Wo][N], dbeta [N], dgamma [N])"""
+    B, H, W, C = layer.full_shape
+    dev = dy_pool.device
+    s1 = s1 if s1 is not None else torch.empty(C, dtype=torch.float32, device=dev)
+    s2 = s2 if s2 is not None else torch.empty(C, dtype=torch.float32, device=dev)
+    m1 = torch.empty(C, dtype=torch.float64, device=dev)
+    m2 = torch.empty(C, dtype=torch.float64, device=dev)
+    part = torch.empty((_L().efgh_bwd_groups(B * (H // 2) * (W // 2)), 2, C), dtype=torch.float64, device=dev)
+    _C.check(_L().efgh_pool_bn_bwd_reduce_pooled_win(ptr(dy_pool), ptr(y_pool), ptr(raw_win), ptr(mean), ptr(invstd), ptr(pscale),
+                                                     ptr(pshift), B, H, W, C, ptr(part), ptr(s1), ptr(s2), ptr(m1), ptr(m2), _st()))
+    draw = torch.empty((B, H, W, C), dtype=torch.float32, device=dev)
+    d = layer.desc(scale=pscale, shift=pshift, act=ACT_RELU)
+    _C.check(_L().efgh_c4_pool_bwd_draw(ctypes.byref(d), ptr(dy_pool), ptr(mean), ptr(invstd), ptr(coef), ptr(m1), ptr(m2), ptr(draw),
+                                        _st()))
+    return draw, s1, s2
+
+
 def act_bn_bwd_apply(dy, lddy, y, ldy, raw, ldraw, mean, invstd, coef, m1, m2, M, C, act, slope, draw, lddraw,
                      dres, lddres, pscale=None, pshift=None):
     _C.check(_L().efgh_act_bn_bwd_apply(ptr(dy), lddy, ptr(y), ldy, ptr(raw), ldraw, ptr(mean), ptr(invstd), ptr(coef), ptr(m1),

@@ -66,7 +66,9 @@ const char *efgh_last_error(void);
  *      efgh_prep_sweeps_filter, efgh_prep_sweeps_gather_transform, efgh_prep_sweeps_materialize (multi-sweep accumulation and
  *      stride-3 rows in sample preparation);
  *      efgh_prep_voxel_workspace, efgh_prep_voxel_keep, efgh_prep_sweeps_voxel_keep (thinning on a voxel grid in sample preparation);
- *      efgh_prep_jitter_partials, efgh_prep_jitter_sum, efgh_prep_jitter_apply (photometric jitter of the image in sample preparation). */
+ *      efgh_prep_jitter_partials, efgh_prep_jitter_sum, efgh_prep_jitter_apply (photometric jitter of the image in sample preparation);
+ *      efgh_c4_conv3x3_stats, efgh_c4_conv3x3_pooled_train, efgh_c4_pool_bwd_draw, efgh_pool_bn_bwd_reduce_pooled_win (the pooled
+ *      4-channel input layers in training without their full-resolution maps). */
 #define EFGH_ABI_VERSION 4
 int efgh_version(void);
 
@@ -593,6 +595,12 @@ int efgh_pool_bn_bwd_reduce_pooled(const float *dy_pool, const float *y_pool, co
                                    const float *invstd, const float *pscale, const float *pshift, int32_t B, int32_t H, int32_t W,
                                    int32_t C, double *part, float *sum_dpre, float *sum_dpre_xhat, double *mean_dpre,
                                    double *mean_dpre_xhat, void *stream);
+/* the same with raw_win [B][H/2][W/2][C] (efgh_c4_conv3x3_pooled_train) in place of raw: the winner's raw value is read at the pooled
+ * index, for exactly the channels above; same sums, bit for bit */
+int efgh_pool_bn_bwd_reduce_pooled_win(const float *dy_pool, const float *y_pool, const float *raw_win, const float *mean,
+                                       const float *invstd, const float *pscale, const float *pshift, int32_t B, int32_t H,
+                                       int32_t W, int32_t C, double *part, float *sum_dpre, float *sum_dpre_xhat,
+                                       double *mean_dpre, double *mean_dpre_xhat, void *stream);
 int efgh_pool_bn_bwd_apply(const float *dy_pool, const float *raw, const float *mean, const float *invstd, const float *coef,
                            const double *m1, const double *m2, const float *pscale, const float *pshift, int32_t B, int32_t H,
                            int32_t W, int32_t C, int32_t act, float slope, float *draw, void *stream);
@@ -838,6 +846,17 @@ int efgh_c4_conv3x3(const efgh_gemm_desc *d, void *stream);
  * POOLED map [B][Ho/2][Wo/2][ldo]; bit-identical to efgh_c4_conv3x3 + efgh_maxpool2 */
 int efgh_c4_pooled_supported(const efgh_gemm_desc *d);
 int efgh_c4_conv3x3_pooled(const efgh_gemm_desc *d, void *stream);
+/* the same layer in TRAINING (train-mode BatchNorm + ReLU + MaxPool2d(2,2), stride 1, no residual) without its full-resolution map:
+ * efgh_c4_conv3x3_stats leaves only the statistics rows of efgh_c4_conv3x3 (same grid, same bits; d->out is not written);
+ * efgh_c4_conv3x3_pooled_train (d->scale / d->shift from those statistics, d->act == 1, d->out the pooled map) gives the bits of
+ * efgh_c4_conv3x3 + efgh_maxpool2_affine and, for the channels whose backward sums take xhat from raw (see
+ * efgh_pool_bn_bwd_reduce_pooled), writes the raw value of each window's first maximum to raw_win [B][Ho/2][Wo/2][N] - nothing for the
+ * other channels; efgh_c4_pool_bwd_draw recomputes raw from d->A and writes draw [B][Ho][Wo][N] with the bits of
+ * efgh_pool_bn_bwd_apply (d->scale / d->shift: pscale / pshift; an odd last row / column gets the dense term only). */
+int efgh_c4_conv3x3_stats(const efgh_gemm_desc *d, void *stream);
+int efgh_c4_conv3x3_pooled_train(const efgh_gemm_desc *d, const float *mean, const float *invstd, float *raw_win, void *stream);
+int efgh_c4_pool_bwd_draw(const efgh_gemm_desc *d, const float *dy_pool, const float *mean, const float *invstd, const float *coef,
+                          const double *m1, const double *m2, float *draw, void *stream);
 int efgh_c4_wgrad_supported(const efgh_gemm_desc *d);
 int64_t efgh_c4_wgrad_workspace(const efgh_gemm_desc *d);
 int efgh_c4_wgrad(const efgh_gemm_desc *d, const float *G, int64_t ldg, float *dWp, float *workspace,
