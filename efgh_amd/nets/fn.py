@@ -187,6 +187,206 @@ class BnSrc:
 TRACE = None          # debug aid (tools/layer_census.py): list of per-layer records appended by GemmLayerFn.backward
 
 
+# ---- the tails of a GEMM layer: what runs between the GEMM output and the returned activation, and its mirror between dy and draw.
+# GemmLayerFn._forward chooses one (_choose_tail) and records its name as ctx.tail; the backward runs that tail's head (TAILS).
+#   forward(ctx, spec, x, weight, b, gamma, beta, res, lazy, out_target) -> (y, what the head reads: saved behind x and weight)
+#   head(ctx, spec, dy, sums, saved, gs1, gs2, delivered) -> (draw, pre_v, pre_gy, dbeta, dgamma, dbias, dres)
+# What a head needs to know besides the saved tensors its forward writes to ctx as plain values: ctx.mask - where the activation
+# mask comes from: 'bits' (sign bits left by the forward), 'y' (the activation), 'affine' (re-derived from raw * scale + shift);
+# ctx.fused_pool (bn_pool).  ctx.train_bn (train-mode statistics) is common to all.
+def _c4_layer(spec, x, weight, b):
+    """the ops.C4PoolLayer of a pooled 4-channel layer (b: its padded bias), for the choice, the forward and the backward alike"""
+    return ops.C4PoolLayer(x, ld_of(x), spec.layouts[0].pack(weight), ceil4(spec.N), spec.launches[0][0], spec.launches[0][1], b)
+
+
+def _choose_tail(spec, x, weight, b, lazy, res, needs_grad):
+    assert not spec.pool or (spec.bn is not None and res is None), 'the pool rides in the BatchNorm pass of a layer without residual'
+    if not spec.pool:
+        return 'plain' if spec.bn is None else 'bn'
+    # a pooled 4-channel input layer (train-mode BatchNorm + ReLU, stride 1) under a recording tape: the full-resolution raw map is
+    # neither written nor saved (ops.C4_POOL_RECOMPUTE).  Its sums are those of ops.pool_bn_bwd's pooled reduction, so it follows
+    # that switch
+    if (ops.C4_POOL_RECOMPUTE and ops.POOL_REDUCE_FROM_Y and spec.train and spec.act == ops.ACT_RELU and ceil4(spec.N) == spec.N
+            and lazy is None and spec.custom_forward is None and len(spec.launches) == 1 and x.shape[-1] == spec.C and needs_grad
+            and ops.c4_pool_recompute_ok(_c4_layer(spec, x, weight, b), spec.mode, spec.C)):
+        return 'bn_pool_c4'
+    return 'bn_pool'
+
+
+def _fuse_bwd(ctx, spec):
+    """may the apply pass of the BatchNorm backward run inside the gradient-side transforms of a 2-D Winograd layer (draw is never
+    stored)?"""
+    return (ops.W2_BWD_FUSED and spec.bwd_fusable and ctx.train_bn and ceil4(spec.N) == spec.N and ctx.needs_input_grad[0]
+            and ctx.needs_input_grad[1] and spec.custom_wgrad is None and ctx.mask != 'y' and len(spec.out_shape) == 3)
+
+
+def _reduce_apply(ctx, spec, dy, sums, raw, mean, invstd, scale, shift, mask, gs1, gs2, fuse_bwd, delivered):
+    """the generic backward head: the two column sums over dy (or `sums`, taken by the kernel that produced dy), then the apply pass
+    into draw (+ dres) or, fuse_bwd, into the layer's two gradient-side transforms.  mask: the tensor ctx.mask speaks of"""
+    has_bias, has_bn, has_res = ctx.has
+    N, Np, M = spec.N, ceil4(spec.N), spec.M
+    psc, psh = (scale, shift) if ctx.mask == 'affine' else (None, None)
+    ldy = Np if mask is None else 0 if ctx.mask == 'bits' else ld_of(mask)      # (sign bits: `y` with ldy = 0, see efgh_act_bn_bwd_reduce)
+    draw = pre_v = pre_gy = dbeta = dgamma = dbias = dres = None
+    part = torch.empty((ops.bwd_groups(M), 2, Np), dtype=torch.float64, device=dy.device)      # float64 column sums (see backward.hip)
+    s1, s2, m1, m2 = ops.bwd_sums(Np, dy.device, gs1, gs2, means=ctx.train_bn)
+    if sums is not None and ctx.train_bn:
+        # the kernel that produced dy took the two column sums in its epilogue: fold its per-block partials
+        s1, s2, m1, m2 = ops.bwd_finalize_f32(sums[0], Np, float(M))
+        if gs1 is not None:
+            s1, s2 = gs1.copy_(s1), gs2.copy_(s2)
+    else:
+        ops.act_bn_bwd_reduce(dy, ld_of(dy), mask, ldy, raw, Np, mean, invstd, M, Np, spec.act, spec.slope, part, s1, s2, m1, m2,
+                              pscale=psc, pshift=psh)
+    if has_bn and gs1 is None:
+        # (s1 / s2 are this backward's own tensors: handed to autograd as they are when there is no padding to cut off)
+        dbeta, dgamma = (s1, s2) if Np == N else (s1[:N].clone(), s2[:N].clone())
+    if has_bias and not has_bn and gs1 is None:
+        dbias = s1 if Np == N else s1[:N].clone()
+    if fuse_bwd:
+        pre_v, pre_gy, dres = ops.wino2d_bwd_transforms(dy, ld_of(dy), raw, Np, mask, psc, psh, mean, invstd, scale, m1, m2, Np,
+                                                        *spec.out_shape, spec.act, spec.slope, has_res)
+    else:
+        draw = torch.empty(tuple(spec.out_shape) + (Np,), dtype=torch.float32, device=dy.device)
+        dres = torch.empty_like(draw) if has_res else None
+        ops.act_bn_bwd_apply(dy, ld_of(dy), mask, ldy, raw, Np, mean if ctx.train_bn else None, invstd if ctx.train_bn else None, scale,
+                             m1, m2, M, Np, spec.act, spec.slope, draw, Np, dres, Np, pscale=psc, pshift=psh)
+    if has_bias and has_bn:          # bias in front of BatchNorm: d/dbias = column sums of draw
+        dbias = _bias_grad_behind_bn(ctx, ctx.params[1], draw, M, Np, N, ctx.train_bn, delivered)
+    return draw, pre_v, pre_gy, dbeta, dgamma, dbias, dres
+
+
+def _pooled_sums(ctx, spec, draw, s1, s2, gs1, delivered):
+    """what a fused-pool head returns behind ops.pool_bn_bwd / ops.c4_pool_bn_bwd (train-mode BatchNorm, no padding, no residual)"""
+    dbias = _bias_grad_behind_bn(ctx, ctx.params[1], draw, spec.M, spec.N, spec.N, True, delivered) if ctx.has[0] else None
+    return (s1, s2, dbias, None) if gs1 is None else (None, None, dbias, None)
+
+
+def _plain_fwd(ctx, spec, x, weight, b, gamma, beta, res, lazy, out_target):
+    """bias (+ residual) (+ activation) straight in the GEMM epilogue"""
+    Np = ceil4(spec.N)
+    y = torch.empty(tuple(spec.out_shape) + (Np,), dtype=torch.float32, device=x.device)
+    run_launches(spec, x, ld_of(x), weight, y, Np, b, False, lazy=lazy, w2v=bool(ctx.needs_input_grad[1]), residual=res,
+                 ldr=0 if res is None else ld_of(res), act=spec.act, slope=spec.slope)
+    ctx.mask = 'y'
+    return y, (y,)
+
+
+def _plain_bwd(ctx, spec, dy, sums, saved, gs1, gs2, delivered):
+    has_bias, _, has_res = ctx.has
+    if not (spec.act != ACT_NONE or has_res or has_bias):      # no pre-activation gradient is needed
+        return dy, None, None, None, None, None, None
+    return _reduce_apply(ctx, spec, dy, sums, None, None, None, None, None, saved[2], gs1, gs2, False, delivered)
+
+
+def _bn_raw(ctx, spec, x, weight, b, gamma, beta, lazy):
+    """-> raw, scale, shift, mean, invstd: the raw GEMM output of a BatchNorm layer and its affine map - from the batch statistics
+    taken with it in train mode, from the running ones otherwise"""
+    bn, Np = spec.bn, ceil4(spec.N)
+    raw = torch.empty(tuple(spec.out_shape) + (Np,), dtype=torch.float32, device=x.device)
+    stats = run_launches(spec, x, ld_of(x), weight, raw, Np, b, spec.train, lazy=lazy, w2v=bool(ctx.needs_input_grad[1]))
+    if spec.train:
+        return (raw,) + tuple(bn_batch_stats(bn, stats, Np, float(spec.M), save=True))
+    with torch.no_grad():
+        invstd = ops.pad_vec(torch.rsqrt(bn.running_var + bn.eps), Np)
+        mean = ops.pad_vec(bn.running_mean.clone(), Np)
+        scale = ops.pad_vec(gamma.detach(), Np) * invstd
+        shift = ops.pad_vec(beta.detach(), Np) - mean * scale
+    return raw, scale, shift, mean, invstd
+
+
+def _bn_fwd(ctx, spec, x, weight, b, gamma, beta, res, lazy, out_target):
+    N, Np, M = spec.N, ceil4(spec.N), spec.M
+    raw, scale, shift, mean, invstd = _bn_raw(ctx, spec, x, weight, b, gamma, beta, lazy)
+    # layers without a residual re-derive the activation mask from raw * scale + shift in backward
+    ctx.mask, mask = 'affine', None
+    if (spec.defer_act and ops.LAZY_ACT and spec.train and res is None and Np == N and out_target is None
+            and spec.custom_forward is None):
+        # the single consumer (a 2-D Winograd layer) normalises and activates inside its input transform: no pass here, no
+        # activation tensor (an ALIAS object of raw, not raw itself: the BnSrc tag below refers to raw, and y referring to something
+        # that refers to y would be a cycle - a step's activations would wait for the garbage collector instead of their reference
+        # counts)
+        y = raw.detach()
+        y._efgh_lazy = ops.LazyAct(scale, shift, spec.act, spec.slope)
+    else:
+        # out_target = (buffer [..][Ct], channel offset): the activation is written straight into that channel slice (the
+        # training-path form of the decoder's torch.cat, see ConcatFn); the returned tensor is a view of the buffer
+        y = None
+        if out_target is not None and Np == N:
+            tb, toff = out_target
+            if tuple(tb.shape[:-1]) == tuple(raw.shape[:-1]) and toff % 4 == 0 and toff + N <= tb.shape[-1]:
+                y = tb[..., toff:toff + N]
+        if y is None:
+            y = torch.empty_like(raw)
+        # a residual layer's activation mask cannot be re-derived from raw alone: its backward used to read the activation back in
+        # both passes; the forward pass leaves the SIGN BITS instead (M*N/32 words)
+        if res is not None:
+            ctx.mask, mask = 'y', y
+            if spec.train and ops.BN_MASK_BITS and Np % 32 == 0 and spec.act != ACT_NONE and any(ctx.needs_input_grad):
+                ctx.mask, mask = 'bits', torch.empty(M * Np // 32, dtype=torch.int32, device=x.device)
+        ops.scale_shift_act(raw, Np, scale, shift, y, ld_of(y), M, Np, spec.act, spec.slope, res=res,
+                            ldr=0 if res is None else ld_of(res), bits=mask if ctx.mask == 'bits' else None)
+    if spec.train and Np == N and any(ctx.needs_input_grad):
+        # (y.detach(): an alias object - y itself carrying a reference to something that refers to y would be a cycle, and a step's
+        # activations would wait for the garbage collector instead of being freed by reference count)
+        ctx.bnsrc = y._efgh_bnsrc = BnSrc(raw, y.detach() if res is not None else None, scale, shift, mean, invstd,
+                                          spec.act, spec.slope, M, Np)
+    # coef = gamma * invstd of the BatchNorm backward is the forward's `scale`
+    return y, (raw, mean, invstd, scale, shift if res is None else None, mask)
+
+
+def _bn_bwd(ctx, spec, dy, sums, saved, gs1, gs2, delivered):
+    raw, mean, invstd, scale, shift, mask = saved[2:]
+    return _reduce_apply(ctx, spec, dy, sums, raw, mean, invstd, scale, shift, mask, gs1, gs2, _fuse_bwd(ctx, spec), delivered)
+
+
+def _bn_pool_fwd(ctx, spec, x, weight, b, gamma, beta, res, lazy, out_target):
+    """BatchNorm + activation + MaxPool2d(2,2) as one pass over raw; the full-resolution activation is never stored"""
+    raw, scale, shift, mean, invstd = _bn_raw(ctx, spec, x, weight, b, gamma, beta, lazy)
+    y = ops.maxpool2_affine(raw, scale, shift, spec.act, spec.slope)
+    ctx.mask = 'affine'
+    ctx.c4 = False                            # (True: the tail below, raw not stored - for whoever inspects the node, as the tests do)
+    # fused: the BatchNorm backward runs straight from the pooled gradient (ops.pool_bn_bwd), which reads the pooled y
+    ctx.fused_pool = spec.train and ceil4(spec.N) == spec.N
+    return y, (raw, mean, invstd, scale, shift, y if ctx.fused_pool else None)
+
+
+def _bn_pool_bwd(ctx, spec, dy, sums, saved, gs1, gs2, delivered):
+    raw, mean, invstd, scale, shift, y = saved[2:]
+    if not ctx.fused_pool:    # pooled gradient -> full resolution (window recomputed from raw*scale+shift), then as an un-pooled layer
+        dy = as_rows(ops.maxpool2_bwd_affine(raw, scale, shift, spec.act, spec.slope, dy.contiguous()))
+        return _reduce_apply(ctx, spec, dy, sums, raw, mean, invstd, scale, shift, None, gs1, gs2, False, delivered)
+    # (no full-resolution dy is ever written; transforms: neither is draw)
+    fuse = _fuse_bwd(ctx, spec) and ops.W2_BWD_FUSED_POOL
+    draw, s1, s2 = ops.pool_bn_bwd(dy.contiguous(), raw, mean, invstd, scale, scale, shift, spec.act, spec.slope, s1=gs1, s2=gs2,
+                                   transforms=fuse, y_pool=y)
+    (pre_v, pre_gy), draw = (draw, None) if fuse else ((None, None), draw)
+    return (draw, pre_v, pre_gy) + _pooled_sums(ctx, spec, draw, s1, s2, gs1, delivered)
+
+
+def _bn_pool_c4_fwd(ctx, spec, x, weight, b, gamma, beta, res, lazy, out_target):
+    """... and without the raw map: statistics pass, batch statistics, pooled pass.  raw_win (pooled size) and the padded bias the
+    backward's convolution re-runs with are saved in its place"""
+    c4 = _c4_layer(spec, x, weight, b)
+    scale, shift, mean, invstd = bn_batch_stats(spec.bn, ops.c4_pool_stats(c4), c4.N, float(spec.M), save=True)
+    y, raw_win = ops.c4_pool_forward(c4, scale, shift, mean, invstd)
+    ctx.c4 = True
+    return y, (y, raw_win, mean, invstd, scale, shift, b)
+
+
+def _bn_pool_c4_bwd(ctx, spec, dy, sums, saved, gs1, gs2, delivered):
+    """the sums from the pooled tensors and raw_win, draw from the recomputed convolution"""
+    x, weight, y, raw_win, mean, invstd, scale, shift, b = saved
+    assert not spec.bwd_fusable              # (a 4-channel layer is never on the 2-D Winograd path)
+    draw, s1, s2 = ops.c4_pool_bn_bwd(_c4_layer(spec, x, weight, b), dy.contiguous(), y, raw_win, mean, invstd, scale, scale, shift,
+                                      s1=gs1, s2=gs2)
+    return (draw, None, None) + _pooled_sums(ctx, spec, draw, s1, s2, gs1, delivered)
+
+
+TAILS = {'plain': (_plain_fwd, _plain_bwd), 'bn': (_bn_fwd, _bn_bwd), 'bn_pool': (_bn_pool_fwd, _bn_pool_bwd),
+         'bn_pool_c4': (_bn_pool_c4_fwd, _bn_pool_c4_bwd)}
+
+
 class GemmLayerFn(torch.autograd.Function):
     """y = act(BN(gemm(x, W) + bias) + residual)   with hand-written backward."""
 
@@ -212,105 +412,23 @@ class GemmLayerFn(torch.autograd.Function):
                                      and ops.lazy_capable(spec.mode, spec.C, ceil4(spec.N), spec.launches[0][0])):
             x, lazy = materialize(x, lazy), None              # (a consumer the producer was not told about: never wrong, only slower)
         ctx.lazy = lazy
-        dev = x.device
-        N, Np = spec.N, ceil4(spec.N)
-        M = spec.M
-        bn = spec.bn
-        b = None if bias is None else ops.pad_vec(bias.detach(), Np)
+        b = None if bias is None else ops.pad_vec(bias.detach(), ceil4(spec.N))
         res = None if residual is None else as_rows(residual)
-        mean = invstd = raw = None
-        need_stats = bn is not None and spec.train
-        assert spec.custom_forward is None or (bn is not None and bias is None)
-        # a pooled 4-channel input layer (train-mode BatchNorm + ReLU, stride 1, no residual) under a recording tape: the
-        # full-resolution raw map is neither written nor saved - statistics pass, batch statistics, pooled pass; the backward
-        # recomputes raw (ops.C4_POOL_RECOMPUTE).  Its sums are those of ops.pool_bn_bwd's pooled reduction, so it follows that switch
-        c4 = raw_win = None
-        if (ops.C4_POOL_RECOMPUTE and ops.POOL_REDUCE_FROM_Y and spec.pool and need_stats and spec.act == ops.ACT_RELU and res is None
-                and Np == N and lazy is None and spec.custom_forward is None and len(spec.launches) == 1
-                and x.shape[-1] == spec.C and any(ctx.needs_input_grad)):
-            c4 = ops.C4PoolLayer(x, ld_of(x), spec.layouts[0].pack(weight), Np, spec.launches[0][0], spec.launches[0][1], b)
-            if not ops.c4_pool_recompute_ok(c4, spec.mode, spec.C):
-                c4 = None
-        ctx.c4 = c4 is not None
-        out = None if c4 is not None else torch.empty(tuple(spec.out_shape) + (Np,), dtype=torch.float32, device=dev)
-        w2v = bool(ctx.needs_input_grad[1])
-        if c4 is not None:
-            stats = ops.c4_pool_stats(c4)
-            scale, shift, mean, invstd = bn_batch_stats(bn, stats, Np, float(M), save=True)
-            y, raw_win = ops.c4_pool_forward(c4, scale, shift, mean, invstd)
-        elif bn is None:                    # bias (+residual) (+act) straight in the epilogue
-            run_launches(spec, x, ld_of(x), weight, out, Np, b, False, lazy=lazy, w2v=w2v, residual=res,
-                         ldr=0 if res is None else ld_of(res), act=spec.act, slope=spec.slope)
-        else:
-            stats = run_launches(spec, x, ld_of(x), weight, out, Np, b, need_stats, lazy=lazy, w2v=w2v)
-        if c4 is None:
-            y = out
-        if bn is not None and c4 is None:
-            raw = out
-            if need_stats:
-                scale, shift, mean, invstd = bn_batch_stats(bn, stats, Np, float(M), save=True)
-            else:
-                with torch.no_grad():
-                    invstd = ops.pad_vec(torch.rsqrt(bn.running_var + bn.eps), Np)
-                    mean = ops.pad_vec(bn.running_mean.clone(), Np)
-                    scale = ops.pad_vec(gamma.detach(), Np) * invstd
-                    shift = ops.pad_vec(beta.detach(), Np) - mean * scale
-            if spec.pool:
-                assert res is None
-                y = ops.maxpool2_affine(raw, scale, shift, spec.act, spec.slope)
-            elif (spec.defer_act and ops.LAZY_ACT and need_stats and res is None and Np == N and out_target is None
-                  and spec.custom_forward is None):
-                # the single consumer (a 2-D Winograd layer) normalises and activates inside its input transform: no pass here,
-                # no activation tensor; this layer's own backward re-derives the mask from raw*scale + shift as it always did
-                # (an ALIAS object of raw, not raw itself: the BnSrc tag below refers to raw, and y referring to something that refers to
-                # y would be a cycle - a step's activations would wait for the garbage collector instead of their reference counts)
-                y = raw.detach()
-                y._efgh_lazy = ops.LazyAct(scale, shift, spec.act, spec.slope)
-            else:
-                # out_target = (buffer [..][Ct], channel offset): the activation is written straight into that channel slice (the
-                # training-path form of the decoder's torch.cat, see ConcatFn); the returned tensor is a view of the buffer
-                y = None
-                if out_target is not None and Np == N:
-                    tb, toff = out_target
-                    if tuple(tb.shape[:-1]) == tuple(raw.shape[:-1]) and toff % 4 == 0 and toff + N <= tb.shape[-1]:
-                        y = tb[..., toff:toff + N]
-                if y is None:
-                    y = torch.empty_like(raw)
-                # a residual layer's activation mask cannot be re-derived from raw alone: its backward used to read the activation
-                # back in both passes; the forward pass leaves the SIGN BITS instead (M*N/32 words)
-                ybits = None
-                if (res is not None and need_stats and ops.BN_MASK_BITS and Np % 32 == 0 and spec.act != ACT_NONE
-                        and any(ctx.needs_input_grad)):
-                    ybits = torch.empty(M * Np // 32, dtype=torch.int32, device=dev)
-                ops.scale_shift_act(raw, Np, scale, shift, y, ld_of(y), M, Np, spec.act, spec.slope, res=res,
-                                    ldr=0 if res is None else ld_of(res), bits=ybits)
-                ctx.ybits = ybits
+        assert spec.custom_forward is None or (spec.bn is not None and bias is None)
+        ctx.train_bn = spec.bn is not None and spec.train
+        ctx.bnsrc = None                      # (the `bn` tail tags what it returns with its BnSrc, `_efgh_bnsrc`)
+        ctx.tail = _choose_tail(spec, x, weight, b, lazy, res, any(ctx.needs_input_grad))
+        y, saved = TAILS[ctx.tail][0](ctx, spec, x, weight, b, gamma, beta, res, lazy, out_target)
         if TRACE is not None:
-            y._efgh_src = ('bn' if bn is not None else 'plain', spec.N, spec.pool, residual is not None)
-        ctx.bnsrc = None
-        if need_stats and not spec.pool and Np == N and any(ctx.needs_input_grad):
-            # (mask from y for residual layers, re-derived from raw * scale + shift otherwise - as the layer's own backward does)
-            # (y.detach(): an alias object - y itself carrying a reference to something that refers to y would be a cycle, and a step's
-            # activations would wait for the garbage collector instead of being freed by reference count)
-            ctx.bnsrc = y._efgh_bnsrc = BnSrc(raw, y.detach() if residual is not None else None, scale, shift, mean, invstd,
-                                              spec.act, spec.slope, M, Np)
+            y._efgh_src = ('bn' if spec.bn is not None else 'plain', spec.N, spec.pool, residual is not None)
         ctx.spec = spec
-        if not hasattr(ctx, 'ybits'):
-            ctx.ybits = None
         ctx.train_step = ops.TLS.train_step      # (backward runs on autograd's device thread: it restores the caller's switch)
         ctx.has = (bias is not None, gamma is not None, residual is not None)
         ctx.params = (weight, bias, gamma, beta)      # the Parameter objects themselves (claim_grad), not saved copies
         if any(ctx.needs_input_grad[1:5]):
             note_use(weight, bias, gamma, beta)
-        # layers without a residual re-derive the activation mask from raw*scale+shift in backward
-        psc, psh = (scale, shift) if (bn is not None and residual is None) else (None, None)
-        # coef = gamma * invstd of the BatchNorm backward is the forward's `scale`
-        # (the recompute path saves raw_win - pooled size - and the padded bias its convolution re-runs with; raw is None there)
-        ctx.save_for_backward(x, weight, y, raw, mean, invstd, scale if bn is not None else None, psc, psh, raw_win,
-                              b if c4 is not None else None)
-        if spec.passthrough:
-            return y, x.view_as(x)
-        return y
+        ctx.save_for_backward(x, weight, *saved)
+        return (y, x.view_as(x)) if spec.passthrough else y
 
     @staticmethod
     def backward(ctx, dy, dskip=None):
@@ -328,26 +446,20 @@ class GemmLayerFn(torch.autograd.Function):
         sums = getattr(dy, '_efgh_bnsums', None) if dy is not None else None
         if sums is not None and (sums[1] is not ctx.bnsrc or sums[2] != dy._version):
             sums = None
+        saved = ctx.saved_tensors
+        x, weight = saved[:2]
+        dev = x.device
         if dy is None:                        # (only the alias was used downstream)
-            dy = torch.zeros(tuple(spec.out_shape) + (ceil4(spec.N),), dtype=torch.float32, device=ctx.saved_tensors[0].device)
-        x, weight, y, raw, mean, invstd, coef, psc, psh, raw_win, c4_bias = ctx.saved_tensors
-        ymask = None if psc is not None else y
-        ybits = ctx.ybits
+            dy = torch.zeros(tuple(spec.out_shape) + (ceil4(spec.N),), dtype=torch.float32, device=dev)
         has_bias, has_bn, has_res = ctx.has
         N, Np, M = spec.N, ceil4(spec.N), spec.M
-        dev = x.device
-        fused_pool = spec.pool and has_bn and spec.train and not has_res and Np == N
         if TRACE is not None:
             g0, m0 = spec.launches[0] if spec.launches else (None, M)
             TRACE.append(dict(M=M, N=N, C=spec.C, T=spec.T, mode=spec.mode, bn=has_bn, res=has_res, pool=spec.pool, act=spec.act,
                               nl=len(spec.launches), route=ops.gemm_route(spec.mode, spec.C, Np, ops.taps_of(spec.T, g0), g0, m0),
                               x_from=getattr(x, '_efgh_src', None), dx=bool(ctx.needs_input_grad[0]),
                               in_elems=int(x.numel()), custom=spec.custom_forward is not None))
-        if spec.pool and not fused_pool:    # pooled gradient -> full resolution (window recomputed from raw*scale+shift)
-            dy = ops.maxpool2_bwd_affine(raw, psc, psh, spec.act, spec.slope, dy.contiguous())
         dy = as_rows(dy)
-        dbias = dgamma = dbeta = dres = None
-        need_pre = spec.act != ACT_NONE or has_bn or has_res or has_bias
         p_w, p_bias, p_gamma, p_beta = ctx.params
         delivered = []
         # per-channel sums go straight into the flat gradient slices when the parameters live in a FlatParams (no padding)
@@ -363,79 +475,12 @@ class GemmLayerFn(torch.autograd.Function):
             gs1, d1 = claim_grad(p_bias)
             if gs1 is not None:
                 delivered.append(d1)
-        own_wgrad = ctx.needs_input_grad[1] and spec.custom_wgrad is None
-        pre_v = pre_gy = None
-        # the apply pass of the BatchNorm backward inside the gradient-side transforms of a 2-D Winograd layer (draw is never stored)
-        fuse_bwd = (ops.W2_BWD_FUSED and spec.bwd_fusable and has_bn and spec.train and Np == N
-                    and ctx.needs_input_grad[0] and own_wgrad and (ybits is not None or (psc is not None and not has_res))
-                    and len(spec.out_shape) == 3 and ((fused_pool and ops.W2_BWD_FUSED_POOL) or not spec.pool))
-        if fused_pool and ctx.c4:
-            # ... and without the raw map: the sums from the pooled tensors and raw_win, draw from the recomputed convolution
-            assert not fuse_bwd
-            c4 = ops.C4PoolLayer(x, ld_of(x), spec.layouts[0].pack(weight), Np, spec.launches[0][0], spec.launches[0][1], c4_bias)
-            draw, s1, s2 = ops.c4_pool_bn_bwd(c4, dy.contiguous(), y, raw_win, mean, invstd, coef, psc, psh, s1=gs1, s2=gs2)
-            if gs1 is None:
-                dbeta, dgamma = s1, s2
-            if has_bias:
-                dbias = _bias_grad_behind_bn(ctx, p_bias, draw, M, Np, N, True, delivered)
-        elif fused_pool:
-            # BatchNorm backward straight from the pooled gradient (no full-resolution dy is ever written)
-            draw, s1, s2 = ops.pool_bn_bwd(dy.contiguous(), raw, mean, invstd, coef, psc, psh, spec.act, spec.slope,
-                                           s1=gs1, s2=gs2, transforms=fuse_bwd, y_pool=y)
-            if fuse_bwd:
-                (pre_v, pre_gy), draw = draw, None
-            if gs1 is None:
-                dbeta, dgamma = s1, s2
-            if has_bias:
-                dbias = _bias_grad_behind_bn(ctx, p_bias, draw, M, Np, N, True, delivered)
-        elif not need_pre:
-            draw = dy
-        else:
-            G = ops.bwd_groups(M)
-            part = torch.empty((G, 2, Np), dtype=torch.float64, device=dev)      # float64 column sums (see backward.hip)
-            s1 = gs1 if gs1 is not None else torch.empty(Np, dtype=torch.float32, device=dev)
-            s2 = gs2 if gs2 is not None else torch.empty(Np, dtype=torch.float32, device=dev)
-            train_bn = has_bn and spec.train
-            m1 = torch.empty(Np, dtype=torch.float64, device=dev) if train_bn else None
-            m2 = torch.empty(Np, dtype=torch.float64, device=dev) if train_bn else None
-            ldy = Np if ymask is None else ld_of(ymask)
-            if ybits is not None:                     # (the mask as sign bits: `y` with ldy = 0, see efgh_act_bn_bwd_reduce)
-                ymask, ldy = ybits, 0
-            if sums is not None and train_bn:
-                # the kernel that produced dy took the two column sums in its epilogue: fold its per-block partials
-                f1, f2, m1, m2 = ops.bwd_finalize_f32(sums[0], Np, float(M))
-                if gs1 is not None:
-                    gs1.copy_(f1)
-                    gs2.copy_(f2)
-                s1, s2 = (gs1, gs2) if gs1 is not None else (f1, f2)
-            else:
-                ops.act_bn_bwd_reduce(dy, ld_of(dy), ymask, ldy, raw, Np, mean if has_bn else None,
-                                      invstd if has_bn else None, M, Np, spec.act, spec.slope, part, s1, s2, m1, m2,
-                                      pscale=psc, pshift=psh)
-            if has_bn and gs1 is None:
-                # (s1 / s2 are this backward's own tensors: handed to autograd as they are when there is no padding to cut off)
-                dbeta, dgamma = (s1, s2) if Np == N else (s1[:N].clone(), s2[:N].clone())
-            if has_bias and not has_bn and gs1 is None:
-                dbias = s1 if Np == N else s1[:N].clone()
-            if fuse_bwd:
-                Bo, Ho, Wo = spec.out_shape
-                pre_v, pre_gy, dres = ops.wino2d_bwd_transforms(dy, ld_of(dy), raw, Np, ybits, None if ybits is not None else psc,
-                                                                None if ybits is not None else psh, mean, invstd, coef, m1, m2, Np,
-                                                                Bo, Ho, Wo, spec.act, spec.slope, has_res)
-                draw = None
-            else:
-                draw = torch.empty(tuple(spec.out_shape) + (Np,), dtype=torch.float32, device=dev)
-                if has_res:
-                    dres = torch.empty(tuple(spec.out_shape) + (Np,), dtype=torch.float32, device=dev)
-                ops.act_bn_bwd_apply(dy, ld_of(dy), ymask, ldy, raw, Np, mean if train_bn else None,
-                                     invstd if train_bn else None, coef, m1, m2, M, Np, spec.act, spec.slope, draw, Np,
-                                     dres, Np, pscale=psc, pshift=psh)
-            if has_bias and has_bn:          # bias in front of BatchNorm: d/dbias = column sums of draw
-                dbias = _bias_grad_behind_bn(ctx, p_bias, draw, M, Np, N, train_bn, delivered)
+        draw, pre_v, pre_gy, dbeta, dgamma, dbias, dres = TAILS[ctx.tail][1](ctx, spec, dy, sums, saved, gs1, gs2, delivered)
         # ---- dgrad is on the critical path of backward and is enqueued first; the weight gradient only needs draw and x, and
         # nothing in this backward pass waits for it: when it can be written straight into the flat gradient buffer it goes to the
         # weight-gradient stream BEHIND this layer's dgrad, so that it runs underneath the HBM-bound BatchNorm passes of the next
         # layer instead of competing with the dgrad for the matrix pipes (measured: waiting only for draw costs 3 ms per step)
+        own_wgrad = ctx.needs_input_grad[1] and spec.custom_wgrad is None
         gW = dw_done = side = None
         if own_wgrad:
             gW, dw_done = claim_grad(p_w)
@@ -478,6 +523,9 @@ class GemmLayerFn(torch.autograd.Function):
                 side.wait_stream(torch.cuda.current_stream())
                 x.record_stream(side)
                 (draw if draw is not None else pre_gy).record_stream(side)
+                if lazy_w is not None:       # (read by efgh_wino2d_input_act on the side stream when the kept transform is missing)
+                    lazy_w.scale.record_stream(side)
+                    lazy_w.shift.record_stream(side)
                 with torch.cuda.stream(side):
                     run_wgrad()
             if gW is not None:

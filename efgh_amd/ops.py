@@ -1589,6 +1589,16 @@ def bwd_groups(M):
     return _L().efgh_bwd_groups(M)
 
 
+def bwd_sums(C, dev, s1=None, s2=None, means=True):
+    """the per-channel results of a BatchNorm / activation backward reduction -> (s1, s2, m1, m2): the two column sums (dbeta,
+    dgamma) - the caller's own, a flat gradient slice, or fresh - and, for train-mode statistics, their float64 means"""
+    s1 = s1 if s1 is not None else torch.empty(C, dtype=torch.float32, device=dev)
+    s2 = s2 if s2 is not None else torch.empty(C, dtype=torch.float32, device=dev)
+    m1 = torch.empty(C, dtype=torch.float64, device=dev) if means else None
+    m2 = torch.empty(C, dtype=torch.float64, device=dev) if means else None
+    return s1, s2, m1, m2
+
+
 def act_bn_bwd_reduce(dy, lddy, y, ldy, raw, ldraw, mean, invstd, M, C, act, slope, part, s1, s2, m1, m2,
                       pscale=None, pshift=None):
     _C.check(_L().efgh_act_bn_bwd_reduce(ptr(dy), lddy, ptr(y), ldy, ptr(raw), ldraw, ptr(mean), ptr(invstd), ptr(pscale),
@@ -1604,20 +1614,15 @@ def pool_bn_bwd(dy_pool, raw, mean, invstd, coef, pscale, pshift, act, slope, s1
     runs inside the layer's two gradient-side transforms (efgh_wino2d_bwd_transforms_pooled) -> ((Vd, Gy), dbeta, dgamma)"""
     B, H, W, C = raw.shape
     dev = raw.device
-    s1 = s1 if s1 is not None else torch.empty(C, dtype=torch.float32, device=dev)
-    s2 = s2 if s2 is not None else torch.empty(C, dtype=torch.float32, device=dev)
-    m1 = torch.empty(C, dtype=torch.float64, device=dev)
-    m2 = torch.empty(C, dtype=torch.float64, device=dev)
+    s1, s2, m1, m2 = bwd_sums(C, dev, s1, s2)
     if (POOL_REDUCE_FROM_Y and y_pool is not None and act == ACT_RELU and y_pool.is_contiguous()
             and tuple(y_pool.shape) == (B, H // 2, W // 2, C)):
         # (y_pool: the layer's own output - the next layer's backward keeps it alive; the full-resolution raw map is not read)
-        G = _L().efgh_bwd_groups(B * (H // 2) * (W // 2))
-        part = torch.empty((G, 2, C), dtype=torch.float64, device=dev)
+        part = torch.empty((_L().efgh_bwd_groups(B * (H // 2) * (W // 2)), 2, C), dtype=torch.float64, device=dev)
         _C.check(_L().efgh_pool_bn_bwd_reduce_pooled(ptr(dy_pool), ptr(y_pool), ptr(raw), ptr(mean), ptr(invstd), ptr(pscale),
                                                      ptr(pshift), B, H, W, C, ptr(part), ptr(s1), ptr(s2), ptr(m1), ptr(m2), _st()))
     else:
-        G = _L().efgh_pool_bwd_groups(B, H, W)
-        part = torch.empty((G, 2, C), dtype=torch.float64, device=dev)
+        part = torch.empty((_L().efgh_pool_bwd_groups(B, H, W), 2, C), dtype=torch.float64, device=dev)
         _C.check(_L().efgh_pool_bn_bwd_reduce(ptr(dy_pool), ptr(raw), ptr(mean), ptr(invstd), ptr(pscale), ptr(pshift), B, H, W, C,
                                               act, slope, ptr(part), ptr(s1), ptr(s2), ptr(m1), ptr(m2), _st()))
     if transforms:
@@ -1701,10 +1706,7 @@ def c4_pool_bn_bwd(layer, dy_pool, y_pool, raw_win, mean, invstd, coef, pscale, 
     -> (draw [B][Ho][Wo][N], dbeta [N], dgamma [N])"""
     B, H, W, C = layer.full_shape
     dev = dy_pool.device
-    s1 = s1 if s1 is not None else torch.empty(C, dtype=torch.float32, device=dev)
-    s2 = s2 if s2 is not None else torch.empty(C, dtype=torch.float32, device=dev)
-    m1 = torch.empty(C, dtype=torch.float64, device=dev)
-    m2 = torch.empty(C, dtype=torch.float64, device=dev)
+    s1, s2, m1, m2 = bwd_sums(C, dev, s1, s2)
     part = torch.empty((_L().efgh_bwd_groups(B * (H // 2) * (W // 2)), 2, C), dtype=torch.float64, device=dev)
     _C.check(_L().efgh_pool_bn_bwd_reduce_pooled_win(ptr(dy_pool), ptr(y_pool), ptr(raw_win), ptr(mean), ptr(invstd), ptr(pscale),
                                                      ptr(pshift), B, H, W, C, ptr(part), ptr(s1), ptr(s2), ptr(m1), ptr(m2), _st()))
