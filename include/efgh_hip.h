@@ -1107,6 +1107,35 @@ int efgh_sum_range_last(const float *pc, int64_t pc_cstride, int32_t N, const do
 int efgh_sum_paint(const void *jobs_dev, int32_t njobs, void *stream);
 int efgh_sum_colorize(const double *minmax, int64_t n, const uint8_t *lut, uint8_t *rgb, uint8_t *mask, void *stream);
 
+/* ---- fusing a registered LiDAR / camera pair (csrc/fuse.hip; tests/fuse_contract.py restates it in numpy) -------------------------
+ * Which pixel every point falls on, whether the camera sees it, and its colour.  Not in the reference; nothing runs unless called.
+ * pc: float32 (B, C >= 3, N), rows x y z, read through a batch and a channel stride in floats (a 4-row cloud is read in place);
+ * P: float64 [B][12], row-major 3x4 matrices that take a point to homogeneous PIXEL coordinates of an H x W image.
+ * Projection (float64, every operation rounded on its own): x = ((T0 px + T1 py) + T2 pz) + T3, y and w likewise; u = x / w,
+ * v = y / w; a point is IN FRONT iff w > min_depth and x, y, w are finite; IN FRAME iff also 0 <= u < W and 0 <= v < H, and then on
+ * pixel c = (int)u, r = (int)v (pixel centres at +0.5) with depth d = (float)w.
+ *   efgh_fuse_zbuffer  sets zbuf (efgh_fuse_workspace_bytes(B, H, W) = 8 B H W bytes, 8-byte aligned; -1 for sizes out of range) to
+ *     all ones, then takes the minimum of key = float_bits(d) << 32 | point index over every pixel of the point's (2 radius + 1)^2
+ *     window clipped to the image (radius 0 .. 8): the nearest point wins a pixel, the lowest index among equal float32 depths.
+ *     64-bit integer atomic minima only: the same bits on every schedule.
+ *   efgh_fuse_resolve  a SEPARATE launch behind it.  state u8 [B][N]: 0 not in front, 1 in front and out of frame, 2 in frame and
+ *     occluded, 3 visible, where visible iff (double)d <= (double)zmin (1 + rel_tol) + abs_tol with zmin the depth of the point's
+ *     pixel in zbuf (a point never hides itself; equal float32 depths are all visible).  rgb u8 [B][N][3]: zeros for state < 2, else
+ *     img[b][r][c] (img: uint8 [B][H][W][3]) or, with bilinear = 1, in float64: fx = u - 0.5, x0 = floor(fx), tx = fx - x0 (and in
+ *     y), x0, x0 + 1, y0, y0 + 1 clamped to the image, top = a + (b - a) tx, bot likewise, val = top + (bot - top) ty, (uint8)(int)
+ *     (val + 0.5).  uv f32 [B][N][2] (may be NULL, 8-byte aligned): (float)u, (float)v for state >= 1, NaN for state 0.
+ *   efgh_fuse_maps     zbuf as images over B * HW pixels: depth f32 (0 where empty, else the winner's float32 depth) and index i32
+ *     (-1 where empty, else the winner's point index); either may be NULL, not both.
+ * No host read, inputs never written.  EFGH_E_INVALID with a message, and nothing launched, for: a null pointer, B (<= 65535), N,
+ * H, W not positive, H W >= 2^31, radius outside 0 .. 8, min_depth / rel_tol / abs_tol negative or not finite, bilinear not 0 / 1. */
+int64_t efgh_fuse_workspace_bytes(int32_t B, int32_t H, int32_t W);
+int efgh_fuse_zbuffer(const float *pc, int64_t pc_bstride, int64_t pc_cstride, int32_t B, int32_t N, const double *P, int32_t H,
+                      int32_t W, int32_t radius, double min_depth, void *zbuf, void *stream);
+int efgh_fuse_resolve(const float *pc, int64_t pc_bstride, int64_t pc_cstride, int32_t B, int32_t N, const double *P,
+                      const uint8_t *img, int32_t H, int32_t W, int32_t bilinear, double min_depth, double rel_tol, double abs_tol,
+                      const void *zbuf, uint8_t *state, uint8_t *rgb, float *uv, void *stream);
+int efgh_fuse_maps(const void *zbuf, int32_t B, int64_t HW, float *depth, int32_t *index, void *stream);
+
 /* ---- pose heads, forward (one launch each) -----------------------------------------------------------------------------------
  * efgh_pose_head_normal: softmax + L2 normalisation of the nd (2 or 3) "abs" logits, sign class = first argmax of the 2^nd sign
  *   logits decoded MSB-first, normal = abs * sign, rotation of the normal onto (dx,dy,dz) as a 4x4 (enet.py:161-176, hnet.py:59-77,
