@@ -440,13 +440,15 @@ k_maxpool2_bwd(const float *__restrict__ x, const float *__restrict__ dy, float 
     // odd trailing rows / columns (floor pooling) receive no gradient: caller zero-fills dx when H or W is odd
 }
 
-// dx[argrow[s][c]][c] = dy[s][c], dx pre-zeroed
+// dx[argrow[s][c]][c] = dy[s][c], dx pre-zeroed; argrow < 0 (an empty segment) has no winner: nothing is written for it
 __global__ void k_segment_colmax_bwd(const float *__restrict__ dy, const int *__restrict__ argrow, int nseg, int C,
                                      float *__restrict__ dx, long long ld) {
     int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= nseg * C) return;
     int c = i % C;
-    dx[(long long)argrow[i] * ld + c] = dy[i];
+    const int r = argrow[i];
+    if (r < 0) return;
+    dx[(long long)r * ld + c] = dy[i];
 }
 
 // dx[s*P + r][c] = dy[s][c] / P

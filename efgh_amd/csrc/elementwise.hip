@@ -233,6 +233,20 @@ k_nhwc_to_nchw(const float *__restrict__ x, long long ld, float *__restrict__ y,
     }
 }
 
+// ---- the segment maximum, one rule for the three kernels below (torch.max on the CPU): a candidate is (value, row), row -1 = nothing
+// seen yet (value -inf).  The first strictly greatest row wins; a NaN beats every number and the first NaN row wins; a column of all
+// -inf keeps its first row; an empty segment stays (-inf, -1).
+// rows visited in ascending order: does v at the next row replace (m, am)?
+__device__ __forceinline__ bool seg_max_next(float v, float m, int am) { return am < 0 || v > m || (v != v && m == m); }
+// candidates in any order: does (v, r) beat (m, am)?
+__device__ __forceinline__ bool seg_max_beats(float v, int r, float m, int am) {
+    if (r < 0) return false;
+    if (am < 0) return true;
+    const bool vn = v != v, mn = m != m;
+    if (vn || mn) return vn && (!mn || r < am);
+    return v > m || (v == m && r < am);
+}
+
 // per-segment column max: x [M][ld], segment s = rows [seg[s], seg[s+1])  -> y[s][C]
 __global__ void __launch_bounds__(TPB)
 k_segment_colmax(const float *__restrict__ x, long long ld, int C, const int *__restrict__ seg,
@@ -240,8 +254,8 @@ k_segment_colmax(const float *__restrict__ x, long long ld, int C, const int *__
     int s = blockIdx.y, c = blockIdx.x * TPB + threadIdx.x;
     if (c >= C) return;
     int r0 = seg[s], r1 = seg[s + 1];
-    float m = -INFINITY; int am = r0;
-    for (int r = r0; r < r1; ++r) { float v = x[(long long)r * ld + c]; if (v > m) { m = v; am = r; } }
+    float m = -INFINITY; int am = -1;
+    for (int r = r0; r < r1; ++r) { float v = x[(long long)r * ld + c]; if (seg_max_next(v, m, am)) { m = v; am = r; } }
     y[(long long)s * C + c] = m;
     if (argrow) argrow[(long long)s * C + c] = am;
 }
@@ -276,17 +290,16 @@ k_segment_colmax_s1(const float *__restrict__ x, long long ld, int C, const int 
     const int c = blockIdx.x * CL + cl, s = blockIdx.y, k = blockIdx.z;
     const int r0 = seg[s], len = seg[s + 1] - r0;
     const int a = r0 + (int)((long long)len * k / RS), b = r0 + (int)((long long)len * (k + 1) / RS);
-    float m = -INFINITY; int am = a;
+    float m = -INFINITY; int am = -1;                // (a lane or a slice without rows stays neutral)
     if (c < C)
-        for (int r = a + rl; r < b; r += RL) { const float v = x[(long long)r * ld + c]; if (v > m) { m = v; am = r; } }
+        for (int r = a + rl; r < b; r += RL) { const float v = x[(long long)r * ld + c]; if (seg_max_next(v, m, am)) { m = v; am = r; } }
     sm[threadIdx.x] = m; sr[threadIdx.x] = am;
     __syncthreads();
     if (rl != 0 || c >= C) return;
-    for (int i = 1; i < RL; ++i) {                   // row lanes interleave the rows: a tie goes to the smaller row index
+    for (int i = 1; i < RL; ++i) {                   // row lanes interleave the rows: a tie (or a second NaN) goes to the smaller row index
         const float v = sm[i * CL + cl]; const int r = sr[i * CL + cl];
-        if (v > m || (v == m && r < am)) { m = v; am = r; }
+        if (seg_max_beats(v, r, m, am)) { m = v; am = r; }
     }
-    if (b <= a) { m = -INFINITY; am = a; }
     pmax[((long long)s * RS + k) * C + c] = m; prow[((long long)s * RS + k) * C + c] = am;
 }
 
@@ -295,10 +308,10 @@ k_segment_colmax_s2(const float *__restrict__ pmax, const int *__restrict__ prow
                     float *__restrict__ y, int *__restrict__ argrow) {
     const int s = blockIdx.y, c = blockIdx.x * TPB + threadIdx.x;
     if (c >= C) return;
-    float m = -INFINITY; int am = seg[s];
+    float m = -INFINITY; int am = -1;                // (an empty segment: every slice is neutral)
     for (int k = 0; k < RS; ++k) {
-        const float v = pmax[((long long)s * RS + k) * C + c];
-        if (v > m) { m = v; am = prow[((long long)s * RS + k) * C + c]; }
+        const float v = pmax[((long long)s * RS + k) * C + c]; const int r = prow[((long long)s * RS + k) * C + c];
+        if (seg_max_beats(v, r, m, am)) { m = v; am = r; }
     }
     y[(long long)s * C + c] = m;
     if (argrow) argrow[(long long)s * C + c] = am;

@@ -177,9 +177,12 @@ int efgh_lattice_part_neighbors(const void *workspace, const float *pts, int64_t
  * [emg[p] (4 channels; emg may be NULL: no such channels) | feat[p*ldf .. +Cf)]  ->
  * splat [H][C], C = (emg ? 4 : 0) + Cf  (row h = reference row h+1; the reference's all-zero row 0 is represented by
  * neighbour index -1), already multiplied by 1/(sum_bary + 1e-5) when `normalize` != 0 (args['bcn_use_norm'], bilateralNN.py:196-211;
- * 0: the plain sparse sum).  wsum [H] holds the density (kept for backward).
- * lanes_per_vertex: 64, 32 (two vertices per wave; needs C/4 <= 32) or 0 = chosen from avg_len (entries per vertex,
- * 4*n_in / H).  The mappings differ in the fp32 summation order only; a given mapping is bit-reproducible.                */
+ * 0: the plain sparse sum).  wsum [H] holds the density (kept for backward).  Every row h < H is written: a vertex with an
+ * empty list (vseg length 0) gets a row of exact zeros and wsum 0, with either value of `normalize`.
+ * lanes_per_vertex: 64, 32 (two vertices per wave; needs C/4 <= 32), 16 (four vertices per wave; needs C/4 <= 16) or
+ * 0 = chosen from avg_len (entries per vertex, 4*n_in / H): 32 when C/4 <= 32 and avg_len <= 32, else 64.  Any other value, or
+ * a row too wide for the mapping, is EFGH_E_ARG.  The mappings differ in the fp32 summation order only; a given mapping is
+ * bit-reproducible.  Cf: a multiple of 4 in [4, 508]; ldf: a multiple of 4.                                                 */
 int efgh_splat_gather(const float *emg, const float *feat, int64_t ldf, int32_t Cf, const float *bary,
                       const int32_t *list, const int32_t *vseg, int32_t H, int32_t avg_len, int32_t lanes_per_vertex,
                       int32_t normalize, float *splat, float *wsum, void *stream);
@@ -350,7 +353,12 @@ int efgh_maxpool_v2(const float *x, float *y, int32_t B, int32_t H, int32_t W, i
 /* model-boundary layout changes: (B,Cs,H,W) <-> [B][H][W][Cd] (extra channels zero) */
 int efgh_nchw_to_nhwc(const float *x, float *y, int32_t B, int32_t Cs, int64_t HW, int32_t Cd, void *stream);
 int efgh_nhwc_to_nchw(const float *x, int64_t ld, float *y, int32_t B, int32_t Cs, int64_t HW, void *stream);
-/* torch.max(x, 2) over ragged segments of rows (enet.py:154, hnet.py:53): y[s][c], argrow opt. */
+/* torch.max(x, 2) over ragged segments of rows (enet.py:154, hnet.py:53): segment s = rows [seg[s], seg[s+1]) of x [M][ld];
+ * y[s][c] and (argrow optional) the winning row, as an index into x.  The rules, the same in the one-stage and the two-stage form:
+ *   winner    the first strictly greatest row of the segment;
+ *   all -inf  a column of all -inf gives -inf and the segment's first row;
+ *   NaN       a NaN in the column gives NaN and the row of the first NaN (torch.max on the CPU);
+ *   empty     an empty segment gives y = -inf and argrow = -1 (no row); efgh_segment_colmax_bwd writes nothing for it. */
 int efgh_segment_colmax(const float *x, int64_t ld, int32_t C, const int32_t *seg, int32_t nseg,
                         float *y, int32_t *argrow, void *stream);
 /* torch.mean(x, 2) over equal segments (gnet.py:165) */
@@ -604,6 +612,8 @@ int efgh_pool_bn_bwd_reduce_pooled_win(const float *dy_pool, const float *y_pool
 int efgh_pool_bn_bwd_apply(const float *dy_pool, const float *raw, const float *mean, const float *invstd, const float *coef,
                            const double *m1, const double *m2, const float *pscale, const float *pshift, int32_t B, int32_t H,
                            int32_t W, int32_t C, int32_t act, float slope, float *draw, void *stream);
+/* dx[argrow[s][c]*ld + c] = dy[s][c]; every other element of dx is left as it is (the caller zero-fills), and so is all of dx for
+ * an argrow < 0 (the empty segment of efgh_segment_colmax) */
 int efgh_segment_colmax_bwd(const float *dy, const int32_t *argrow, int32_t nseg, int32_t C, float *dx,
                             int64_t ld, void *stream);
 int efgh_segment_colmean_bwd(const float *dy, int32_t P, int32_t nseg, int32_t C, float *dx, int64_t ld,

@@ -1030,6 +1030,9 @@ def test_two_stage_segment_reductions_equal_the_one_stage_kernels():
             # torch.max's index on ties is unspecified on CUDA: check ours is the first row that attains the maximum
             first = (x[a:b] == ref.values[None]).float().argmax(0) + a
             assert torch.equal(outs[True][1][s].long(), first)
+        else:                                        # an empty segment has no row: -inf and argrow -1, in both forms
+            for two in (True, False):
+                assert bool((outs[two][0][s] == float('-inf')).all()) and bool((outs[two][1][s] == -1).all()), (s, two)
     for C2, P, B in ((3, 7680, 4), (4, 30720, 1), (64, 1000, 8)):
         t = torch.randn(B * P, 4 if C2 < 4 else C2, device='cuda')
         ms = {}
