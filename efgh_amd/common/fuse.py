@@ -66,27 +66,66 @@ class Fused:
         return int(keep.sum())
 
 
-def _fail(what):
-    raise _C.EfghError('fuse: ' + what)
+def _fail(what, who='fuse'):
+    raise _C.EfghError(who + ': ' + what)
 
 
-def _image_u8(img, B):
-    """uint8 (B,H,W,3) of an image argument, without touching the argument"""
+def _cloud_dims(pc, who='fuse'):
+    """(B, N) of a cloud argument float32 (B, C >= 3, N)"""
+    if not torch.is_tensor(pc):
+        _fail('pc: expected a tensor, got %s' % type(pc).__name__, who)
+    if pc.dtype != torch.float32:
+        _fail('pc: dtype %s, expected float32' % pc.dtype, who)
+    if pc.dim() != 3 or pc.shape[1] < 3 or pc.shape[2] < 1 or pc.shape[0] < 1:
+        _fail('pc: expected (B, C >= 3, N >= 1), got %s' % (tuple(pc.shape),), who)
+    B, _, N = pc.shape
+    if B > 65535 or N >= 2 ** 31:
+        _fail('pc: B = %d (at most 65535) or N = %d (below 2^31) is too large' % (B, N), who)
+    return B, N
+
+
+def _image_u8(img, B, who='fuse'):
+    """an image argument in one of the accepted forms -> (img with a batch axis, H, W), without touching the argument"""
     if not torch.is_tensor(img):
-        _fail('img: expected a tensor, got %s' % type(img).__name__)
+        _fail('img: expected a tensor, got %s' % type(img).__name__, who)
     if img.dtype == torch.uint8:
         if img.dim() == 3:
             img = img[None]
         if img.dim() != 4 or img.shape[3] != 3:
-            _fail('img: a uint8 image is (B,H,W,3) or (H,W,3), got %s' % (tuple(img.shape),))
+            _fail('img: a uint8 image is (B,H,W,3) or (H,W,3), got %s' % (tuple(img.shape),), who)
     elif img.is_floating_point():
         if img.dim() != 4 or img.shape[1] != 3:
-            _fail('img: a float image is the model\'s (B,3,H,W) holding 0..255, got %s' % (tuple(img.shape),))
+            _fail('img: a float image is the model\'s (B,3,H,W) holding 0..255, got %s' % (tuple(img.shape),), who)
     else:
-        _fail('img: dtype %s, expected uint8 or a float type' % img.dtype)
+        _fail('img: dtype %s, expected uint8 or a float type' % img.dtype, who)
     if img.shape[0] != B:
-        _fail('img: batch size %d, the cloud has %d' % (img.shape[0], B))
-    return img
+        _fail('img: batch size %d, the cloud has %d' % (img.shape[0], B), who)
+    H, W = (img.shape[1], img.shape[2]) if img.dtype == torch.uint8 else (img.shape[2], img.shape[3])
+    if H < 1 or W < 1 or H * W >= 2 ** 31 - 1:
+        _fail('img: H = %d, W = %d: both positive and H*W < 2^31' % (H, W), who)
+    return img, H, W
+
+
+def _finite_nonneg(name, v, who='fuse'):
+    if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not 0.0 <= float(v) < float('inf'):
+        _fail('%s: %r, expected a finite number >= 0' % (name, v), who)
+
+
+def _on_the_clouds_device(pc, named, who='fuse', what='the fusion'):
+    """the last check: every tensor on the GPU, and on the cloud's"""
+    for name, t in (('pc', pc),) + tuple(named):
+        if not t.is_cuda:
+            _fail('%s: a CPU tensor; %s runs on the GPU through libefgh_hip.so only' % (name, what), who)
+        if t.device != pc.device:
+            _fail('%s: on %s, the cloud is on %s' % (name, t.device, pc.device), who)
+
+
+def _u8_hwc(img):
+    """contiguous uint8 (B,H,W,3) of a checked image; a float image as summary._u8_hwc converts it: truncation as astype('uint8')
+    for in-range values"""
+    if img.dtype != torch.uint8:
+        img = img.detach().to(torch.int64).to(torch.uint8).permute(0, 2, 3, 1)
+    return img.contiguous()
 
 
 def fuse(pc, img, cam_T_velo, radius=0, rel_tol=0.0, abs_tol=0.0, min_depth=0.0, bilinear=True, want=WANT):
@@ -102,15 +141,7 @@ def fuse(pc, img, cam_T_velo, radius=0, rel_tol=0.0, abs_tol=0.0, min_depth=0.0,
             _fail('want: %r is none of %s' % (k, ', '.join(WANT)))
     if not want:
         _fail('want: nothing asked for')
-    if not torch.is_tensor(pc):
-        _fail('pc: expected a tensor, got %s' % type(pc).__name__)
-    if pc.dtype != torch.float32:
-        _fail('pc: dtype %s, expected float32' % pc.dtype)
-    if pc.dim() != 3 or pc.shape[1] < 3 or pc.shape[2] < 1 or pc.shape[0] < 1:
-        _fail('pc: expected (B, C >= 3, N >= 1), got %s' % (tuple(pc.shape),))
-    B, _, N = pc.shape
-    if B > 65535 or N >= 2 ** 31:
-        _fail('pc: B = %d (at most 65535) or N = %d (below 2^31) is too large' % (B, N))
+    B, N = _cloud_dims(pc)
     T = cam_T_velo
     if not torch.is_tensor(T):
         _fail('cam_T_velo: expected a tensor or a dict, got %s' % type(T).__name__)
@@ -118,20 +149,12 @@ def fuse(pc, img, cam_T_velo, radius=0, rel_tol=0.0, abs_tol=0.0, min_depth=0.0,
         _fail('cam_T_velo: dtype %s, expected float32 or float64' % T.dtype)
     if tuple(T.shape) != (B, 3, 4):
         _fail('cam_T_velo: expected (%d, 3, 4), got %s' % (B, tuple(T.shape)))
-    img = _image_u8(img, B)
-    H, W = (img.shape[1], img.shape[2]) if img.dtype == torch.uint8 else (img.shape[2], img.shape[3])
-    if H < 1 or W < 1 or H * W >= 2 ** 31 - 1:
-        _fail('img: H = %d, W = %d: both positive and H*W < 2^31' % (H, W))
+    img, H, W = _image_u8(img, B)
     if isinstance(radius, bool) or not isinstance(radius, (int, np.integer)) or not 0 <= radius <= MAX_RADIUS:
         _fail('radius: %r, supported are the integers 0 .. %d' % (radius, MAX_RADIUS))
     for name, v in (('rel_tol', rel_tol), ('abs_tol', abs_tol), ('min_depth', min_depth)):
-        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not 0.0 <= float(v) < float('inf'):
-            _fail('%s: %r, expected a finite number >= 0' % (name, v))
-    for name, t in (('pc', pc), ('img', img), ('cam_T_velo', T)):
-        if not t.is_cuda:
-            _fail('%s: a CPU tensor; the fusion runs on the GPU through libefgh_hip.so only' % name)
-        if t.device != pc.device:
-            _fail('%s: on %s, the cloud is on %s' % (name, t.device, pc.device))
+        _finite_nonneg(name, v)
+    _on_the_clouds_device(pc, (('img', img), ('cam_T_velo', T)))
 
     dev = pc.device
     L, st = _C.lib(), _C.stream_ptr
@@ -144,9 +167,7 @@ def fuse(pc, img, cam_T_velo, radius=0, rel_tol=0.0, abs_tol=0.0, min_depth=0.0,
         _C.check(L.efgh_fuse_zbuffer(args[0], args[1], args[2], B, N, args[5], H, W, int(radius), float(min_depth), _C.ptr(zbuf), st()))
         out = {}
         if any(k in want for k in ('rgb', 'state', 'uv')):
-            if img.dtype != torch.uint8:                         # summary._u8_hwc: truncation as astype('uint8') for in-range values
-                img = img.detach().to(torch.int64).to(torch.uint8).permute(0, 2, 3, 1)
-            img = img.contiguous()
+            img = _u8_hwc(img)
             state = torch.empty((B, N), dtype=torch.uint8, device=dev)
             rgb = torch.empty((B, N, 3), dtype=torch.uint8, device=dev)
             uv = torch.empty((B, N, 2), dtype=torch.float32, device=dev) if 'uv' in want else None

@@ -6,9 +6,8 @@
 // The key order is the depth order (depths are positive floats) with the lower index winning a tie, and an integer minimum does not
 // depend on the order of its operands: the result is the same on every schedule.  The projection is float64 with every operation
 // written out (tests/fuse_contract.py restates it in numpy), and this file is built with -ffp-contract=off so that none of them is
-// fused: a multiply-add rounds once where the contract rounds twice.
-#include "common.h"
-#include <cmath>
+// fused: a multiply-add rounds once where the contract rounds twice.  The projection itself is in fuse_project.h.
+#include "fuse_project.h"               // Hit, ST_*, project: shared with score.hip
 
 namespace {
 constexpr int TPB = 256;
@@ -17,28 +16,6 @@ constexpr int MAX_RADIUS = 8;
 #ifndef EFGH_FUSE_PEEK
 #define EFGH_FUSE_PEEK 0
 #endif
-
-enum { ST_BEHIND = 0, ST_OUT = 1, ST_OCCLUDED = 2, ST_VISIBLE = 3 };
-
-struct Hit { double u, v; float d; int r, c, state; };          // state: ST_BEHIND, ST_OUT or ST_OCCLUDED (= in frame, not yet resolved)
-
-// THE projection: every kernel that needs a pixel calls this.  T = P[b], row-major 3x4
-__device__ __forceinline__ Hit project(const float *__restrict__ pc, long long cs, int i, const double *__restrict__ T, int H, int W,
-                                       double min_depth) {
-    const double px = (double)pc[i], py = (double)pc[cs + i], pz = (double)pc[2 * cs + i];
-    const double x = ((T[0] * px + T[1] * py) + T[2] * pz) + T[3];
-    const double y = ((T[4] * px + T[5] * py) + T[6] * pz) + T[7];
-    const double w = ((T[8] * px + T[9] * py) + T[10] * pz) + T[11];
-    const double inf = HUGE_VAL;
-    Hit h;
-    h.u = x / w; h.v = y / w; h.d = (float)w; h.r = 0; h.c = 0;
-    // positive comparisons: a NaN fails every one of them
-    if (!(w > min_depth && w < inf && fabs(x) < inf && fabs(y) < inf)) { h.state = ST_BEHIND; return h; }
-    if (!(h.u >= 0.0 && h.u < (double)W && h.v >= 0.0 && h.v < (double)H)) { h.state = ST_OUT; return h; }
-    h.c = (int)h.u; h.r = (int)h.v;
-    h.state = ST_OCCLUDED;
-    return h;
-}
 
 __global__ void __launch_bounds__(TPB)
 k_fuse_zbuffer(const float *__restrict__ pc, long long bs, long long cs, int N, const double *__restrict__ P, int H, int W, int radius,

@@ -1,0 +1,170 @@
+// Scoring candidate poses of a LiDAR / camera pair without ground truth ("Scoring poses"): the mutual information between
+// a per-point scalar (reflectance, a range) and the image grey level under the projected point, for K candidate matrices per sample
+// in one launch.  Two kernels:
+//   k_score_hist   grid (point chunk, k, b): the block's points through fuse_project.h's projection under candidate k, an in-frame
+//                  point adds 1 to cell (value bin, grey bin) of a bins x bins histogram in LDS (integer LDS atomics); the non-zero
+//                  cells then go to the global histogram with integer atomicAdd
+//   k_score_mi     one workgroup per (b, k): marginals, total, and in float64 the three sums of c log c through a fixed pairwise
+//                  tree of plain LDS stores; entropies, mi, nmi
+// Integer sums do not depend on their order, and the float64 tree has one shape and one order: the same bits on every schedule and
+// run.  There is no floating-point atomic.  No occlusion test: which points a nearer surface hides changes with the candidate, and
+// a z-buffer per candidate is not built.  Built with -ffp-contract=off for the projection and for the value bin, whose subtraction
+// and product round separately (tests/score_contract.py restates both in numpy).
+#include "fuse_project.h"
+
+namespace {
+constexpr int TPB = 256;
+constexpr int MAX_BINS = 64;
+constexpr int MAX_K = 4096;
+// points of one sample and candidate that one workgroup counts into its LDS histogram before it flushes (a multiple of TPB).  The
+// flush costs up to bins^2 global atomics a workgroup, the chunk is what it is spread over; profiles/score.txt has the measurement
+#ifndef EFGH_SCORE_CHUNK
+#define EFGH_SCORE_CHUNK 4096
+#endif
+static_assert(EFGH_SCORE_CHUNK % TPB == 0 && EFGH_SCORE_CHUNK > 0, "the chunk is whole passes of the block");
+
+// Pillow's L of an RGB pixel (jitter.hip's luma)
+__device__ __forceinline__ int luma(const uint8_t *p) { return (19595 * p[0] + 38470 * p[1] + 7471 * p[2] + 0x8000) >> 16; }
+
+__global__ void __launch_bounds__(TPB)
+k_score_hist(const float *__restrict__ pc, long long bs, long long cs, int N, const float *__restrict__ value, long long vbs,
+             const double *__restrict__ P, int K, const uint8_t *__restrict__ img, int H, int W, int bins, float lo, float scale,
+             double min_depth, unsigned *__restrict__ hist) {
+    __shared__ unsigned cnt[MAX_BINS * MAX_BINS];
+    const int k = blockIdx.y, b = blockIdx.z, nb = bins * bins;
+    for (int c = threadIdx.x; c < nb; c += TPB) cnt[c] = 0u;
+    __syncthreads();
+    const float *__restrict__ pcb = pc + b * bs;
+    const float *__restrict__ vb = value + b * vbs;
+    const double *__restrict__ T = P + 12 * ((long long)b * K + k);
+    const uint8_t *__restrict__ imgb = img + (long long)b * H * W * 3;
+    const float top = (float)(bins - 1);
+    const long long first = (long long)blockIdx.x * EFGH_SCORE_CHUNK;
+    const long long end = min(first + EFGH_SCORE_CHUNK, (long long)N);
+    for (long long j = first + threadIdx.x; j < end; j += TPB) {  // (64-bit: j + TPB may pass 2^31 in the last chunk of the largest N)
+        const int i = (int)j;
+        const float v = vb[i];
+        if (!(v == v)) continue;                                 // a NaN value drops the point
+        const Hit h = project(pcb, cs, i, T, H, W, min_depth);
+        if (h.state != ST_OCCLUDED) continue;                    // in frame; nothing here asks whether it is hidden
+        const float t = (v - lo) * scale;                        // two float32 operations
+        // clamped BEFORE the conversion: (int) of an infinity is undefined
+        const int x = t >= top ? bins - 1 : (t > 0.f ? (int)t : 0);
+        const int y = (luma(imgb + ((long long)h.r * W + h.c) * 3) * bins) >> 8;
+        atomicAdd(&cnt[x * bins + y], 1u);
+    }
+    __syncthreads();
+    unsigned *__restrict__ out = hist + ((long long)b * K + k) * nb;
+    for (int c = threadIdx.x; c < nb; c += TPB) {
+        const unsigned n = cnt[c];
+        if (n) atomicAdd(out + c, n);
+    }
+}
+
+// t[0 .. n) (n a power of two) summed in place, pairs a distance n/2, n/4, .. 1 apart: ONE shape and order whatever the block does
+__device__ __forceinline__ double tree_sum(double *t, int n) {
+    for (int s = n >> 1; s > 0; s >>= 1) {
+        __syncthreads();
+        for (int i = threadIdx.x; i < s; i += TPB) t[i] = t[i] + t[i + s];
+    }
+    __syncthreads();
+    const double r = t[0];
+    __syncthreads();
+    return r;
+}
+
+__device__ __forceinline__ double clogc(unsigned c) { return c ? (double)c * log((double)c) : 0.0; }
+
+__global__ void __launch_bounds__(TPB)
+k_score_mi(const unsigned *__restrict__ hist, int bins, double *__restrict__ score, int *__restrict__ count) {
+    __shared__ double t[MAX_BINS * MAX_BINS];
+    __shared__ unsigned row[MAX_BINS], col[MAX_BINS];
+    __shared__ unsigned total;
+    __shared__ int one[3];                                        // does ONE cell hold everything (joint, rows, columns)?
+    const int nb = bins * bins;
+    const unsigned *__restrict__ h = hist + (long long)blockIdx.x * nb;
+    if (threadIdx.x < MAX_BINS) row[threadIdx.x] = col[threadIdx.x] = 0u;
+    if (threadIdx.x < 3) one[threadIdx.x] = 0;
+    if (threadIdx.x == 0) total = 0u;
+    __syncthreads();
+    for (int c = threadIdx.x; c < nb; c += TPB) {
+        const unsigned n = h[c];
+        t[c] = clogc(n);
+        if (n) { atomicAdd(&row[c / bins], n); atomicAdd(&col[c % bins], n); atomicAdd(&total, n); }
+    }
+    __syncthreads();
+    const unsigned n = total;
+    for (int c = threadIdx.x; c < nb; c += TPB) if (n && h[c] == n) one[0] = 1;
+    const double sxy = tree_sum(t, nb);
+    if (threadIdx.x < bins) { t[threadIdx.x] = clogc(row[threadIdx.x]); if (n && row[threadIdx.x] == n) one[1] = 1; }
+    const double sx = tree_sum(t, bins);
+    if (threadIdx.x < bins) { t[threadIdx.x] = clogc(col[threadIdx.x]); if (n && col[threadIdx.x] == n) one[2] = 1; }
+    const double sy = tree_sum(t, bins);
+    if (threadIdx.x == 0) {
+        double *o = score + 5 * (long long)blockIdx.x;
+        double hx = 0.0, hy = 0.0, hxy = 0.0;
+        if (n) {
+            // a distribution on one cell has entropy 0 by definition: log n - (n log n) / n need not round to it
+            const double ln = log((double)n), dn = (double)n;
+            hx = one[1] ? 0.0 : ln - sx / dn;
+            hy = one[2] ? 0.0 : ln - sy / dn;
+            hxy = one[0] ? 0.0 : ln - sxy / dn;
+        }
+        const double sum = hx + hy;
+        o[0] = sum - hxy;
+        o[1] = hxy == 0.0 ? 0.0 : sum / hxy;
+        o[2] = hx; o[3] = hy; o[4] = hxy;
+        count[blockIdx.x] = (int)n;
+    }
+}
+
+#define SCORE_ARG(cond, ...)                                                         \
+    do {                                                                             \
+        if (!(cond)) {                                                               \
+            efgh_set_error(__VA_ARGS__);                                             \
+            return EFGH_E_INVALID;                                                   \
+        }                                                                            \
+    } while (0)
+
+bool bins_ok(int bins) { return bins == 8 || bins == 16 || bins == 32 || bins == 64; }
+}  // namespace
+
+extern "C" int32_t efgh_score_chunk(void) { return EFGH_SCORE_CHUNK; }
+
+extern "C" int efgh_score_hist(const float *pc, int64_t pc_bstride, int64_t pc_cstride, int32_t B, int32_t N, const float *value,
+                               int64_t value_bstride, const double *P, int32_t K, const uint8_t *img, int32_t H, int32_t W,
+                               int32_t bins, float lo, float hi, double min_depth, uint32_t *hist, void *stream) {
+    hipStream_t st = (hipStream_t)stream;
+    SCORE_ARG(pc && value && P && img && hist, "efgh_score_hist: null pointer (pc %p, value %p, P %p, img %p, hist %p)", (const void *)pc,
+              (const void *)value, (const void *)P, (const void *)img, (void *)hist);
+    SCORE_ARG(bins_ok(bins), "efgh_score_hist: bins = %d, supported are 8, 16, 32 and 64 (the counters live in LDS)", (int)bins);
+    SCORE_ARG(K > 0 && K <= MAX_K, "efgh_score_hist: K = %d candidates, supported are 1 .. %d", (int)K, MAX_K);
+    SCORE_ARG(B > 0 && B <= 65535, "efgh_score_hist: B = %d, supported are 1 .. 65535", (int)B);
+    SCORE_ARG(N > 0 && (int64_t)N < 0x7fffffffLL, "efgh_score_hist: N = %d must be positive and below 2^31", (int)N);
+    SCORE_ARG(H > 0 && W > 0 && (int64_t)H * W < 0x7fffffffLL, "efgh_score_hist: H = %d, W = %d: both positive and H*W < 2^31", (int)H, (int)W);
+    SCORE_ARG(min_depth >= 0.0 && std::isfinite(min_depth), "efgh_score_hist: min_depth = %g must be finite and >= 0", min_depth);
+    SCORE_ARG(std::isfinite(lo) && std::isfinite(hi) && lo < hi, "efgh_score_hist: value range lo = %g, hi = %g: finite and lo < hi",
+              (double)lo, (double)hi);
+    const float width = hi - lo;
+    const float scale = (float)bins / width;                    // formed once, here, in float32
+    SCORE_ARG(std::isfinite(width) && std::isfinite(scale) && scale > 0.f,
+              "efgh_score_hist: value range lo = %g, hi = %g: bins / (hi - lo) is not a finite float32", (double)lo, (double)hi);
+    if (hipMemsetAsync(hist, 0, (size_t)4 * B * K * bins * bins, st) != hipSuccess) {
+        efgh_set_error("efgh_score_hist: memset failed");
+        return EFGH_E_LAUNCH;
+    }
+    k_score_hist<<<dim3(cdiv(N, EFGH_SCORE_CHUNK), K, B), TPB, 0, st>>>(pc, pc_bstride, pc_cstride, N, value, value_bstride, P, K, img,
+                                                                        H, W, bins, lo, scale, min_depth, hist);
+    EFGH_CHECK_LAUNCH();
+    return EFGH_OK;
+}
+
+extern "C" int efgh_score_mi(const uint32_t *hist, int32_t B, int32_t K, int32_t bins, double *score, int32_t *count, void *stream) {
+    SCORE_ARG(hist && score && count, "efgh_score_mi: null pointer (hist %p, score %p, count %p)", (const void *)hist, (void *)score,
+              (void *)count);
+    SCORE_ARG(bins_ok(bins), "efgh_score_mi: bins = %d, supported are 8, 16, 32 and 64", (int)bins);
+    SCORE_ARG(K > 0 && K <= MAX_K && B > 0 && B <= 65535, "efgh_score_mi: B = %d (1 .. 65535), K = %d (1 .. %d)", (int)B, (int)K, MAX_K);
+    k_score_mi<<<B * K, TPB, 0, (hipStream_t)stream>>>(hist, bins, score, count);
+    EFGH_CHECK_LAUNCH();
+    return EFGH_OK;
+}

@@ -1146,6 +1146,32 @@ int efgh_fuse_resolve(const float *pc, int64_t pc_bstride, int64_t pc_cstride, i
                       const void *zbuf, uint8_t *state, uint8_t *rgb, float *uv, void *stream);
 int efgh_fuse_maps(const void *zbuf, int32_t B, int64_t HW, float *depth, int32_t *index, void *stream);
 
+/* ---- scoring candidate poses without ground truth (csrc/score.hip; tests/score_contract.py restates it in numpy) -------------------
+ * The mutual information between a per-point scalar (`value`: reflectance, a range) and the image grey level under the projected
+ * point (Pandey et al., "Automatic extrinsic calibration of vision and lidar by maximizing mutual information"), for K candidate
+ * matrices per sample at once.  Not in the reference; nothing runs unless called.  pc, H, W, min_depth and the projection are those of
+ * the fuse section above, P is float64 [B][K][12].  A point COUNTS iff it is in frame under its candidate and its value is not NaN.
+ * There is NO occlusion test: which points a nearer surface hides changes with the candidate, and no z-buffer per candidate is built.
+ *   efgh_score_hist   zeroes hist (uint32 [B][K][bins][bins]) on the stream, then counts every point into cell [x][y]:
+ *     y (grey):  L = (19595 R + 38470 G + 7471 B + 32768) >> 16 of pixel img[b][r][c] (nearest neighbour), y = (L * bins) >> 8;
+ *     x (value): t = (v - lo) * scale in float32, the subtraction and the product rounded separately, scale = (float)bins /
+ *                (hi - lo) formed once in float32; x = bins - 1 where t >= bins - 1, 0 where t <= 0, else (int)t (so +-inf clamp like
+ *                any value out of range; the clamp comes before the conversion).  value: float32 [B][N] with a batch stride in floats.
+ *     bins is 8, 16, 32 or 64 (the counters of a workgroup live in LDS: at most 16 KB); K <= 4096, B <= 65535, N < 2^31.  Integer
+ *     atomics only: the same counts on every schedule.  efgh_score_chunk(): the points a workgroup counts before it flushes.
+ *   efgh_score_mi     a SEPARATE launch behind it, one workgroup per (b, k).  count i32 [B][K]: n, the histogram's total.  score f64
+ *     [B][K][5] = (mi, nmi, Hx, Hy, Hxy) in nats: with S = sum c log c over the non-zero cells (rows, columns, joint; float64, a
+ *     fixed pairwise tree of plain stores: the same bits run to run), H = log n - S / n, and H = 0 exactly where one cell holds all
+ *     n; mi = (Hx + Hy) - Hxy, nmi = (Hx + Hy) / Hxy.  n == 0: all five are 0; Hxy == 0: nmi = 0.  Never NaN.
+ * No host read, inputs never written.  EFGH_E_INVALID with a message naming the value, and nothing launched, for: a null pointer,
+ * bins not one of the four, K, B, N, H, W out of range, min_depth negative or not finite, lo / hi not finite or lo >= hi.
+ * MI of a sparse histogram is biased upwards when n is small: candidates with very different counts are not comparable as they are. */
+int32_t efgh_score_chunk(void);
+int efgh_score_hist(const float *pc, int64_t pc_bstride, int64_t pc_cstride, int32_t B, int32_t N, const float *value,
+                    int64_t value_bstride, const double *P, int32_t K, const uint8_t *img, int32_t H, int32_t W, int32_t bins,
+                    float lo, float hi, double min_depth, uint32_t *hist, void *stream);
+int efgh_score_mi(const uint32_t *hist, int32_t B, int32_t K, int32_t bins, double *score, int32_t *count, void *stream);
+
 /* ---- pose heads, forward (one launch each) -----------------------------------------------------------------------------------
  * efgh_pose_head_normal: softmax + L2 normalisation of the nd (2 or 3) "abs" logits, sign class = first argmax of the 2^nd sign
  *   logits decoded MSB-first, normal = abs * sign, rotation of the normal onto (dx,dy,dz) as a 4x4 (enet.py:161-176, hnet.py:59-77,
