@@ -94,8 +94,6 @@ class EFGHBackbone(nn.Module):
         for holder in self._epoch_holders():
             ops.repack_stale(pc.device, holder)
         ops.TLS.train_step = bool(self.training and torch.is_grad_enabled())   # (GemmLayerFn carries it over to its backward)
-        if self.training:
-            ops.w2v_clear()
         shared_img = ops.nchw_to_nhwc(img, 4)                # channels-last copy used by both H and G
         g_pre = None
         s_h = None

@@ -72,12 +72,15 @@ class LayerSpec:
         return self
 
 
-def run_launches(spec, x, lda, weight, out, ldo, bias, want_stats, a_off=0, out_off=0, lazy=None, pool=False, w2v=None, **epilogue):
+def run_launches(spec, x, lda, weight, out, ldo, bias, want_stats, a_off=0, out_off=0, lazy=None, pool=False, keep_on=None, **epilogue):
     """the launch stage of both paths: pack each launch's weight and run the launches of `spec` (or its custom_forward) into `out`.
     want_stats: train-mode BatchNorm follows - the per-column statistics [G][2][Np] are returned, taken in the launches' epilogues or,
     for the kernels without one (ops.no_stats_epilogue) and for a custom_forward, by one ops.col_stats pass over the output;
     the caller then passes no `epilogue` (scale / shift / residual / act: the raw output is wanted).
-    w2v: tape path only - TLS.w2v_wanted around the launches"""
+    keep_on: tape path only - the layer's node, when its own weight gradient will be asked for: a 2-D Winograd launch whose weight
+    gradient runs on that path too leaves B^T x B of its input there (ops.gather_gemm keep_v=), as keep_on.kept_v[launch index] - a
+    plain attribute (x itself is among the saved tensors, which catch an in-place edit of it) that lives as long as the layer's graph
+    does and that GemmLayerFn._backward takes"""
     Np = ceil4(spec.N)
     wps = [lay.pack(weight) for lay in spec.layouts]
     custom = spec.custom_forward
@@ -89,8 +92,6 @@ def run_launches(spec, x, lda, weight, out, ldo, bias, want_stats, a_off=0, out_
             stats = torch.empty((sum(gs), 2, Np), dtype=torch.float32, device=x.device)
     if custom is not None:
         custom(x, weight, out)
-    if w2v is not None:
-        ops.TLS.w2v_wanted = w2v
     g0 = 0
     for li, (geom, m) in enumerate(spec.launches if custom is None else ()):
         T = ops.taps_of(spec.T, geom)
@@ -98,10 +99,14 @@ def run_launches(spec, x, lda, weight, out, ldo, bias, want_stats, a_off=0, out_
         if stats is not None:
             st = stats[g0:g0 + gs[li]]
             g0 += gs[li]
+        slot = None if keep_on is None else []
         ops.gather_gemm(x, lda, spec.C, T, wps[li], Np, m, out, ldo, mode=spec.mode, geom=geom, table=spec.table, bias=bias, stats=st,
-                        a_off=a_off, out_off=out_off, flops=2.0 * m * spec.N * T * spec.c_real, lazy=lazy, pool=pool, **epilogue)
-    if w2v is not None:
-        ops.TLS.w2v_wanted = False
+                        a_off=a_off, out_off=out_off, flops=2.0 * m * spec.N * T * spec.c_real, lazy=lazy, pool=pool, keep_v=slot,
+                        **epilogue)
+        if slot and ops.wgrad_route(spec.mode, spec.C, Np, T, geom) == 'wino2d':      # (else nobody will ask for it: freed here)
+            if keep_on.kept_v is None:
+                keep_on.kept_v = {}
+            keep_on.kept_v[li] = slot[0]
     if thin:
         stats, _ = ops.col_stats(out, spec.M, Np, ldo, x_off=out_off)
     return stats
@@ -215,9 +220,11 @@ def _choose_tail(spec, x, weight, b, lazy, res, needs_grad):
 
 def _fuse_bwd(ctx, spec):
     """may the apply pass of the BatchNorm backward run inside the gradient-side transforms of a 2-D Winograd layer (draw is never
-    stored)?"""
+    stored)?  (spec.bwd_fusable is the forward's answer; the weight gradient's route is asked again here: with a switch flipped between
+    forward and backward the layer takes the two-pass form instead of handing pre_gy to a kernel that cannot take it)"""
     return (ops.W2_BWD_FUSED and spec.bwd_fusable and ctx.train_bn and ceil4(spec.N) == spec.N and ctx.needs_input_grad[0]
-            and ctx.needs_input_grad[1] and spec.custom_wgrad is None and ctx.mask != 'y' and len(spec.out_shape) == 3)
+            and ctx.needs_input_grad[1] and spec.custom_wgrad is None and ctx.mask != 'y' and len(spec.out_shape) == 3
+            and ops.wgrad_lazy_capable(spec.mode, spec.C, spec.N, spec.launches[0][0]))
 
 
 def _reduce_apply(ctx, spec, dy, sums, raw, mean, invstd, scale, shift, mask, gs1, gs2, fuse_bwd, delivered):
@@ -262,11 +269,16 @@ def _pooled_sums(ctx, spec, draw, s1, s2, gs1, delivered):
     return (s1, s2, dbias, None) if gs1 is None else (None, None, dbias, None)
 
 
+def _own_wgrad(ctx, spec):
+    """ctx when this layer's weight gradient will be asked for and is the layer's own (run_launches keep_on=), else None"""
+    return ctx if (ctx.needs_input_grad[1] and spec.custom_wgrad is None) else None
+
+
 def _plain_fwd(ctx, spec, x, weight, b, gamma, beta, res, lazy, out_target):
     """bias (+ residual) (+ activation) straight in the GEMM epilogue"""
     Np = ceil4(spec.N)
     y = torch.empty(tuple(spec.out_shape) + (Np,), dtype=torch.float32, device=x.device)
-    run_launches(spec, x, ld_of(x), weight, y, Np, b, False, lazy=lazy, w2v=bool(ctx.needs_input_grad[1]), residual=res,
+    run_launches(spec, x, ld_of(x), weight, y, Np, b, False, lazy=lazy, keep_on=_own_wgrad(ctx, spec), residual=res,
                  ldr=0 if res is None else ld_of(res), act=spec.act, slope=spec.slope)
     ctx.mask = 'y'
     return y, (y,)
@@ -284,7 +296,7 @@ def _bn_raw(ctx, spec, x, weight, b, gamma, beta, lazy):
     taken with it in train mode, from the running ones otherwise"""
     bn, Np = spec.bn, ceil4(spec.N)
     raw = torch.empty(tuple(spec.out_shape) + (Np,), dtype=torch.float32, device=x.device)
-    stats = run_launches(spec, x, ld_of(x), weight, raw, Np, b, spec.train, lazy=lazy, w2v=bool(ctx.needs_input_grad[1]))
+    stats = run_launches(spec, x, ld_of(x), weight, raw, Np, b, spec.train, lazy=lazy, keep_on=_own_wgrad(ctx, spec))
     if spec.train:
         return (raw,) + tuple(bn_batch_stats(bn, stats, Np, float(spec.M), save=True))
     with torch.no_grad():
@@ -417,6 +429,7 @@ class GemmLayerFn(torch.autograd.Function):
         assert spec.custom_forward is None or (spec.bn is not None and bias is None)
         ctx.train_bn = spec.bn is not None and spec.train
         ctx.bnsrc = None                      # (the `bn` tail tags what it returns with its BnSrc, `_efgh_bnsrc`)
+        ctx.kept_v = None                     # ({launch index: B^T x B of x}, left by run_launches(keep_on=ctx))
         ctx.tail = _choose_tail(spec, x, weight, b, lazy, res, any(ctx.needs_input_grad))
         y, saved = TAILS[ctx.tail][0](ctx, spec, x, weight, b, gamma, beta, res, lazy, out_target)
         if TRACE is not None:
@@ -506,15 +519,22 @@ class GemmLayerFn(torch.autograd.Function):
             if lazy_w is not None and not ops.wgrad_lazy_capable(spec.mode, spec.C, Np, spec.launches[0][0]):
                 xw, lazy_w = materialize(x, lazy_w), None      # (a switch flipped between forward and backward: never wrong, only slower)
 
+            # the forward's input transforms are taken off the node: freed when the weight gradient has been enqueued, and a second
+            # backward over a retained graph transforms again
+            kept, ctx.kept_v = ctx.kept_v, None
+
             def run_wgrad():
                 x = xw
-                for (geom, m), lay in zip(spec.launches, spec.layouts):
+                for li, ((geom, m), lay) in enumerate(zip(spec.launches, spec.layouts)):
                     T = ops.taps_of(spec.T, geom)
+                    xv = kept.pop(li, None) if kept else None
+                    if xv is not None and ops.wgrad_route(spec.mode, spec.C, Np, T, geom) != 'wino2d':
+                        xv = None            # (a switch flipped between forward and backward: dropped, like the fallback above)
                     dWp = torch.empty((Np, T, spec.C), dtype=torch.float32, device=dev)
                     ua = lay.fold_args()            # (ops.gather_wgrad(unpack=...): fold + unpack in one launch)
                     done = ops.gather_wgrad(x, ld_of(x), spec.C, T, Np, m, draw, Np, dWp, mode=spec.mode, geom=geom,
                                             table=spec.table, unpack=None if ua is None else (dW,) + ua,
-                                            lazy=lazy_w, pre_gy=pre_gy)
+                                            lazy=lazy_w, pre_gy=pre_gy, pre_v=xv)
                     if not done:             # (a single row chunk, or a path with a transform behind its fold)
                         lay.unpack(dWp, dW)
             if side is None:
@@ -523,6 +543,8 @@ class GemmLayerFn(torch.autograd.Function):
                 side.wait_stream(torch.cuda.current_stream())
                 x.record_stream(side)
                 (draw if draw is not None else pre_gy).record_stream(side)
+                for v in kept.values() if kept else ():      # (made on the forward's stream)
+                    v.record_stream(side)
                 if lazy_w is not None:       # (read by efgh_wino2d_input_act on the side stream when the kept transform is missing)
                     lazy_w.scale.record_stream(side)
                     lazy_w.shift.record_stream(side)

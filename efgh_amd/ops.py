@@ -71,14 +71,13 @@ class _ThreadState(threading.local):
     """per-thread switches (two Python threads may drive two models on one GPU; autograd's device thread is a third):
     train_step - inside a training step (forward: set by EFGHBackbone.forward; backward: GemmLayerFn.backward restores the value
     its forward saw); planes_split - the plane-GEMM precision of the layer being run (GemmLayerFn: resolved once in its forward,
-    restored in its backward); w2v_wanted - set by GemmLayerFn.forward around its launches when the weight gradient will be asked for;
+    restored in its backward);
     depth_weight - the g_depth weight of the micro-batch whose loss is being computed (Trainer.step_accumulated hands it to
     EFGHCriterion._dp_weight_masked_mean: a one-element device tensor, or the float 1.0 for "no weight"; None: nothing handed over)"""
 
     def __init__(self):
         self.depth_weight = None
         self.train_step = False
-        self.w2v_wanted = False
         self.nbt_pending = None        # see bn_tick
         self.planes_split = None       # see planes_split_active: the mode GemmLayerFn resolved for this layer (None: outside a layer)
 
@@ -662,7 +661,8 @@ def _blur_gemm_ksplit(A, lda, C, Wp, N, M, out, ldo, table, bias, act, slope, a_
 
 def gather_gemm(A, lda, C, T, Wp, N, M, out, ldo, mode=0, geom=None, table=None, bias=None, scale=None,
                 shift=None, residual=None, ldr=0, act=ACT_NONE, slope=0.0, stats=None, a_off=0, out_off=0,
-                res_off=0, M_dev=None, flops=None, batch=None, alias_mask=False, bn_bwd=None, pool=False, lazy=None, pre_v=None):
+                res_off=0, M_dev=None, flops=None, batch=None, alias_mask=False, bn_bwd=None, pool=False, lazy=None, pre_v=None,
+                keep_v=None):
     """See efgh_gemm_desc.  A/out/residual may be addressed with an element offset (channel slices).
     pool: `out` is the 2x2 max-pooled map [B][Ho/2][Wo/2][ldo] (only for launches pool_fusable() accepts: the 2-D Winograd path).
     bn_bwd: a BnSrc (nets/fn.py) - the BatchNorm layer that produced the tensor whose GRADIENT this launch writes; when the
@@ -670,7 +670,9 @@ def gather_gemm(A, lda, C, T, Wp, N, M, out, ldo, mode=0, geom=None, table=None,
     epilogue and the [rows][2][N] partials are RETURNED (else None: the layer runs its own reduction pass).
     lazy: a LazyAct - A is the RAW output of a train-mode BatchNorm layer and act(A*scale + shift) is applied by the consumer (only the
     2-D Winograd input transform can: the caller asks lazy_capable() first).  pre_v: the input transform of the launch, already
-    made (wino2d_bwd_transforms: the data gradient of a layer whose draw is never stored); A may then be None."""
+    made (wino2d_bwd_transforms: the data gradient of a layer whose draw is never stored); A may then be None.
+    keep_v: a list - a 2-D Winograd launch that makes its input transform appends it (under W2V_KEEP: the caller hands it to the
+    layer's weight gradient, gather_wgrad(pre_v=)); any other launch leaves the list as it is."""
     key = (mode, C, N, T, geom, M, stats is not None, M_dev is not None, batch is not None, pool,
            scale is None and shift is None and residual is None and (bias is None or bias.numel() == N))
     route = gemm_route(*key)
@@ -709,7 +711,7 @@ def gather_gemm(A, lda, C, T, Wp, N, M, out, ldo, mode=0, geom=None, table=None,
             # layer's reduction pass (a read of dy and of raw) is not run
             rows = _L().efgh_wino2d_stats_rows(geom[0], geom[1], geom[2], N)
             bn_stats = _bn_bwd_sums(d, bn_bwd, rows, N, out.device)
-        _wino2d_forward(d, A, a_off, lda, C, N, geom, Wp, pool=pool, lazy=lazy, pre_v=pre_v)
+        _wino2d_forward(d, A, a_off, lda, C, N, geom, Wp, pool=pool, lazy=lazy, pre_v=pre_v, keep_v=keep_v)
     elif route == 'wino_hpool':
         _C.check(_L().efgh_wino_conv3x3_hpool(ctypes.byref(d), ptr(wino_weight(Wp, N, C)), _st()))
     elif route == 'wino':
@@ -787,19 +789,7 @@ def _batched_plain_gemm(A3, W3, out3, rows, C, N):
     _prof_end(ev, 'planes', (0, rows, N, 36, C), 2.0 * 36 * rows * C * N, PROFILE_WINO2D_GEMM)
 
 
-W2V_CACHE = {}          # training: B^T x B of a layer's input, kept from the forward for the layer's weight gradient
-W2V_KEEP = True
-
-
-def w2v_clear():
-    """drop the transformed inputs of THIS thread's forwards that no backward came for (nets.EFGHBackbone.forward calls this at
-    the start of every train-mode forward, train.Trainer at the start of every step: an entry never outlives the step that made
-    it, whatever loop drives it).  Entries are tagged with the thread that made them - the backward that pops them runs on
-    autograd's device thread - so two threads driving two models do not drop each other's."""
-    me = threading.get_ident()
-    with _LOCK:
-        for k in [k for k, v in W2V_CACHE.items() if v[2] == me]:
-            del W2V_CACHE[k]
+W2V_KEEP = True         # training: B^T x B of a layer's input goes from the forward to the layer's weight gradient (gather_gemm keep_v=)
 
 
 POOL_FUSED = True               # inference: MaxPool2d(2,2) folded into the producing layer (4-channel input layers, 2-D Winograd output transform)
@@ -865,29 +855,62 @@ def wino2d_bwd_transforms(dy, lddy, raw, ldraw, ybits, psc, psh, mean, invstd, c
     return Vd, Gy, dres
 
 
-def _wino2d_forward(d, A, a_off, lda, C, N, geom, Wp, pool=False, lazy=None, pre_v=None):
+def _wino2d_v(pre_v, A, a_off, lda, C, B, H, W, T, lazy, dev):
+    """B^T x B of a 2-D Winograd launch's input [T][36][C]: the one given (pre_v), or made here - from A, or from act(A*scale + shift)
+    when A carries a pending activation (lazy)"""
+    if pre_v is not None:
+        assert tuple(pre_v.shape) == (T, 36, C)
+        return pre_v
+    V = torch.empty((T, 36, C), dtype=torch.float32, device=dev)
+    wino2d_input(A, a_off, lda, C, B, H, W, V, lazy)
+    return V
+
+
+def _wino2d_forward(d, A, a_off, lda, C, N, geom, Wp, pool=False, lazy=None, pre_v=None, keep_v=None):
     """input transform -> 36 batched GEMMs -> output transform with the layer's epilogue (descriptor d)"""
     B, H, W = geom[0], geom[1], geom[2]
     T = _L().efgh_wino2d_tiles(B, H, W)
     dev = A.device if A is not None else pre_v.device
     Mb = torch.empty((T, 36, N), dtype=torch.float32, device=dev)
-    if pre_v is not None:
-        assert tuple(pre_v.shape) == (T, 36, C)
-        V = pre_v
-    else:
-        V = torch.empty((T, 36, C), dtype=torch.float32, device=dev)
-        wino2d_input(A, a_off, lda, C, B, H, W, V, lazy)
-    if pre_v is None and W2V_KEEP and TLS.w2v_wanted and a_off == 0:
+    V = _wino2d_v(pre_v, A, a_off, lda, C, B, H, W, T, lazy, dev)
+    if keep_v is not None and pre_v is None and W2V_KEEP:
         # 2.25x the activation, ~10 GB over the eligible layers at batch 8 (of 288 GB): saves one transform pass per layer and step
-        with _LOCK:
-            if len(W2V_CACHE) > 512:
-                W2V_CACHE.clear()
-            W2V_CACHE[(A.data_ptr(), lda, C, B, H, W)] = (V, A._version, threading.get_ident())
+        keep_v.append(V)
     _batched_plain_gemm(V, wino2d_weight(Wp, N, C), Mb, T, C, N)
     if pool:
         _C.check(_L().efgh_wino2d_output_pooled(ptr(Mb), ctypes.byref(d), _st()))
     else:
         _C.check(_L().efgh_wino2d_output(ptr(Mb), ctypes.byref(d), _st()))
+
+
+def _wino2d_wgrad(A, lda, C, N, geom, G, ldg, dWp, odp, lazy=None, pre_v=None, pre_gy=None):
+    """input transform and gradient-side transform (each unless given) -> 36 batched weight-gradient GEMMs -> finish kernel, which
+    leaves the packed gradient in dWp or, with an efgh_wgrad_out_desc (odp), the reference layout -> True when it did the latter"""
+    B, H, W = geom[0], geom[1], geom[2]
+    T2 = _L().efgh_wino2d_tiles(B, H, W)
+    dev = dWp.device
+    S = torch.empty((36, N, C), dtype=torch.float32, device=dev)
+    V = _wino2d_v(pre_v, A, 0, lda, C, B, H, W, T2, lazy, dev)
+    if pre_gy is not None:
+        assert tuple(pre_gy.shape) == (T2, 36, N)
+        Gy = pre_gy
+    else:
+        Gy = torch.empty((T2, 36, N), dtype=torch.float32, device=dev)
+        _C.check(_L().efgh_wino2d_dy(ptr(G), ldg, N, B, H, W, ptr(Gy), _st()))
+    g = _desc(V, 36 * C, C, 1, 0, N, T2, batch=(36, C, 0, 0))
+    pv = _prof_start(PROFILE_WINO2D_GEMM)
+    if PLANE_DMA and _L().efgh_plane_wgrad_supported(ctypes.byref(g), 36 * N):
+        split = _planes_split_now()
+        if split:
+            PLANE_SPLIT_HITS[1] += 1
+        _C.check((_L().efgh_plane_wgrad_x6_batched if split else _L().efgh_plane_wgrad_batched)(
+            ctypes.byref(g), ptr(Gy), 36 * N, N, ptr(S), N * C,
+            ptr(_scratch(_L().efgh_plane_wgrad_workspace(ctypes.byref(g)), dev)), PLANE_DMA_NBUF, _st()))
+    else:
+        _C.check(_L().efgh_gather_wgrad_batched(ctypes.byref(g), ptr(Gy), 36 * N, N, ptr(S), N * C,
+                                                ptr(_scratch(_L().efgh_gather_wgrad_workspace(ctypes.byref(g)), dev)), _st()))
+    _prof_end(pv, 'planes', (0, T2, N, 36, C), 2.0 * 36 * T2 * C * N, PROFILE_WINO2D_GEMM)
+    return _C.check_wrote(_L().efgh_wino2d_wfinish(ptr(S), ptr(dWp), N, C, odp, _st()))      # (only the finish kernel may write the reference layout)
 
 
 # ----------------------------------------------------------------------------------------------
@@ -1499,15 +1522,19 @@ def _wgrad_aligned(route, d, lda, ldg, G, dWp):
     return lda % 4 == 0 and ldg % 4 == 0 and d.A % 16 == 0 and G.data_ptr() % 16 == 0
 
 
-def gather_wgrad(A, lda, C, T, N, M, G, ldg, dWp, mode=0, geom=None, table=None, unpack=None, lazy=None, pre_gy=None):
+def gather_wgrad(A, lda, C, T, N, M, G, ldg, dWp, mode=0, geom=None, table=None, unpack=None, lazy=None, pre_gy=None, pre_v=None):
     """unpack: (dW, N_real, T, C_real, Cp, sn, sc, st, taps, accumulate) - where the gradient belongs in the reference layout
     (ops.unpack_weight's arguments).  -> True when the launch left it there itself (its final fold did the unpack: dWp is then
     NOT written), False when dWp holds the packed gradient and the caller has to unpack it (always so for mode MODE_BLUR_R).
-    lazy: A is a raw BatchNorm output with a pending activation (LazyAct; 2-D Winograd path only: the kept forward transform already has
-    it applied, a re-transform applies it again).  pre_gy: the gradient-side transform, already made (wino2d_bwd_transforms); G may be None"""
+    lazy: A is a raw BatchNorm output with a pending activation (LazyAct; 2-D Winograd path only).  pre_gy: the gradient-side
+    transform, already made (wino2d_bwd_transforms); G may be None.  pre_v: the input transform of A, already made (the forward's,
+    gather_gemm(keep_v=): it has a pending activation applied; without it A is transformed here, `lazy` applied); only for a launch
+    whose wgrad_route is 'wino2d'"""
     route = wgrad_route(mode, C, N, T, geom)
     if (lazy is not None or pre_gy is not None) and not (route == 'wino2d' and min(C, N) >= 64):
         raise _C.EfghError('gather_wgrad(lazy= / pre_gy=) on a launch the 2-D Winograd weight gradient does not serve')
+    if pre_v is not None and route != 'wino2d':
+        raise _C.EfghError('gather_wgrad(pre_v=) on a launch the 2-D Winograd weight gradient does not serve')
     if route == 'blur_r':
         blur_r_wgrad(A, lda, C, T, N, M, G, ldg, dWp, table)
         return False
@@ -1528,39 +1555,7 @@ def gather_wgrad(A, lda, C, T, N, M, G, ldg, dWp, mode=0, geom=None, table=None,
     # partial planes that are folded in a fixed order: all 353 gradients of a training step are bit-reproducible run to run by
     # default, and EFGH_DETERMINISTIC has nothing left to switch)
     if route == 'wino2d':
-        B, H, W = geom[0], geom[1], geom[2]
-        T2 = _L().efgh_wino2d_tiles(B, H, W)
-        dev = dWp.device
-        with _LOCK:
-            kept = W2V_CACHE.pop((A.data_ptr(), lda, C, B, H, W), None)
-        if kept is not None:
-            kept[0].record_stream(torch.cuda.current_stream())          # (made on the forward's stream, maybe read on another)
-        S = torch.empty((36, N, C), dtype=torch.float32, device=dev)
-        if kept is not None and kept[1] == A._version and kept[0].shape == (T2, 36, C):
-            V = kept[0]                                                            # B^T x B from the forward pass
-        else:
-            V = torch.empty((T2, 36, C), dtype=torch.float32, device=dev)
-            wino2d_input(A, 0, lda, C, B, H, W, V, lazy)
-        if pre_gy is not None:
-            assert tuple(pre_gy.shape) == (T2, 36, N)
-            Gy = pre_gy
-        else:
-            Gy = torch.empty((T2, 36, N), dtype=torch.float32, device=dev)
-            _C.check(_L().efgh_wino2d_dy(ptr(G), ldg, N, B, H, W, ptr(Gy), _st()))
-        g = _desc(V, 36 * C, C, 1, 0, N, T2, batch=(36, C, 0, 0))
-        pv = _prof_start(PROFILE_WINO2D_GEMM)
-        if PLANE_DMA and _L().efgh_plane_wgrad_supported(ctypes.byref(g), 36 * N):
-            split = _planes_split_now()
-            if split:
-                PLANE_SPLIT_HITS[1] += 1
-            _C.check((_L().efgh_plane_wgrad_x6_batched if split else _L().efgh_plane_wgrad_batched)(
-                ctypes.byref(g), ptr(Gy), 36 * N, N, ptr(S), N * C,
-                ptr(_scratch(_L().efgh_plane_wgrad_workspace(ctypes.byref(g)), dev)), PLANE_DMA_NBUF, _st()))
-        else:
-            _C.check(_L().efgh_gather_wgrad_batched(ctypes.byref(g), ptr(Gy), 36 * N, N, ptr(S), N * C,
-                                                    ptr(_scratch(_L().efgh_gather_wgrad_workspace(ctypes.byref(g)), dev)), _st()))
-        _prof_end(pv, 'planes', (0, T2, N, 36, C), 2.0 * 36 * T2 * C * N, PROFILE_WINO2D_GEMM)
-        done = _C.check_wrote(_L().efgh_wino2d_wfinish(ptr(S), ptr(dWp), N, C, odp, _st()))      # (only the finish kernel may write the reference layout)
+        done = _wino2d_wgrad(A, lda, C, N, geom, G, ldg, dWp, odp, lazy=lazy, pre_v=pre_v, pre_gy=pre_gy)
     elif route == 'wino':
         S = _scratch(_L().efgh_wino_wgrad_workspace(ctypes.byref(d)), dWp.device)    # per-tile-range partials
         done = _C.check_wrote(_L().efgh_wino_wgrad(ctypes.byref(d), ptr(G), ldg, ptr(S), ptr(dWp), odp, _st()))

@@ -991,7 +991,6 @@ class Trainer:
 
     def _forward_loss(self, pc, img, calib, A, gt, depth_weight=None):
         """forward and loss of one (micro-)batch -> (losses, gt, pred) as the criterion and the model return them"""
-        ops.w2v_clear()
         self.flat.uses = [0] * len(self.flat.params)
         self.flat.collect_ticks = True
         try:

@@ -73,8 +73,7 @@ class LayerCapture(RC.Capture):
         """-> [forward entry points | exception type, backward entry points, digest]"""
         from efgh_amd.nets import layers as L
         ops = self.ops
-        ops.W2V_CACHE.clear()
-        ops.TLS.train_step, ops.TLS.w2v_wanted, ops.BLUR_DGRAD_FUSED = bool(train and grad), False, True
+        ops.TLS.train_step, ops.BLUR_DGRAD_FUSED = bool(train and grad), True
         self.take()
         with torch.set_grad_enabled(grad), _Keep() as keep:
             named, bns, run = build(grad)

@@ -8,7 +8,8 @@ the library (descriptor fields verbatim, pointers as (argument tensor, byte offs
 the answers of stats_rows / pool_fusable / lazy_capable / wgrad_lazy_capable; the return value.
 
 The stand-in answers EFGH_WROTE_OUT when it is handed an efgh_wgrad_out_desc, so that the `done` path of gather_wgrad is taken.
-A kept W2V_CACHE entry makes gather_wgrad call torch.cuda.current_stream() and Tensor.record_stream: both get a stand-in too."""
+The input transform a 2-D Winograd forward keeps for its weight gradient travels as the caller's own nets/fn.py hands it over:
+gather_gemm(keep_v=) receives it, gather_wgrad(pre_v=) takes it - a buffer the dispatch made, so it stays 'tmp' in the digests."""
 import ctypes
 import base64
 import hashlib
@@ -98,15 +99,12 @@ class Capture:
 
     def __enter__(self):
         ops, _C = self.ops, self._C
-        self.saved = [(ops, '_L', ops._L), (ops, '_st', ops._st), (_C, 'stream_ptr', _C.stream_ptr), (torch.cuda, 'Event', torch.cuda.Event),
-                      (torch.cuda, 'current_stream', torch.cuda.current_stream)]
+        self.saved = [(ops, '_L', ops._L), (ops, '_st', ops._st), (_C, 'stream_ptr', _C.stream_ptr), (torch.cuda, 'Event', torch.cuda.Event)]
         self.saved += [(ops, k, getattr(ops, k)) for k in LISTS + OFF_IN_TURN + THRESHOLDS
                        + ('PLANES_SPLIT', 'KSPLIT_MAX_ROWS', 'BN_BWD_FUSED', 'BN_BWD_FUSED_2D', 'FOLD_UNPACK', 'W2V_KEEP')]
         ops._L = lambda: self
         ops._st = _C.stream_ptr = lambda: 0
         torch.cuda.Event = _Ev
-        torch.cuda.current_stream = lambda *a: None
-        torch.Tensor.record_stream = lambda t, s: None
         for k in LISTS:
             setattr(ops, k, [])
         self.train_step = ops.TLS.train_step
@@ -115,9 +113,7 @@ class Capture:
     def __exit__(self, *exc):
         for o, k, v in self.saved:
             setattr(o, k, v)
-        del torch.Tensor.record_stream
-        self.ops.TLS.train_step, self.ops.TLS.w2v_wanted = self.train_step, False
-        self.ops.W2V_CACHE.clear()
+        self.ops.TLS.train_step = self.train_step
 
     def run(self, fn, tensors, sw=None):
         """one case -> [entry points | exception type, digest hash of (profile records, arguments, return value)]"""
@@ -166,6 +162,7 @@ def _gemm(cap, A, lda, C, T, Wp, N, M, out, ldo, sw=None, **kw):
 
 def _wgrad(cap, A, lda, C, T, N, M, G, ldg, dWp, sw=None, **kw):
     names = dict(kw, A=A, G=G, dWp=dWp)
+    names.pop('pre_v', None)         # (the forward's own buffer, not an argument of the layer: 'tmp')
     if kw.get('unpack') is not None:
         names['unpack.dW'] = kw['unpack'][0]
     o = kw.get('lazy')
@@ -322,11 +319,12 @@ def special_cases(cap):
             up = (z(N, C, 3, 3), N, 9, C, C, C * 9, 9, 1, list(range(9)), fold)
             yield tag + 'wgrad unpack FOLD_UNPACK=%s' % fold, _wgrad(cap, A, C, C, 9, N, M, out, N, z(N, 9, C), {'FOLD_UNPACK': fold},
                                                                     mode=1, geom=g, unpack=up)
-        # the transform kept by the forward (TLS.w2v_wanted), found by the weight gradient; then missing (it was popped)
-        ops.TLS.w2v_wanted = True
-        yield tag + 'forward keeps', _gemm(cap, A, C, C, 9, Wp, N, M, out, N, mode=1, geom=g)
-        ops.TLS.w2v_wanted = False
-        yield tag + 'wgrad finds kept', _wgrad(cap, A, C, C, 9, N, M, out, N, z(N, 9, C), mode=1, geom=g)
+        # the transform kept by the forward (keep_v=), handed to the weight gradient where that runs on the 2-D Winograd path, as
+        # nets/fn.py does; then without it (a second backward)
+        slot = []
+        yield tag + 'forward keeps', _gemm(cap, A, C, C, 9, Wp, N, M, out, N, mode=1, geom=g, keep_v=slot)
+        kept = {'pre_v': slot[0]} if (slot and ops.wgrad_route(1, C, N, 9, g) == 'wino2d') else {}
+        yield tag + 'wgrad finds kept', _wgrad(cap, A, C, C, 9, N, M, out, N, z(N, 9, C), mode=1, geom=g, **kept)
         yield tag + 'wgrad kept gone', _wgrad(cap, A, C, C, 9, N, M, out, N, z(N, 9, C), mode=1, geom=g)
         yield tag + 'wgrad W2V_KEEP off', _gemm(cap, A, C, C, 9, Wp, N, M, out, N, {'W2V_KEEP': False}, mode=1, geom=g)
     # 16- / 32-channel launches on a channel slice at an offset of 2 floats (not 16-byte aligned), with and without statistics
@@ -356,7 +354,6 @@ def table():
         ops = cap.ops
         for name, sw, train, grid in SETTINGS:
             ops.TLS.train_step = train
-            ops.W2V_CACHE.clear()
             for k, v in sw.items():
                 setattr(ops, k, v)
             rows = list(grid_cases(cap, grid)) + list(special_cases(cap))

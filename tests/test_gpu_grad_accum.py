@@ -172,7 +172,6 @@ def test_one_micro_batch_is_a_plain_step(world, route):
 def _micro_gradient(tr, mb):
     """Trainer.step's path up to the optimizer, by hand: the flat gradient of one micro-batch"""
     pc, img, calib, A, gt = mb
-    ops.w2v_clear()
     tr.flat.uses = [0] * len(tr.flat.params)
     tr.model.train()
     tr.flat.collect_ticks = True

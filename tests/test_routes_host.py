@@ -15,8 +15,8 @@ The case list (route_capture.grid_cases, special_cases), run under every setting
 - linear rows (mode 0, no geometry; N == 4 and C == 4 among them), the four transposed-convolution parity classes, the BCL blur on
   both sides of every k-split condition and with alias_mask, the batched correlation launches, M_dev and batch on shapes every family
   would serve, MODE_BLUR_R plain and with each argument it rejects, lazy / pre_v / pre_gy and pool=True / 'h' on routes that take
-  them and on routes that do not, bn_bwd with BN_BWD_FUSED / BN_BWD_FUSED_2D on and off, unpack with FOLD_UNPACK on and off, a kept
-  and a missing W2V_CACHE entry (torch.cuda.current_stream and Tensor.record_stream get a stand-in), 16- / 32-channel launches at
+  them and on routes that do not, bn_bwd with BN_BWD_FUSED / BN_BWD_FUSED_2D on and off, unpack with FOLD_UNPACK on and off, the
+  forward's input transform kept (keep_v=) and handed to the weight gradient (pre_v=) or not, 16- / 32-channel launches at
   a_off / out_off / res_off of 2 with and without statistics, and misaligned weight-gradient operands.
 At fa9984f the table reaches every entry point of REQUIRED in tests/test_gpu_launch_contract.py (checked below on the fixture)."""
 import json
