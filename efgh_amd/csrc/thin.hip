@@ -847,7 +847,7 @@ extern "C" int efgh_convt_col2im(const float *Y, int64_t ldy, int32_t B, int32_t
                                  int32_t Wo, int32_t O, int32_t pad, const float *scale, const float *shift,
                                  int32_t act, float slope, float *out, int64_t ldo, void *stream_) {
     EFGH_CHECK_ARG(Y && out && B > 0 && Hin > 0 && Win > 0 && Ho > 0 && Wo > 0 && O >= 1 && O <= 4);
-    EFGH_CHECK_ARG(ldy >= 9 * O && ldo >= 4 && ldo % 4 == 0);
+    EFGH_CHECK_ARG(ldy >= 9 * O && ldo >= 4 && ldo % 4 == 0 && (((uintptr_t)out) & 15) == 0);     // one 16-byte store per pixel
     hipStream_t st = (hipStream_t)stream_;
     if (B <= 65535 && Ho <= 65535) {
         const dim3 grid((Wo + 255) / 256, Ho, B);

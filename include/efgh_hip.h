@@ -909,6 +909,7 @@ int efgh_plane_wgrad_x6_batched(const efgh_gemm_desc *d, const float *G, int64_t
 /* stride-2 3x3 transposed conv with <= 4 output channels (G's depth / mask heads, gnet.py:56-68) as
  * ONE gather-GEMM over the input pixels (Y [B*Hin*Win][ldy], column (kh*3+kw)*O+o) + this fold:
  * out[b][oh][ow][o] = act(scale[o]*sum_{oh=2ih-pad+kh, ow=2iw-pad+kw} Y[b][ih][iw][..] + shift[o]).
+ * out is written as one 16-byte store per pixel: ldo % 4 == 0 and a 16-byte aligned `out`, anything else is refused.
  * efgh_convt_im2col is the adjoint unfold of the output gradient (feeds the weight-gradient GEMM). */
 int efgh_convt_col2im(const float *Y, int64_t ldy, int32_t B, int32_t Hin, int32_t Win, int32_t Ho, int32_t Wo,
                       int32_t O, int32_t pad, const float *scale, const float *shift, int32_t act, float slope,
