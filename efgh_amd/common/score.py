@@ -48,15 +48,12 @@ class Score:
         return torch.argmax(getattr(self, by), dim=1)
 
 
-def _fail(what):
-    _fuse_fail(what, 'score')
-
-
-def score(pc, img, cam_T_velo, value=None, value_range=(0.0, 1.0), bins=32, min_depth=0.0, want_hist=False):
-    """pc float32 (B, C >= 3, N) | img as in `fuse` | cam_T_velo (B,K,3,4), or (B,3,4) for K = 1, of either float width | value
-    float32 (B,N) binned over value_range = (lo, hi), or uint8 (B,N) binned over (0, 256); None: pc[:, 3] | bins 8, 16, 32 or 64
-    -> Score.  Inputs are never written, outputs are new tensors, nothing is read back to the host."""
-    B, N = _cloud_dims(pc, 'score')
+def _checked(who, pc, img, cam_T_velo, value, value_range, bins, min_depth):
+    """the argument checks `score` and `score_soft` share, every one in front of any launch -> (B, N, K, T (B,K,3,4), img, H, W,
+    value, lo, hi)"""
+    def _fail(what):
+        _fuse_fail(what, who)
+    B, N = _cloud_dims(pc, who)
     T = cam_T_velo
     if not torch.is_tensor(T):
         _fail('cam_T_velo: expected a tensor, got %s (stage_poses stacks the matrices of a `pred` dict)' % type(T).__name__)
@@ -69,7 +66,7 @@ def score(pc, img, cam_T_velo, value=None, value_range=(0.0, 1.0), bins=32, min_
     K = T.shape[1]
     if K > MAX_CANDIDATES:
         _fail('cam_T_velo: K = %d candidates, at most %d a call' % (K, MAX_CANDIDATES))
-    img, H, W = _image_u8(img, B, 'score')
+    img, H, W = _image_u8(img, B, who)
     if value is None:
         if pc.shape[1] < 4:
             _fail('value: None takes pc[:, 3], and the cloud has %d rows' % pc.shape[1])
@@ -90,21 +87,35 @@ def score(pc, img, cam_T_velo, value=None, value_range=(0.0, 1.0), bins=32, min_
         if not (math.isfinite(lo) and math.isfinite(hi) and lo < hi):
             _fail('value_range: %r, expected finite lo < hi' % (value_range,))
     if isinstance(bins, bool) or not isinstance(bins, (int, np.integer)) or bins not in BINS:
-        _fail('bins: %r, supported are %s (the counters live in LDS; no smoothing kernel is built)' % (bins, ', '.join(map(str, BINS))))
-    _finite_nonneg('min_depth', min_depth, 'score')
-    _on_the_clouds_device(pc, (('img', img), ('cam_T_velo', T), ('value', value)), 'score', 'the scoring')
+        _fail('bins: %r, supported are %s (the counters live in LDS)' % (bins, ', '.join(map(str, BINS))))
+    _finite_nonneg('min_depth', min_depth, who)
+    _on_the_clouds_device(pc, (('img', img), ('cam_T_velo', T), ('value', value)), who, 'the scoring')
+    return B, N, K, T, img, H, W, value, lo, hi
+
+
+def _kernel_inputs(pc, value, T, img):
+    """the checked arguments as the kernels read them (call with the cloud's device current): a cloud with unit point stride, a
+    float32 value with unit stride, float64 matrices (B,K,3,4) contiguous, a uint8 (B,H,W,3) image"""
+    if pc.stride(2) != 1:
+        pc = pc.contiguous()
+    if value.dtype == torch.uint8:
+        value = value.to(torch.float32)                          # exact
+    elif value.stride(1) != 1:
+        value = value.contiguous()
+    P = T.detach().to(torch.float64).contiguous()                # float32 -> float64 is exact
+    return pc, value, P, _u8_hwc(img)
+
+
+def score(pc, img, cam_T_velo, value=None, value_range=(0.0, 1.0), bins=32, min_depth=0.0, want_hist=False):
+    """pc float32 (B, C >= 3, N) | img as in `fuse` | cam_T_velo (B,K,3,4), or (B,3,4) for K = 1, of either float width | value
+    float32 (B,N) binned over value_range = (lo, hi), or uint8 (B,N) binned over (0, 256); None: pc[:, 3] | bins 8, 16, 32 or 64
+    -> Score.  Inputs are never written, outputs are new tensors, nothing is read back to the host."""
+    B, N, K, T, img, H, W, value, lo, hi = _checked('score', pc, img, cam_T_velo, value, value_range, bins, min_depth)
 
     dev = pc.device
     L, st = _C.lib(), _C.stream_ptr
     with torch.cuda.device(dev):
-        if pc.stride(2) != 1:
-            pc = pc.contiguous()
-        if value.dtype == torch.uint8:
-            value = value.to(torch.float32)                      # exact
-        elif value.stride(1) != 1:
-            value = value.contiguous()
-        P = T.detach().to(torch.float64).contiguous()            # float32 -> float64 is exact
-        img = _u8_hwc(img)
+        pc, value, P, img = _kernel_inputs(pc, value, T, img)
         hist = torch.empty((B, K, bins, bins), dtype=torch.int32, device=dev)      # (counts stay below 2^31: N does)
         out = torch.empty((B, K, 5), dtype=torch.float64, device=dev)
         count = torch.empty((B, K), dtype=torch.int32, device=dev)
@@ -159,11 +170,15 @@ def perturbations(rot_deg, trans, steps=1, device=None):
         mid = K // 2                                             # the all-zero row of the lexicographic order goes first
         grid = torch.cat([grid[mid:mid + 1], grid[:mid], grid[mid + 1:]])
         p[:, axes] = grid * torch.tensor([scale[a] for a in axes], **f64)
-    r = torch.deg2rad(p[:, :3])
+    return _rigid(torch.deg2rad(p[:, :3]), p[:, 3:])
+
+
+def _rigid(r, t):
+    """r (K,3) Euler angles in radians, t (K,3) -> (K,4,4) float64 [Rz Ry Rx | t], with torch ops (differentiable in r and t)"""
     (cx, cy, cz), (sx, sy, sz) = torch.cos(r).unbind(1), torch.sin(r).unbind(1)
-    zero, one = torch.zeros(K, **f64), torch.ones(K, **f64)
-    rows = [[cz * cy, cz * sy * sx - sz * cx, cz * sy * cx + sz * sx, p[:, 3]], [sz * cy, sz * sy * sx + cz * cx, sz * sy * cx - cz * sx, p[:, 4]],
-            [-sy, cy * sx, cy * cx, p[:, 5]], [zero, zero, zero, one]]
+    zero, one = torch.zeros_like(cx), torch.ones_like(cx)
+    rows = [[cz * cy, cz * sy * sx - sz * cx, cz * sy * cx + sz * sx, t[:, 0]], [sz * cy, sz * sy * sx + cz * cx, sz * sy * cx - cz * sx, t[:, 1]],
+            [-sy, cy * sx, cy * cx, t[:, 2]], [zero, zero, zero, one]]
     return torch.stack([torch.stack(row, 1) for row in rows], 1)
 
 

@@ -10,22 +10,9 @@
 // run.  There is no floating-point atomic.  No occlusion test: which points a nearer surface hides changes with the candidate, and
 // a z-buffer per candidate is not built.  Built with -ffp-contract=off for the projection and for the value bin, whose subtraction
 // and product round separately (tests/score_contract.py restates both in numpy).
-#include "fuse_project.h"
+#include "score_common.h"
 
 namespace {
-constexpr int TPB = 256;
-constexpr int MAX_BINS = 64;
-constexpr int MAX_K = 4096;
-// points of one sample and candidate that one workgroup counts into its LDS histogram before it flushes (a multiple of TPB).  The
-// flush costs up to bins^2 global atomics a workgroup, the chunk is what it is spread over; profiles/score.txt has the measurement
-#ifndef EFGH_SCORE_CHUNK
-#define EFGH_SCORE_CHUNK 4096
-#endif
-static_assert(EFGH_SCORE_CHUNK % TPB == 0 && EFGH_SCORE_CHUNK > 0, "the chunk is whole passes of the block");
-
-// Pillow's L of an RGB pixel (jitter.hip's luma)
-__device__ __forceinline__ int luma(const uint8_t *p) { return (19595 * p[0] + 38470 * p[1] + 7471 * p[2] + 0x8000) >> 16; }
-
 __global__ void __launch_bounds__(TPB)
 k_score_hist(const float *__restrict__ pc, long long bs, long long cs, int N, const float *__restrict__ value, long long vbs,
              const double *__restrict__ P, int K, const uint8_t *__restrict__ img, int H, int W, int bins, float lo, float scale,
@@ -59,18 +46,6 @@ k_score_hist(const float *__restrict__ pc, long long bs, long long cs, int N, co
         const unsigned n = cnt[c];
         if (n) atomicAdd(out + c, n);
     }
-}
-
-// t[0 .. n) (n a power of two) summed in place, pairs a distance n/2, n/4, .. 1 apart: ONE shape and order whatever the block does
-__device__ __forceinline__ double tree_sum(double *t, int n) {
-    for (int s = n >> 1; s > 0; s >>= 1) {
-        __syncthreads();
-        for (int i = threadIdx.x; i < s; i += TPB) t[i] = t[i] + t[i + s];
-    }
-    __syncthreads();
-    const double r = t[0];
-    __syncthreads();
-    return r;
 }
 
 __device__ __forceinline__ double clogc(unsigned c) { return c ? (double)c * log((double)c) : 0.0; }
@@ -118,15 +93,6 @@ k_score_mi(const unsigned *__restrict__ hist, int bins, double *__restrict__ sco
     }
 }
 
-#define SCORE_ARG(cond, ...)                                                         \
-    do {                                                                             \
-        if (!(cond)) {                                                               \
-            efgh_set_error(__VA_ARGS__);                                             \
-            return EFGH_E_INVALID;                                                   \
-        }                                                                            \
-    } while (0)
-
-bool bins_ok(int bins) { return bins == 8 || bins == 16 || bins == 32 || bins == 64; }
 }  // namespace
 
 extern "C" int32_t efgh_score_chunk(void) { return EFGH_SCORE_CHUNK; }

@@ -1173,6 +1173,44 @@ int efgh_score_hist(const float *pc, int64_t pc_bstride, int64_t pc_cstride, int
                     float lo, float hi, double min_depth, uint32_t *hist, void *stream);
 int efgh_score_mi(const uint32_t *hist, int32_t B, int32_t K, int32_t bins, double *score, int32_t *count, void *stream);
 
+/* ---- the differentiable form of the score: soft histogram and pose gradient (csrc/score_soft.hip; tests/score_soft_contract.py) ------
+ * A Parzen-smoothed joint histogram (Mattes' formulation of the objective above) whose MI has an analytic gradient with respect to
+ * the projection matrix.  Not in the reference; nothing runs unless called.  All arguments that efgh_score_hist has mean what they
+ * mean there; a point COUNTS by the same rule and has the same value bin x.  All float arithmetic is float64, every operation
+ * rounded on its own.  The weight resolution is FRAC = 256: a point adds 256 to its histogram.
+ *   Grey sample: bilinear on the integer L at (u - 0.5, v - 0.5), efgh_fuse_resolve's convention: x0 = floor(u - 0.5), tx = (u - 0.5)
+ *     - x0 (and in y), the four neighbours clamped to the image, a, b, c, d = L at (ya,xa), (ya,xb), (yb,xa), (yb,xb);
+ *     top = a + (b - a) tx, bot = c + (d - c) tx, g = top + (bot - top) ty; gu = (b - a) + ((d - c) - (b - a)) ty, gv = bot - top.
+ *   Grey cell: t = g (bins / 256) - 0.5, j = clip(floor(t), 0, bins - 2), fr = clip(t - j, 0, 1), q = (int)(256 fr + 0.5); the gate
+ *     s = 1 iff 0 < t - j < 1 (the grey coordinate is not clamped and not on a cell centre).
+ *   efgh_score_soft_hist   zeroes hist, then hist[x][j] += 256 - q and hist[x][j + 1] += q for every point that counts.  pool = 0:
+ *     uint32 [B][K][bins][bins]; pool = 1: [K][bins][bins], summed over the samples.  Integer atomics only.  N < 2^23, and B N < 2^23
+ *     when pooled (the total stays below 2^31).  The result goes through efgh_score_mi as it is (pooled: with B = 1): its `count`
+ *     is 256 times the number of points, and MI does not change under that scale.
+ *   efgh_score_soft_table  one workgroup per histogram (n_hist = B K, or K pooled): column sums h_y in integers; table f64 [n_hist]
+ *     [bins][bins] = log h_xy - log h_y where h_xy > 0 and 0 elsewhere; flag u8, the same shape: h_xy > 0; total u32 [n_hist].
+ *   efgh_score_soft_grad   grid (chunk, k, b) behind it.  Per point with s = 1 and both cells [x][j], [x][j + 1] non-empty:
+ *     a = ((table[x][j+1] - table[x][j]) (bins / 256)) / n, n = total / 256 of the point's histogram; with X = (px, py, pz, 1) and w
+ *     the projection's third row, r0 = (a gu) / w, r1 = (a gv) / w, r2 = -((a (gu u + gv v)) / w): r0 X, r1 X, r2 X are added to
+ *     rows 0, 1, 2 of dMI/dP.  A thread sums its points in index order, the block by a fixed pairwise tree of plain LDS stores;
+ *     part f64 [B][K][n_chunk][12], n_chunk = ceil(N / efgh_score_chunk()), is written with plain stores.
+ *   efgh_score_soft_fold   one workgroup per (b, k): the n_chunk (<= 2048) partials, padded with zeros to a power of two, through
+ *     the same tree -> grad f64 [B][K][12] (row-major 3x4).
+ * No floating-point atomic: the same bits run to run.  An empty histogram gives a zero gradient; nothing is NaN.  The gradient is the
+ * derivative of the UNQUANTISED function (q = 256 fr without the rounding) at fixed membership: it ignores points that enter or
+ * leave the frame, and is zero where t is clamped.  There is no occlusion test.  EFGH_E_INVALID with a message naming the value, and
+ * nothing launched, for what efgh_score_hist refuses, pool not 0 / 1, N or pooled B N >= 2^23, n_hist or n_chunk out of range. */
+int efgh_score_soft_hist(const float *pc, int64_t pc_bstride, int64_t pc_cstride, int32_t B, int32_t N, const float *value,
+                         int64_t value_bstride, const double *P, int32_t K, const uint8_t *img, int32_t H, int32_t W, int32_t bins,
+                         float lo, float hi, double min_depth, int32_t pool, uint32_t *hist, void *stream);
+int efgh_score_soft_table(const uint32_t *hist, int32_t n_hist, int32_t bins, double *table, uint8_t *flag, uint32_t *total,
+                          void *stream);
+int efgh_score_soft_grad(const float *pc, int64_t pc_bstride, int64_t pc_cstride, int32_t B, int32_t N, const float *value,
+                         int64_t value_bstride, const double *P, int32_t K, const uint8_t *img, int32_t H, int32_t W, int32_t bins,
+                         float lo, float hi, double min_depth, int32_t pool, const double *table, const uint8_t *flag,
+                         const uint32_t *total, double *part, void *stream);
+int efgh_score_soft_fold(const double *part, int32_t B, int32_t K, int32_t n_chunk, double *grad, void *stream);
+
 /* ---- pose heads, forward (one launch each) -----------------------------------------------------------------------------------
  * efgh_pose_head_normal: softmax + L2 normalisation of the nd (2 or 3) "abs" logits, sign class = first argmax of the 2^nd sign
  *   logits decoded MSB-first, normal = abs * sign, rotation of the normal onto (dx,dy,dz) as a 4x4 (enet.py:161-176, hnet.py:59-77,
