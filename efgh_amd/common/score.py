@@ -10,13 +10,14 @@ one call.  The number peaks where the two sensors agree.  Not in the reference; 
     around = candidates_around(pred['cam_T_velo'], rot_deg=(0.5, 0.5, 0.5), trans=(0.05, 0.05, 0.05))      # (B,729,3,4)
 
 Pixel convention, image and matrices are `fuse`'s: the image is the one the matrices project into (`raw_cam_img_size`).  A point
-counts iff it is in frame under its candidate and its value is not NaN.  There is NO occlusion test - which points a nearer surface
-hides changes with the candidate, and a z-buffer per candidate is not built.
+counts iff it is in frame under its candidate and its value is not NaN.  `score` itself asks nothing about occlusion - which points a
+nearer surface hides changes with the candidate; `score_visible` (score_vis.py) puts a depth test per candidate in front of the
+same histogram.
 
 MI of a sparse histogram is biased UPWARDS when the count n is small (with n points on bins^2 cells the plug-in estimate of an
-independent pair is about (bins - 1)^2 / (2 n) nats, not 0), so candidates with very different `count` are not comparable without a
-correction: `count` and, with want_hist, `hist` are returned for that.  No effect on registration accuracy is claimed or was
-measured."""
+independent pair is about (bins - 1)^2 / (2 n) nats, not 0), so candidates with very different `count` are not comparable as they
+are: `miller_madow(score(..., want_hist=True))` (score_vis.py) applies the standard correction from `count` and `hist`, and
+`score_visible` returns it as `mi_mm`.  No effect on registration accuracy is claimed or was measured."""
 import math
 
 import numpy as np
@@ -48,9 +49,8 @@ class Score:
         return torch.argmax(getattr(self, by), dim=1)
 
 
-def _checked(who, pc, img, cam_T_velo, value, value_range, bins, min_depth):
-    """the argument checks `score` and `score_soft` share, every one in front of any launch -> (B, N, K, T (B,K,3,4), img, H, W,
-    value, lo, hi)"""
+def _checked_poses(who, pc, cam_T_velo):
+    """the cloud and the candidate matrices -> (B, N, K, T (B,K,3,4)); the head of `_checked`, and all `visible_mask` needs of it"""
     def _fail(what):
         _fuse_fail(what, who)
     B, N = _cloud_dims(pc, who)
@@ -66,6 +66,15 @@ def _checked(who, pc, img, cam_T_velo, value, value_range, bins, min_depth):
     K = T.shape[1]
     if K > MAX_CANDIDATES:
         _fail('cam_T_velo: K = %d candidates, at most %d a call' % (K, MAX_CANDIDATES))
+    return B, N, K, T
+
+
+def _checked(who, pc, img, cam_T_velo, value, value_range, bins, min_depth, more=None):
+    """the argument checks `score`, `score_soft` and their `_visible` forms share, every one in front of any launch -> (B, N, K,
+    T (B,K,3,4), img, H, W, value, lo, hi).  `more(B, K, H, W)`, if given, runs in front of the device check, which stays the last"""
+    def _fail(what):
+        _fuse_fail(what, who)
+    B, N, K, T = _checked_poses(who, pc, cam_T_velo)
     img, H, W = _image_u8(img, B, who)
     if value is None:
         if pc.shape[1] < 4:
@@ -89,6 +98,8 @@ def _checked(who, pc, img, cam_T_velo, value, value_range, bins, min_depth):
     if isinstance(bins, bool) or not isinstance(bins, (int, np.integer)) or bins not in BINS:
         _fail('bins: %r, supported are %s (the counters live in LDS)' % (bins, ', '.join(map(str, BINS))))
     _finite_nonneg('min_depth', min_depth, who)
+    if more is not None:
+        more(B, K, H, W)
     _on_the_clouds_device(pc, (('img', img), ('cam_T_velo', T), ('value', value)), who, 'the scoring')
     return B, N, K, T, img, H, W, value, lo, hi
 

@@ -10,7 +10,8 @@ objective), which gives the MI an analytic gradient with respect to the projecti
 
 The gradient is the derivative of the UNQUANTISED function (the weights are rounded to 1/256 for the integer histogram) at fixed
 membership: it ignores points that enter or leave the frame, and it is zero where the grey coordinate is clamped.  Everything `score`
-says about occlusion, about the bias of a sparse histogram and about what was measured holds here too."""
+says about occlusion, about the bias of a sparse histogram and about what was measured holds here too: the depth test per candidate
+is `score_soft_visible`, the correction `miller_madow` (both score_vis.py), and `refine` takes the former as its `scorer`."""
 import math
 
 import torch
@@ -106,10 +107,12 @@ def refine(pc, img, P0, value=None, value_range=(0.0, 1.0), bins=32, iters=100, 
     P0 itself, bit for bit.
 
     It is a LOCAL optimiser: it climbs from P0 and stops at the nearest maximum of a function that has many, so start it from a
-    pose that is already close (the network's, yesterday's extrinsics, the best of `candidates_around`).  There is no occlusion
-    test.  MI of a sparse histogram is biased upwards, so histograms of very different `count` are not comparable - an iterate
-    that pushes points out of the frame can score higher for that alone.  No effect on registration accuracy is claimed or was
-    measured."""
+    pose that is already close (the network's, yesterday's extrinsics, the best of `candidates_around`).  The default scorer has
+    no occlusion test; `scorer=functools.partial(score_soft_visible, occlusion=Occlusion(...))` (score_vis.py) scores every iterate
+    on the points visible under it.  MI of a sparse histogram is biased upwards, so histograms of very different `count` are not
+    comparable - an iterate that pushes points out of the frame can score higher for that alone; `refine` climbs the uncorrected
+    `mi` (the Miller-Madow term of score_vis.py is piecewise constant in the pose).  No effect on registration accuracy is claimed
+    or was measured."""
     who = 'refine'
     if not torch.is_tensor(P0) or P0.dim() != 3 or tuple(P0.shape[1:]) != (3, 4) or P0.dtype not in (torch.float32, torch.float64):
         raise _C.EfghError('%s: P0: expected a float (B,3,4) tensor, got %s'

@@ -1,5 +1,5 @@
-// What score.hip and score_soft.hip share (both built with -ffp-contract=off): the projection, the block size, the limits and the
-// chunk of a launch, Pillow's L, the fixed pairwise tree, the argument refusals.
+// What score.hip, score_soft.hip and score_vis.hip share (all built with -ffp-contract=off): the projection, the block size, the
+// limits and the chunk of a launch, Pillow's L, the visibility mask's layout, the fixed pairwise tree, the argument refusals.
 #pragma once
 #include "fuse_project.h"
 
@@ -16,6 +16,11 @@ static_assert(EFGH_SCORE_CHUNK % TPB == 0 && EFGH_SCORE_CHUNK > 0, "the chunk is
 
 // Pillow's L of an RGB pixel (jitter.hip's luma)
 __device__ __forceinline__ int luma(const uint8_t *p) { return (19595 * p[0] + 38470 * p[1] + 7471 * p[2] + 0x8000) >> 16; }
+
+// bit i % 32 of word i / 32 of one candidate's visibility mask (score_vis.hip writes it): does point i count?
+__device__ __forceinline__ bool mask_bit(const unsigned *__restrict__ m, int i) { return (m[i >> 5] >> (i & 31)) & 1u; }
+// the mask words of one (b, k): ceil(N / 32)
+__device__ __forceinline__ long long mask_words(int N) { return ((long long)N + 31) >> 5; }
 
 // t[0 .. n) (n a power of two) summed in place, pairs a distance n/2, n/4, .. 1 apart: ONE shape and order whatever the block does
 __device__ __forceinline__ double tree_sum(double *t, int n) {

@@ -11,7 +11,9 @@
 //   k_soft_fold    one workgroup per (b, k): the chunks' partials through the same fixed tree
 // Float64 throughout with every operation rounded on its own (-ffp-contract=off; tests/score_soft_contract.py restates it in numpy).
 // No floating-point atomic: two runs give the same bits.  The gradient is that of the unquantised function at fixed membership: it
-// ignores points that enter or leave the frame and is zero where the grey coordinate is clamped.
+// ignores points that enter or leave the frame and is zero where the grey coordinate is clamped.  k_soft_hist and k_soft_grad have
+// ONE body and two instances each: the MASKED one (efgh_score_soft_hist_masked, efgh_score_soft_grad_masked) also wants the point's bit
+// in score_vis.hip's per-candidate visibility mask, so histogram and gradient share their membership by construction.
 #include "score_common.h"
 
 namespace {
@@ -60,10 +62,11 @@ __device__ __forceinline__ bool sample(const float *__restrict__ pcb, long long 
     return true;
 }
 
+template <bool MASKED>
 __global__ void __launch_bounds__(TPB)
 k_soft_hist(const float *__restrict__ pc, long long bs, long long cs, int N, const float *__restrict__ value, long long vbs,
             const double *__restrict__ P, int K, const uint8_t *__restrict__ img, int H, int W, int bins, float lo, float scale,
-            double min_depth, int pool, unsigned *__restrict__ hist) {
+            double min_depth, int pool, const unsigned *__restrict__ mask, unsigned *__restrict__ hist) {
     __shared__ unsigned cnt[MAX_BINS * MAX_BINS];
     const int k = blockIdx.y, b = blockIdx.z, nb = bins * bins;
     for (int c = threadIdx.x; c < nb; c += TPB) cnt[c] = 0u;
@@ -72,10 +75,12 @@ k_soft_hist(const float *__restrict__ pc, long long bs, long long cs, int N, con
     const float *__restrict__ vb = value + b * vbs;
     const double *__restrict__ T = P + 12 * ((long long)b * K + k);
     const uint8_t *__restrict__ imgb = img + (long long)b * H * W * 3;
+    const unsigned *__restrict__ mk = MASKED ? mask + ((long long)b * K + k) * mask_words(N) : nullptr;
     const int first = blockIdx.x * EFGH_SCORE_CHUNK;        // (N < 2^23: no index here comes near 2^31)
     const int end = min(first + EFGH_SCORE_CHUNK, N);
     for (int i = first + threadIdx.x; i < end; i += TPB) {
         Sample s;
+        if (MASKED && !mask_bit(mk, i)) continue;                // hidden under this candidate
         if (!sample(pcb, cs, i, vb[i], T, imgb, H, W, bins, lo, scale, min_depth, s)) continue;
         unsigned *row = cnt + s.x * bins + s.j;                  // j <= bins - 2: cell j + 1 is in the row
         if (s.q != FRAC) atomicAdd(row, (unsigned)(FRAC - s.q));
@@ -129,17 +134,19 @@ __device__ __forceinline__ void tree12(double (*red)[TPB]) {
     __syncthreads();
 }
 
+template <bool MASKED>
 __global__ void __launch_bounds__(TPB)
 k_soft_grad(const float *__restrict__ pc, long long bs, long long cs, int N, const float *__restrict__ value, long long vbs,
             const double *__restrict__ P, int K, const uint8_t *__restrict__ img, int H, int W, int bins, float lo, float scale,
             double min_depth, int pool, const double *__restrict__ table, const uint8_t *__restrict__ flag,
-            const unsigned *__restrict__ total, double *__restrict__ part) {
+            const unsigned *__restrict__ total, const unsigned *__restrict__ mask, double *__restrict__ part) {
     __shared__ double red[12][TPB];
     const int k = blockIdx.y, b = blockIdx.z, nb = bins * bins;
     const float *__restrict__ pcb = pc + b * bs;
     const float *__restrict__ vb = value + b * vbs;
     const double *__restrict__ T = P + 12 * ((long long)b * K + k);
     const uint8_t *__restrict__ imgb = img + (long long)b * H * W * 3;
+    const unsigned *__restrict__ mk = MASKED ? mask + ((long long)b * K + k) * mask_words(N) : nullptr;
     const long long hi = pool ? (long long)k : (long long)b * K + k;
     const double *__restrict__ Tt = table + hi * nb;
     const uint8_t *__restrict__ fl = flag + hi * nb;
@@ -152,6 +159,7 @@ k_soft_grad(const float *__restrict__ pc, long long bs, long long cs, int N, con
     const int end = min(first + EFGH_SCORE_CHUNK, N);
     for (int i = first + threadIdx.x; i < end; i += TPB) {      // a thread's points in index order
         Sample s;
+        if (MASKED && !mask_bit(mk, i)) continue;                // hidden under this candidate
         if (!sample(pcb, cs, i, vb[i], T, imgb, H, W, bins, lo, scale, min_depth, s)) continue;
         const int c0 = s.x * bins + s.j;
         if (!(s.s && fl[c0] && fl[c0 + 1])) continue;            // gate shut, or a cell that is empty: no contribution
@@ -201,22 +209,66 @@ int check_points(const char *who, int B, int N, int K, int H, int W, int bins, f
 }
 }  // namespace
 
+namespace {
+int launch_soft_hist(const char *who, bool masked, const float *pc, int64_t pc_bstride, int64_t pc_cstride, int32_t B, int32_t N,
+                     const float *value, int64_t value_bstride, const double *P, int32_t K, const uint8_t *img, int32_t H, int32_t W,
+                     int32_t bins, float lo, float hi, double min_depth, int32_t pool, const uint32_t *mask, uint32_t *hist, void *stream) {
+    hipStream_t st = (hipStream_t)stream;
+    SCORE_ARG(pc && value && P && img && hist, "%s: null pointer (pc %p, value %p, P %p, img %p, hist %p)", who, (const void *)pc,
+             (const void *)value, (const void *)P, (const void *)img, (void *)hist);
+    SCORE_ARG(!masked || mask, "%s: null pointer (mask %p)", who, (const void *)mask);
+    float scale = 0.f;
+    if (int rc = check_points(who, B, N, K, H, W, bins, lo, hi, min_depth, pool, &scale)) return rc;
+    if (hipMemsetAsync(hist, 0, (size_t)4 * (pool ? 1 : B) * K * bins * bins, st) != hipSuccess) {
+        efgh_set_error("%s: memset failed", who);
+        return EFGH_E_LAUNCH;
+    }
+    const dim3 grid(cdiv(N, EFGH_SCORE_CHUNK), K, B);
+    if (masked)
+        k_soft_hist<true><<<grid, TPB, 0, st>>>(pc, pc_bstride, pc_cstride, N, value, value_bstride, P, K, img, H, W, bins, lo, scale,
+                                                min_depth, pool, mask, hist);
+    else
+        k_soft_hist<false><<<grid, TPB, 0, st>>>(pc, pc_bstride, pc_cstride, N, value, value_bstride, P, K, img, H, W, bins, lo, scale,
+                                                 min_depth, pool, nullptr, hist);
+    EFGH_CHECK_LAUNCH();
+    return EFGH_OK;
+}
+
+int launch_soft_grad(const char *who, bool masked, const float *pc, int64_t pc_bstride, int64_t pc_cstride, int32_t B, int32_t N,
+                     const float *value, int64_t value_bstride, const double *P, int32_t K, const uint8_t *img, int32_t H, int32_t W,
+                     int32_t bins, float lo, float hi, double min_depth, int32_t pool, const double *table, const uint8_t *flag,
+                     const uint32_t *total, const uint32_t *mask, double *part, void *stream) {
+    SCORE_ARG(pc && value && P && img && table && flag && total && part,
+             "%s: null pointer (pc %p, value %p, P %p, img %p, table %p, flag %p, total %p, part %p)", who, (const void *)pc,
+             (const void *)value, (const void *)P, (const void *)img, (const void *)table, (const void *)flag, (const void *)total, (void *)part);
+    SCORE_ARG(!masked || mask, "%s: null pointer (mask %p)", who, (const void *)mask);
+    float scale = 0.f;
+    if (int rc = check_points(who, B, N, K, H, W, bins, lo, hi, min_depth, pool, &scale)) return rc;
+    const dim3 grid(cdiv(N, EFGH_SCORE_CHUNK), K, B);
+    if (masked)
+        k_soft_grad<true><<<grid, TPB, 0, (hipStream_t)stream>>>(pc, pc_bstride, pc_cstride, N, value, value_bstride, P, K, img, H, W, bins,
+                                                                 lo, scale, min_depth, pool, table, flag, total, mask, part);
+    else
+        k_soft_grad<false><<<grid, TPB, 0, (hipStream_t)stream>>>(pc, pc_bstride, pc_cstride, N, value, value_bstride, P, K, img, H, W, bins,
+                                                                  lo, scale, min_depth, pool, table, flag, total, nullptr, part);
+    EFGH_CHECK_LAUNCH();
+    return EFGH_OK;
+}
+}  // namespace
+
 extern "C" int efgh_score_soft_hist(const float *pc, int64_t pc_bstride, int64_t pc_cstride, int32_t B, int32_t N, const float *value,
                                     int64_t value_bstride, const double *P, int32_t K, const uint8_t *img, int32_t H, int32_t W,
                                     int32_t bins, float lo, float hi, double min_depth, int32_t pool, uint32_t *hist, void *stream) {
-    hipStream_t st = (hipStream_t)stream;
-    SCORE_ARG(pc && value && P && img && hist, "efgh_score_soft_hist: null pointer (pc %p, value %p, P %p, img %p, hist %p)", (const void *)pc,
-             (const void *)value, (const void *)P, (const void *)img, (void *)hist);
-    float scale = 0.f;
-    if (int rc = check_points("efgh_score_soft_hist", B, N, K, H, W, bins, lo, hi, min_depth, pool, &scale)) return rc;
-    if (hipMemsetAsync(hist, 0, (size_t)4 * (pool ? 1 : B) * K * bins * bins, st) != hipSuccess) {
-        efgh_set_error("efgh_score_soft_hist: memset failed");
-        return EFGH_E_LAUNCH;
-    }
-    k_soft_hist<<<dim3(cdiv(N, EFGH_SCORE_CHUNK), K, B), TPB, 0, st>>>(pc, pc_bstride, pc_cstride, N, value, value_bstride, P, K, img, H,
-                                                                          W, bins, lo, scale, min_depth, pool, hist);
-    EFGH_CHECK_LAUNCH();
-    return EFGH_OK;
+    return launch_soft_hist("efgh_score_soft_hist", false, pc, pc_bstride, pc_cstride, B, N, value, value_bstride, P, K, img, H, W, bins, lo,
+                            hi, min_depth, pool, nullptr, hist, stream);
+}
+
+extern "C" int efgh_score_soft_hist_masked(const float *pc, int64_t pc_bstride, int64_t pc_cstride, int32_t B, int32_t N,
+                                           const float *value, int64_t value_bstride, const double *P, int32_t K, const uint8_t *img,
+                                           int32_t H, int32_t W, int32_t bins, float lo, float hi, double min_depth, int32_t pool,
+                                           const uint32_t *mask, uint32_t *hist, void *stream) {
+    return launch_soft_hist("efgh_score_soft_hist_masked", true, pc, pc_bstride, pc_cstride, B, N, value, value_bstride, P, K, img, H, W,
+                            bins, lo, hi, min_depth, pool, mask, hist, stream);
 }
 
 extern "C" int efgh_score_soft_table(const uint32_t *hist, int32_t n_hist, int32_t bins, double *table, uint8_t *flag, uint32_t *total,
@@ -235,15 +287,17 @@ extern "C" int efgh_score_soft_grad(const float *pc, int64_t pc_bstride, int64_t
                                     int64_t value_bstride, const double *P, int32_t K, const uint8_t *img, int32_t H, int32_t W,
                                     int32_t bins, float lo, float hi, double min_depth, int32_t pool, const double *table,
                                     const uint8_t *flag, const uint32_t *total, double *part, void *stream) {
-    SCORE_ARG(pc && value && P && img && table && flag && total && part,
-             "efgh_score_soft_grad: null pointer (pc %p, value %p, P %p, img %p, table %p, flag %p, total %p, part %p)", (const void *)pc,
-             (const void *)value, (const void *)P, (const void *)img, (const void *)table, (const void *)flag, (const void *)total, (void *)part);
-    float scale = 0.f;
-    if (int rc = check_points("efgh_score_soft_grad", B, N, K, H, W, bins, lo, hi, min_depth, pool, &scale)) return rc;
-    k_soft_grad<<<dim3(cdiv(N, EFGH_SCORE_CHUNK), K, B), TPB, 0, (hipStream_t)stream>>>(
-        pc, pc_bstride, pc_cstride, N, value, value_bstride, P, K, img, H, W, bins, lo, scale, min_depth, pool, table, flag, total, part);
-    EFGH_CHECK_LAUNCH();
-    return EFGH_OK;
+    return launch_soft_grad("efgh_score_soft_grad", false, pc, pc_bstride, pc_cstride, B, N, value, value_bstride, P, K, img, H, W, bins, lo,
+                            hi, min_depth, pool, table, flag, total, nullptr, part, stream);
+}
+
+extern "C" int efgh_score_soft_grad_masked(const float *pc, int64_t pc_bstride, int64_t pc_cstride, int32_t B, int32_t N,
+                                           const float *value, int64_t value_bstride, const double *P, int32_t K, const uint8_t *img,
+                                           int32_t H, int32_t W, int32_t bins, float lo, float hi, double min_depth, int32_t pool,
+                                           const double *table, const uint8_t *flag, const uint32_t *total, const uint32_t *mask,
+                                           double *part, void *stream) {
+    return launch_soft_grad("efgh_score_soft_grad_masked", true, pc, pc_bstride, pc_cstride, B, N, value, value_bstride, P, K, img, H, W,
+                            bins, lo, hi, min_depth, pool, table, flag, total, mask, part, stream);
 }
 
 extern "C" int efgh_score_soft_fold(const double *part, int32_t B, int32_t K, int32_t n_chunk, double *grad, void *stream) {

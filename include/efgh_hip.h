@@ -1152,7 +1152,8 @@ int efgh_fuse_maps(const void *zbuf, int32_t B, int64_t HW, float *depth, int32_
  * point (Pandey et al., "Automatic extrinsic calibration of vision and lidar by maximizing mutual information"), for K candidate
  * matrices per sample at once.  Not in the reference; nothing runs unless called.  pc, H, W, min_depth and the projection are those of
  * the fuse section above, P is float64 [B][K][12].  A point COUNTS iff it is in frame under its candidate and its value is not NaN.
- * There is NO occlusion test: which points a nearer surface hides changes with the candidate, and no z-buffer per candidate is built.
+ * These two entry points ask nothing about occlusion; the depth test per candidate is efgh_score_zmin / efgh_score_visible /
+ * efgh_score_hist_masked of the "visible points" section below.
  *   efgh_score_hist   zeroes hist (uint32 [B][K][bins][bins]) on the stream, then counts every point into cell [x][y]:
  *     y (grey):  L = (19595 R + 38470 G + 7471 B + 32768) >> 16 of pixel img[b][r][c] (nearest neighbour), y = (L * bins) >> 8;
  *     x (value): t = (v - lo) * scale in float32, the subtraction and the product rounded separately, scale = (float)bins /
@@ -1166,7 +1167,8 @@ int efgh_fuse_maps(const void *zbuf, int32_t B, int64_t HW, float *depth, int32_
  *     n; mi = (Hx + Hy) - Hxy, nmi = (Hx + Hy) / Hxy.  n == 0: all five are 0; Hxy == 0: nmi = 0.  Never NaN.
  * No host read, inputs never written.  EFGH_E_INVALID with a message naming the value, and nothing launched, for: a null pointer,
  * bins not one of the four, K, B, N, H, W out of range, min_depth negative or not finite, lo / hi not finite or lo >= hi.
- * MI of a sparse histogram is biased upwards when n is small: candidates with very different counts are not comparable as they are. */
+ * MI of a sparse histogram is biased upwards when n is small: candidates with very different counts are not comparable as they are
+ * (efgh_score_occupancy below counts what the Miller-Madow correction needs). */
 int32_t efgh_score_chunk(void);
 int efgh_score_hist(const float *pc, int64_t pc_bstride, int64_t pc_cstride, int32_t B, int32_t N, const float *value,
                     int64_t value_bstride, const double *P, int32_t K, const uint8_t *img, int32_t H, int32_t W, int32_t bins,
@@ -1198,7 +1200,7 @@ int efgh_score_mi(const uint32_t *hist, int32_t B, int32_t K, int32_t bins, doub
  *     the same tree -> grad f64 [B][K][12] (row-major 3x4).
  * No floating-point atomic: the same bits run to run.  An empty histogram gives a zero gradient; nothing is NaN.  The gradient is the
  * derivative of the UNQUANTISED function (q = 256 fr without the rounding) at fixed membership: it ignores points that enter or
- * leave the frame, and is zero where t is clamped.  There is no occlusion test.  EFGH_E_INVALID with a message naming the value, and
+ * leave the frame, and is zero where t is clamped.  The occlusion test is in the section below.  EFGH_E_INVALID with a message naming the value, and
  * nothing launched, for what efgh_score_hist refuses, pool not 0 / 1, N or pooled B N >= 2^23, n_hist or n_chunk out of range. */
 int efgh_score_soft_hist(const float *pc, int64_t pc_bstride, int64_t pc_cstride, int32_t B, int32_t N, const float *value,
                          int64_t value_bstride, const double *P, int32_t K, const uint8_t *img, int32_t H, int32_t W, int32_t bins,
@@ -1210,6 +1212,47 @@ int efgh_score_soft_grad(const float *pc, int64_t pc_bstride, int64_t pc_cstride
                          float lo, float hi, double min_depth, int32_t pool, const double *table, const uint8_t *flag,
                          const uint32_t *total, double *part, void *stream);
 int efgh_score_soft_fold(const double *part, int32_t B, int32_t K, int32_t n_chunk, double *grad, void *stream);
+
+/* ---- scoring on visible points only, and the Miller-Madow correction (csrc/score_vis.hip; tests/score_vis_contract.py) -------------
+ * A depth test PER CANDIDATE in front of the two histograms above, and the occupancy counts of the sparse histogram's bias
+ * correction.  Not in the reference; nothing runs unless called.  pc, P [B][K][12], H, W, min_depth and the projection are those of
+ * the sections above.  The image is cut into cells of cell_h x cell_w pixels (1 .. 64 each), clipped at the right and bottom edges:
+ * Hc = ceil(H / cell_h), Wc = ceil(W / cell_w); an in-frame point on pixel (r, c) belongs to cell (r / cell_h, c / cell_w).
+ *   efgh_score_zmin_bytes  4 B K Hc Wc, the size of zmin; -1 for sizes out of range or above 2^29 cells (a memory sanity cap).
+ *   efgh_score_zmin      sets zmin (uint32 [B][K][Hc][Wc]) to the bits of +inf (0x7f800000), then takes the unsigned minimum of the
+ *     bit pattern of d = (float)w over every point in frame under candidate (b, k) into the point's cell: positive float32 bit
+ *     patterns order like unsigned integers.  The point's value plays no part.  One 32-bit integer atomic minimum a point: the same
+ *     bits on every schedule.
+ *   efgh_score_visible   a SEPARATE launch behind it.  mask uint32 [B][K][ceil(N / 32)], bit i % 32 of word i / 32: point i is in
+ *     frame under (b, k) and (double)d <= (double)zmin (1 + rel_tol) + abs_tol, efgh_fuse_resolve's expression in its order (equal
+ *     float32 depths are all visible; cell 1 x 1 is efgh_fuse_* at radius 0).  Bits past N are zero; every word is written with a
+ *     plain store, so mask needs no initialisation.
+ *   efgh_score_hist_masked, efgh_score_soft_hist_masked, efgh_score_soft_grad_masked   the entry points above with one more
+ *     condition for a point to COUNT: its bit in mask is set.  The same kernel bodies, so everything said there holds; pooled, the
+ *     mask stays per (b, k).  Histogram and gradient share their membership by construction.
+ *   efgh_score_occupancy  one workgroup per histogram (uint32 [n_hist][bins][bins]): occ i32 [n_hist][3] = (Rx, Ry, Rxy), the
+ *     non-empty rows (value bins), columns (grey bins) and cells.  The Miller-Madow estimate is mi - (Rxy - Rx - Ry + 1) / (2 n).
+ * No host read, inputs never written.  EFGH_E_INVALID with a message naming the value, and nothing launched, for: a null pointer,
+ * what the entry points above refuse, cell_h or cell_w outside 1 .. 64, more than 2^29 cells, rel_tol / abs_tol negative or not
+ * finite. */
+int64_t efgh_score_zmin_bytes(int32_t B, int32_t K, int32_t H, int32_t W, int32_t cell_h, int32_t cell_w);
+int efgh_score_zmin(const float *pc, int64_t pc_bstride, int64_t pc_cstride, int32_t B, int32_t N, const double *P, int32_t K, int32_t H,
+                    int32_t W, int32_t cell_h, int32_t cell_w, double min_depth, uint32_t *zmin, void *stream);
+int efgh_score_visible(const float *pc, int64_t pc_bstride, int64_t pc_cstride, int32_t B, int32_t N, const double *P, int32_t K,
+                       int32_t H, int32_t W, int32_t cell_h, int32_t cell_w, double min_depth, double rel_tol, double abs_tol,
+                       const uint32_t *zmin, uint32_t *mask, void *stream);
+int efgh_score_hist_masked(const float *pc, int64_t pc_bstride, int64_t pc_cstride, int32_t B, int32_t N, const float *value,
+                           int64_t value_bstride, const double *P, int32_t K, const uint8_t *img, int32_t H, int32_t W, int32_t bins,
+                           float lo, float hi, double min_depth, const uint32_t *mask, uint32_t *hist, void *stream);
+int efgh_score_soft_hist_masked(const float *pc, int64_t pc_bstride, int64_t pc_cstride, int32_t B, int32_t N, const float *value,
+                                int64_t value_bstride, const double *P, int32_t K, const uint8_t *img, int32_t H, int32_t W,
+                                int32_t bins, float lo, float hi, double min_depth, int32_t pool, const uint32_t *mask, uint32_t *hist,
+                                void *stream);
+int efgh_score_soft_grad_masked(const float *pc, int64_t pc_bstride, int64_t pc_cstride, int32_t B, int32_t N, const float *value,
+                                int64_t value_bstride, const double *P, int32_t K, const uint8_t *img, int32_t H, int32_t W,
+                                int32_t bins, float lo, float hi, double min_depth, int32_t pool, const double *table,
+                                const uint8_t *flag, const uint32_t *total, const uint32_t *mask, double *part, void *stream);
+int efgh_score_occupancy(const uint32_t *hist, int32_t n_hist, int32_t bins, int32_t *occ, void *stream);
 
 /* ---- pose heads, forward (one launch each) -----------------------------------------------------------------------------------
  * efgh_pose_head_normal: softmax + L2 normalisation of the nd (2 or 3) "abs" logits, sign class = first argmax of the 2^nd sign
