@@ -13,7 +13,8 @@ SO = os.path.join(LIBDIR, 'libefgh_hip.so')
 EXTRA = {'lattice.hip': ['-ffp-contract=off'], 'pose.hip': ['-ffp-contract=off'], 'jitter.hip': ['-ffp-contract=off'],
          'fuse.hip': ['-ffp-contract=off'], 'score.hip': ['-ffp-contract=off'],      # score.hip: the same projection (fuse_project.h)
          'score_soft.hip': ['-ffp-contract=off'],                                   # likewise, and its float64 gradient terms
-         'score_vis.hip': ['-ffp-contract=off']}                                    # likewise, and the visibility bound's product and sum
+         'score_vis.hip': ['-ffp-contract=off'],                                    # likewise, and the visibility bound's product and sum
+         'refine.hip': ['-ffp-contract=off']}                                       # the float64 chain rule, Adam and pose product of refine_contract.py
 COMMON = ['--offload-arch=gfx950', '-O3', '-fPIC', '-std=c++17', '-Wall', '-Wno-unused-function']
 # A/B builds (tools): EFGH_BUILD_FLAGS='-DSOMETHING=1' EFGH_BUILD_DIR=lib_ab python -m efgh_amd.build -> efgh_amd/lib_ab/libefgh_hip.so (EFGH_LIB selects it)
 COMMON += os.environ.get('EFGH_BUILD_FLAGS', '').split()

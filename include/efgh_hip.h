@@ -1254,6 +1254,38 @@ int efgh_score_soft_grad_masked(const float *pc, int64_t pc_bstride, int64_t pc_
                                 const uint8_t *flag, const uint32_t *total, const uint32_t *mask, double *part, void *stream);
 int efgh_score_occupancy(const uint32_t *hist, int32_t n_hist, int32_t bins, int32_t *occ, void *stream);
 
+/* ---- climbing from many start poses at once: the device-side refinement step and the selection (csrc/refine.hip; tests/refine_contract.py) ----
+ * What `refine` does with about forty torch launches an iteration - the chain rule from dMI/dP to six rigid parameters, Adam, the
+ * next pose, the best-so-far bookkeeping - as ONE launch for every start.  Not in the reference; nothing runs unless called.  The
+ * S starts ride on the K axis of the scoring entry points above.  A parameter ROW is (b, s), row = b S + s (pool = 0), or s with one
+ * z for the whole batch (pool = 1): rows = B S or S.  All arithmetic is float64 with every operation rounded on its own; plain
+ * stores only, no atomic, one thread a row: the same bits on every run and for every grid shape.
+ *   efgh_refine_step   G, Pstart, P, best_pose f64 [B][S][12] (row-major 3x4); mi, best_mi f64 [rows]; best_iter i64 [rows]; z, m, v f64
+ *     [rows][6]; trace f64 [>= it + 1][rows].  `it` (>= 0) numbers the iterate that P holds and that mi and G were computed at.  In
+ *     this order:
+ *       1. bookkeeping: trace[it] = mi; better = it == 0 or mi > best_mi (strict: the first of equals stays, a NaN never wins); on
+ *          better, best_mi = mi, best_iter = it, best_pose = P for every b of the row.  With last = 1 the call ends here (G may be null).
+ *       2. chain rule: p = z * scale, D(p) = [Rz Ry Rx | t] (p0..2 Euler angles about x, y, z, p3..5 the translation), P = Pstart D.
+ *          dMI/dz_a = scale_a sum_b sum_ij G[b][i][j] (Pstart[b] dD/dp_a)[i][j] with the nine entries' derivatives written out; a
+ *          term whose G entry is 0 is 0 whatever Pstart holds, an axis with scale_a = 0 has gradient 0 exactly.  The terms of one b
+ *          are added in row-major order, the samples in index order.
+ *       3. Adam on -mi, lr 1, betas 0.9 / 0.999, eps 1e-8: g = -dMI/dz; m = 0.9 m + (1 - 0.9) g; v = 0.999 v + (1 - 0.999) (g g);
+ *          z = z - step_size (m / (sqrt(v) / bc2_sqrt + 1e-8)).  step_size = 1 / (1 - 0.9^(it+1)) and bc2_sqrt = sqrt(1 - 0.999^(it+1))
+ *          come BY VALUE from the host: no device pow, no upload.
+ *       4. next pose: P[b] = Pstart[b] D(z * scale) for every b of the row, entry [i][j] = (A[i][0] D[0][j] + A[i][1] D[1][j]) +
+ *          A[i][2] D[2][j], column 3 plus Pstart[i][3].  A row whose z is all zero gets Pstart itself, bit for bit.
+ *     P is read (1) and then written (4) by the same thread: the call goes behind whatever else reads P on the stream.
+ *   efgh_refine_select   one workgroup per row of val f64 [rows][K]: idx i32 [rows][keep] = the keep largest, in descending order;
+ *     equal values by ascending index; a NaN ranks below every number (NaNs among themselves by index).  K <= 4096, keep <= min(K, 64).
+ * EFGH_E_INVALID with a message naming the entry point and the value, and nothing launched, for: a null pointer, B outside
+ * 1 .. 65535, S outside 1 .. 4096, pool / last not 0 / 1, it < 0, a scale that is negative or not finite, step_size or bc2_sqrt not
+ * finite and positive; rows outside 1 .. 65535, K outside 1 .. 4096, keep outside 1 .. min(K, 64). */
+int efgh_refine_step(const double *G, const double *Pstart, double *P, const double *mi, int32_t B, int32_t S, int32_t pool, double *z,
+                     double *m, double *v, double *best_mi, int64_t *best_iter, double *best_pose, double *trace, double scale0,
+                     double scale1, double scale2, double scale3, double scale4, double scale5, int32_t it, double step_size,
+                     double bc2_sqrt, int32_t last, void *stream);
+int efgh_refine_select(const double *val, int32_t rows, int32_t K, int32_t keep, int32_t *idx, void *stream);
+
 /* ---- pose heads, forward (one launch each) -----------------------------------------------------------------------------------
  * efgh_pose_head_normal: softmax + L2 normalisation of the nd (2 or 3) "abs" logits, sign class = first argmax of the 2^nd sign
  *   logits decoded MSB-first, normal = abs * sign, rotation of the normal onto (dx,dy,dz) as a 4x4 (enet.py:161-176, hnet.py:59-77,
